@@ -19,6 +19,10 @@ The JSON line (rank 0) carries
 * `c3` / `c4`: BASELINE configs[2] and [3] (FASTQ 100 M x 150 bp; the C2 bytes BGZF-framed) with their
   dominant-kernel rooflines and the reference beside them on a stated sample.
 
+A plain run (one GPU) prints only the contract keys: set-up, warm-up, the timed steps and, with
+`--dump-outputs DIR`, what the last step computed.  Everything else above, and the full-size parity
+checks, run with `--full`.
+
 N > 1: one process per GPU, ONE file sharded by byte range (configs[4] shape): every rank reads only its
 own range (+ nothing else: bytes never move between GPUs), one all-gather of the 28-word boundary
 summaries stitches the record that crosses each cut.
@@ -70,6 +74,9 @@ def parse():
     ap.add_argument("--c4-ref-queries", type=int, default=100_000, help="queries of the C4 leg that the reference answers too (ascending offsets, through its restart points)")
     ap.add_argument("--c4-reference-full", action="store_true", help="ALL queries of the C4 leg through the reference (builder-run: profiles/r06_c4_full_reference.json; minutes of one core)")
     ap.add_argument("--pmc-file", default=None, help=argparse.SUPPRESS)                  # the counter passes' child opens this file instead of generating the stream
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline step (one GPU): full-size parity, per-kernel times and rooflines, "
+                                                        "the end-to-end file leg, the CPU baseline, the counter passes, the C3 / C4 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps (one GPU), write what the last step computed as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -1518,9 +1525,28 @@ def _emit(line):
         data = data[os.write(_LINE_FD, data):]
 
 
+DUMP_QUERIES = 65536                                         # answers written by --dump-outputs: 65536 x 100 bases as float32 = 26 MB
+
+
+def dump_outputs(d, job, d_out, d_len, n_queries, qlen):
+    """--dump-outputs: what the timed step hands its caller after the last step, as DIR/<name>.npy -- every column of the
+    record table (float64: offsets pass 2^24) and, for a fixed seeded sample of the batch's queries, the answer's length
+    and its bases (float32), so that two builds run with the same arguments can be compared output for output."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    for k, v in job.local_rows().items():
+        np.save(os.path.join(d, "index_%s.npy" % k), v.astype(np.float64))
+    pick = np.sort(np.random.default_rng(4242).choice(n_queries, min(n_queries, DUMP_QUERIES), replace=False))
+    idx = torch.from_numpy(pick).to(d_out.device)
+    np.save(os.path.join(d, "fetch_len.npy"), d_len[idx].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "fetch_bases.npy"), d_out.view(n_queries, qlen)[idx].cpu().numpy().astype(np.float32))
+
+
 # ------------------------------------------------------------------------------------------ main
 def main():
     a = parse()
+    if a.dump_outputs and (a.gpus > 1 or a.scaling == "strong" or os.environ.get("FX_BENCH_FORCE_SHARDED")):
+        raise SystemExit("--dump-outputs: only the single-GPU weak run writes its outputs")
     if a.pmc_child and a.pmc_file:                           # one counter pass of live_pmc_traffic: the file, three builds, nothing else in the process
         os.environ["FX_NO_TORCH"] = "1"
         from pyfastx_amd import _lib
@@ -1591,7 +1617,7 @@ def main():
     # ---------------- workload: the whole stream, resident in HBM
     total_bp = int(a.gbp * 1e9)
     plan = synth.fasta_plan(total_bp=total_bp, seed=20260612)      # (N > 1 never gets here: main_sharded / main_strong above)
-    blob, flat, flat_start = synth.fasta_generate(plan, dev, keep_flat=not a.no_verify)
+    blob, flat, flat_start = synth.fasta_generate(plan, dev, keep_flat=a.full and not a.no_verify)
     q = synth.fasta_queries(plan, n=a.queries, seed=12345)
     ids, st, sp, strand = q
     qlen = int(sp[0] - st[0])
@@ -1621,7 +1647,7 @@ def main():
 
     for _ in range(a.warmup):
         step()
-    job.blob.prof_enable(2)                               # events around the dominant kernel only (k_span_scan)
+    job.blob.prof_enable(2)                               # events around the dominant kernel only (k_span_scan; on in a plain run too: the same timed region)
     job.blob.prof_reset()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -1629,9 +1655,23 @@ def main():
         step()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
+    el = t1 - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, job, d_out, d_len, a.queries, qlen)
+    line = {
+        "metric": "FASTA index build + 1M random 100bp subseq fetches, 3 Gbp plain FASTA per GPU (throughput of the whole step, stream resident in HBM)",
+        "value": round(world * a.gbp / (el / a.steps), 3), "unit": "Gbp/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(el / a.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": "configs[1]: synthetic %.1f Gbp hg38-shaped plain FASTA per GPU (200 contigs, 60-col LF, soft-masked, N runs), "
+                               "index build + %d random %d bp intervals (50%% '-' strand)" % (a.gbp, a.queries, qlen),
+                   "file_bytes_per_gpu": int(plan["n_bytes"]), "parallelism": "one GPU, the whole stream resident in its HBM"},
+    }
+    if not a.full:
+        _emit(line)
+        return
     # the index build on its own (its own synchronisation), outside the timed region: the first half of the metric
-    t_index = sum(build_only() for _ in range(a.steps))
-    el, ti = t1 - t0, t_index
+    ti = sum(build_only() for _ in range(a.steps))
     prof = job.blob.prof_read()
     # per-kernel table from a separate, untimed pass (timing every kernel costs ~20 events per step)
     job.blob.prof_enable(1)
@@ -1697,21 +1737,13 @@ def main():
                       "rows_equal": True}
         del d_comp2
 
-    ms = el / a.steps * 1e3
     shard_bytes = job.n_bytes
     fetch_ms = sum(prof_all.get(k, (0.0, 1))[0] / max(prof_all.get(k, (0.0, 1))[1], 1) for k in ("k_fetch", "k_fetch_rest"))   # kernel time of one batch: the line-arithmetic kernel + the general one over its leftovers
     scan_ms, scan_n = prof.get("k_span_scan", (0.0, 0))
     scan_avg = scan_ms / max(scan_n, 1)
     achieved = shard_bytes / (scan_avg * 1e-3) / 1e9 if scan_avg > 0 else 0.0
     fetch_alg = 234 * a.queries                           # ~102 B read + 100 B written + 32 B descriptor / offset per query
-    line = {
-        "metric": "FASTA index build + 1M random 100bp subseq fetches, 3 Gbp plain FASTA per GPU (throughput of the whole step, stream resident in HBM)",
-        "value": round(world * a.gbp / (el / a.steps), 3), "unit": "Gbp/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-        "config": {"workload": "configs[1]: synthetic %.1f Gbp hg38-shaped plain FASTA per GPU (200 contigs, 60-col LF, soft-masked, N runs), "
-                               "index build + %d random %d bp intervals (50%% '-' strand)" % (a.gbp, a.queries, qlen),
-                   "file_bytes_per_gpu": int(plan["n_bytes"]), "parallelism": "one GPU, the whole stream resident in its HBM"},
+    line.update({
         "index_build_s": round(ti / a.steps, 6),
         "fetch_M_per_s": round(world * a.queries / max(fetch_ms * 1e-3, 1e-9) / 1e6, 2),
         "parity_verified_full_size": verified,
@@ -1726,7 +1758,7 @@ def main():
         "roofline_fetch": {"kernel": "fx::k_fetch_lines<4,1> (+ fx::k_fetch<true,4,16> over what it leaves over)", "bound": "hbm", "algorithmic_bytes_per_launch": fetch_alg,
                            "avg_launch_ms": round(fetch_ms, 4),
                            "frac": round(fetch_alg / max(fetch_ms * 1e-3, 1e-9) / 1e9 / HBM_PEAK_GBS, 4)},
-    }
+    })
     _lap("generate + timed steps + parity at full size")
     if True:
         # release the device-resident copies before the file legs (the same bytes go to a file first)

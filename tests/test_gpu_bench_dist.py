@@ -197,7 +197,7 @@ print("FX_COMM_OK")
 
 
 def test_bench_single_small():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--gbp", "0.05",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--gbp", "0.05",
            "--queries", "20000", "--c3-reads", "2e5", "--c3-sample", "5e4"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -219,6 +219,35 @@ def test_bench_single_small():
     r = line["roofline"]
     assert r["traffic_source"].startswith("measured in this run"), r["traffic_source"]
     assert 0.5 * r["algorithmic_bytes_per_launch"] < r["traffic"] < 2.0 * r["algorithmic_bytes_per_launch"]
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain run prints the contract keys and nothing else; --dump-outputs writes what the last timed step computed: the
+    record table (against the generator's analytic rows) and a sample of the answers -- the same files in two runs."""
+    import numpy as np
+    from pyfastx_amd import synth
+    keys = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config"}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--gbp", "0.05",
+               "--queries", "20000", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = _last_json(out)
+        assert set(line) == keys and line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+        files = {p.name: np.load(p) for p in sorted(d.iterdir())}
+        assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+        assert sum(v.nbytes for v in files.values()) <= 64 << 20
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    f = dumps[0]
+    plan = synth.fasta_plan(total_bp=int(0.05e9), seed=20260612)
+    for k in ("hoff", "boff", "blen", "slen", "llen", "dlen", "name_len"):
+        assert np.array_equal(f["index_%s.npy" % k], plan[k].astype(np.float64)), k
+    assert f["fetch_len.npy"].shape == (20000,) and (f["fetch_len.npy"] == 100).all()
+    assert f["fetch_bases.npy"].shape == (20000, 100) and np.isin(f["fetch_bases.npy"], np.frombuffer(b"ACGTNacgtn", np.uint8)).all()
 
 
 def test_bench_sharded_path_over_nccl_with_one_rank():

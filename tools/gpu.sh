@@ -4,7 +4,7 @@
 # steps (any order, any subset; a step's arguments follow it as step:arg1:arg2):
 #   pytest:<file>[:<file>...]  some test files (-m gpu)
 #   tests          pytest -m gpu                           smoke       __graft_entry__.smoke()
-#   bench          the driver's default bench line, timed  prof        the same command under rocprofv3 --kernel-trace --stats
+#   bench          the bench line with every leg, timed   prof        the same command under rocprofv3 --kernel-trace --stats
 #   bench_c3full   the bench with the reference on the WHOLE configs[2] file (10^8 reads: ~3 minutes of one core)
 #   bench_c4full   the bench with ALL 1 M queries of the C4 leg answered by the reference too (builder-run evidence)
 #   bench8         the driver's --gpus 8 command shape on this ONE device (gloo; all ranks share it)
@@ -37,14 +37,14 @@ for STEP in "$@"; do
   pytest) FILES=""; for f in $A1 $A2 $A3 $A4 $A5 $A6 $A7 $A8; do FILES="$FILES tests/$f"; done
     ( time timeout 1800 python -m pytest $FILES -m gpu -x -q ) > $OUT/pytest_${A1%.py}.log 2>&1; tail -15 $OUT/pytest_${A1%.py}.log | grep -v "^$" | tail -12 ;;
   smoke) ( timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ) > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log ;;
-  bench) ( time timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench.time; cat $OUT/bench.time; cut -c1-800 $OUT/bench.json ;;
+  bench) ( time timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench.time; cat $OUT/bench.time; cut -c1-800 $OUT/bench.json ;;
   prof)
-    ( time timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o trace -- python bench.py --no-pmc --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err ) 2> $OUT/prof.time; cat $OUT/prof.time
+    ( time timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o trace -- python bench.py --full --no-pmc --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err ) 2> $OUT/prof.time; cat $OUT/prof.time
     DB=$(find $OUT/prof -name '*.db' | head -1)
     [ -n "$DB" ] && python tools/rocprof_summary.py $DB $OUT/kernel_stats.txt && grep 'fx::' $OUT/kernel_stats.txt | head -80
     rm -rf $OUT/prof ;;
-  bench_c3full) ( time timeout 2700 python bench.py --c3-reference-full --no-c4 > $OUT/bench_c3full.json 2> $OUT/bench_c3full.err ) 2> $OUT/bench_c3full.time; cat $OUT/bench_c3full.time; python -c "import json; d=json.loads([l for l in open('$OUT/bench_c3full.json') if l.startswith('{')][-1]); print(json.dumps(d['c3']['e2e_full'])[:3500])" ;;
-  bench_c4full) ( time timeout 2400 python bench.py --c4-reference-full --no-c3 > $OUT/bench_c4full.json 2> $OUT/bench_c4full.err ) 2> $OUT/bench_c4full.time; cat $OUT/bench_c4full.time; python -c "import json; d=json.loads([l for l in open('$OUT/bench_c4full.json') if l.startswith('{')][-1]); print(json.dumps(d['c4'])[:3000])" ;;
+  bench_c3full) ( time timeout 2700 python bench.py --full --c3-reference-full --no-c4 > $OUT/bench_c3full.json 2> $OUT/bench_c3full.err ) 2> $OUT/bench_c3full.time; cat $OUT/bench_c3full.time; python -c "import json; d=json.loads([l for l in open('$OUT/bench_c3full.json') if l.startswith('{')][-1]); print(json.dumps(d['c3']['e2e_full'])[:3500])" ;;
+  bench_c4full) ( time timeout 2400 python bench.py --full --c4-reference-full --no-c3 > $OUT/bench_c4full.json 2> $OUT/bench_c4full.err ) 2> $OUT/bench_c4full.time; cat $OUT/bench_c4full.time; python -c "import json; d=json.loads([l for l in open('$OUT/bench_c4full.json') if l.startswith('{')][-1]); print(json.dumps(d['c4'])[:3000])" ;;
   bench8) ( time FX_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 8 > $OUT/bench8.json 2> $OUT/bench8.err ) 2> $OUT/bench8.time; cat $OUT/bench8.time; python -c "import json,sys; d=json.loads([l for l in open('$OUT/bench8.json') if l.startswith('{')][-1]); print(json.dumps(d.get('fastq_strong')))"; tail -3 $OUT/bench8.err ;;
   counters) rocprofv3 -L > $OUT/counters.txt 2>&1; grep -c . $OUT/counters.txt ;;
   valuprobe)
@@ -91,7 +91,7 @@ for STEP in "$@"; do
       pmc_fq) P="python tools/fq_build_bench.py ${A1:-2e7}"; F=k_fastq ;;
       pmc_fq_one) P="python tools/fq_one_probe.py ${A1:-2e7}"; F=k_fastq ;;
       pmc_fqcomp) P="python tools/fq_comp_probe.py ${A1:-1e7}"; F=k_fastq_comp ;;
-      pmc_comp) P="python bench.py --no-pmc --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-c3 --no-c4"; F=${A1:-k_} ;;
+      pmc_comp) P="python bench.py --full --no-pmc --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-c3 --no-c4"; F=${A1:-k_} ;;
       pmc_fetch) P="python tools/fetch_probe.py 3.0 2e7"; F=fetch ;;
       pmc_fxi) P="python tools/fxi_pmc_probe.py ${A1:-2e7}"; F=k_fxi ;;
       pmc_sort) P="python tools/sort_probe.py ${A1:-1e8}"; F=k_ ;;
