@@ -309,6 +309,31 @@ int fx_fasta_fetch_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const i
  * enqueued, [4] answers back (second wait), [5] the whole call. */
 int fx_fetch_phases(double *ms, int cap);
 
+/* ------------------------------------------------------------------ search
+ * Extension (the reference answers only Sequence.search, sequence.c:519-558: the first hit in one record, str.find on a
+ * host copy).  Every OVERLAPPING hit of one pattern of 1..64 letters in the `seq` of the records -- what fx_fasta_fetch
+ * returns for the whole record: bytes 10/13/32 dropped, Py_TOUPPER'd under FX_SEARCH_UPPER, cut at slen -- two passes over
+ * the resident stream and a device scan between them (pyfastx_amd/csrc/fx_search.hpp).  No hit crosses from one record
+ * into the next.
+ *   pat / rpat   the patterns of the + and of the - strand (plen letters each; rpat is the caller's reverse complement of
+ *                pat: fx_revcomp for an exact pattern, the IUPAC complement for a degenerate one); either may be NULL when
+ *                its strand is not asked for.
+ *   mode         FX_SEARCH_PLUS / FX_SEARCH_MINUS: the strands; FX_SEARCH_UPPER: the text as Fasta(uppercase=True)
+ *                presents it; FX_SEARCH_DEGENERATE: pattern letters are IUPAC codes (any case, U = T) and a text letter
+ *                matches when it is an IUPAC letter whose base set lies inside the pattern letter's (other bytes match
+ *                nothing).  Exact mode compares bytes.
+ *   ids, n_ids   the records to search (0-based, ascending for file order; NULL: all of them).
+ *   cap          room for hits.  *n_hits = the number of hits; above cap: FX_ERANGE and nothing is allocated.  cap = 0
+ *                with counts != NULL: counts only.
+ *   rec, start, strand   the hits, by (record, start), '+' before '-' at one start: record id, 0-based start of the
+ *                occurrence on the forward strand (stop = start + plen) for both strands, '+' / '-'; pinned blocks of
+ *                fx_pinned_alloc that belong to the caller (fx_pinned_free each).
+ *   counts       optional host array [n_sel][2]: hits per searched record on + and on -.
+ * Whole streams only: a byte-range shard (fx_set_shard, fx_open_file_range) gives FX_EINVAL. */
+enum { FX_SEARCH_DEGENERATE = 1, FX_SEARCH_UPPER = 2, FX_SEARCH_PLUS = 4, FX_SEARCH_MINUS = 8 };
+int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, const int64_t *ids, int64_t n_ids,
+                    int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int64_t *n_hits, int64_t *counts);
+
 /* FASTQ reads by 0-based id (read.c:37-45, 152-167, 237-278): seq and qual
  * are rlen bytes each at dst_off[i]; quali = qual - phred as int8
  * (phred 0 -> 33, read.c:268).  Any of seq/qual/quali may be NULL. */

@@ -820,6 +820,39 @@ class Fasta(_fxobj.FastaCore):
             return buf, offs
 
 
+    def search_all(self, pattern, strand="both", degenerate=False, ids=None, max_hits=10**8):
+        """Extension: every overlapping hit of `pattern` (1..64 letters) in the `seq` of every record -- what fa[i].seq
+        presents: white space dropped, upper case under uppercase=True -- on strand '+', '-' or 'both'.  Exact by default
+        (the '-' pattern is the reverse complement Sequence.search uses); degenerate=True reads the pattern as IUPAC codes
+        (a text letter matches when its base set lies inside the pattern letter's).  -> SearchHits(ids, starts, stops,
+        strands) of numpy arrays in pinned memory, 0-based half-open forward-strand coordinates as fetch_many takes them,
+        ordered by (record, start), '+' before '-' at one start.  ids: restrict to these records (names or 0-based ids).
+        More than max_hits hits: ValueError with the count, nothing allocated.  Two passes over the resident stream on
+        the GPU (csrc/fx_search.hpp)."""
+        from . import search
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        blob = self._search_blob()
+        return search.search_blob(blob, pattern, strand, degenerate, self._uppercase, sel, max_hits, self._st.device)
+
+    def search_counts(self, pattern, strand="both", degenerate=False):
+        """Extension: hits of search_all per record -> int64[len(fa), 2] (column 0 '+', column 1 '-'); the hits themselves
+        are never materialised."""
+        from . import search
+        blob = self._search_blob()
+        return search.count_blob(blob, pattern, strand, degenerate, self._uppercase, self._st.device)
+
+    def _search_blob(self):
+        """The blob with the record table resident (installed once from the .fxi, as fetch_many does); a sharded or windowed
+        stream has no halo for hits that straddle its cuts."""
+        self._need_index()
+        if self._sharded:
+            raise NotImplementedError("search on a sharded or windowed stream: a hit can straddle a cut")
+        blob = self._st.blob
+        if not getattr(blob, "_table_ready", False):
+            t = self._table()
+            blob.fasta_set_table(t["boff"], t["blen"], t["slen"], t["llen"], t["elen"], t["norm"])
+        return blob
+
     def _ids_of(self, names_or_ids):
         """Sequence names or 0-based ids -> int64 ids (KeyError / IndexError as the subscript raises them)."""
         first = names_or_ids[0] if len(names_or_ids) else 0

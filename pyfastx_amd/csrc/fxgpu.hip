@@ -42,6 +42,7 @@
 #include "fx_pgzip.hpp"
 #include "fx_sort.hpp"
 #include "fx_kseq.hpp"
+#include "fx_search.hpp"
 
 using namespace fx;
 
@@ -318,10 +319,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit"};
 
 struct Prof {
     bool on = false;
@@ -3445,6 +3446,164 @@ extern "C" int fx_fasta_fetch_alloc(fx_handle *h, int64_t n, const int64_t *seq_
     h->prof.drain();
     *dst = out; *dst_off = offs;
     pc.done();
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ search (fx_search.hpp)
+// Shift-And masks of every byte value: bit j of .x (.y) is set when the byte matches letter j of the forward (reverse)
+// pattern.  Exact: byte equality with the byte as `seq` presents it (Py_TOUPPER first under FX_SEARCH_UPPER).  Degenerate:
+// the byte is an IUPAC letter whose base set lies inside the pattern letter's.
+static uint8_t iupac_set(uint8_t c) {
+    switch (c & 0xDF) {
+    case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': case 'U': return 8;
+    case 'R': return 5; case 'Y': return 10; case 'S': return 6; case 'W': return 9; case 'K': return 12; case 'M': return 3;
+    case 'B': return 14; case 'D': return 13; case 'H': return 11; case 'V': return 7; case 'N': return 15;
+    default: return 0;
+    }
+}
+static bool search_masks(const uint8_t *pat, int plen, int mode, uint64_t *fwd) {
+    const bool deg = mode & FX_SEARCH_DEGENERATE;
+    for (int j = 0; j < plen; ++j) if (deg && !iupac_set(pat[j])) return false;
+    for (int c = 0; c < 256; ++c) {
+        uint64_t m = 0;
+        const uint8_t t = (mode & FX_SEARCH_UPPER) && c >= 'a' && c <= 'z' ? (uint8_t)(c - 32) : (uint8_t)c;
+        const uint8_t ts = c < 128 ? iupac_set((uint8_t)c) : 0;
+        for (int j = 0; j < plen; ++j) {
+            const bool hit = deg ? (ts && !(ts & ~iupac_set(pat[j]))) : t == pat[j];
+            if (hit) m |= 1ull << j;
+        }
+        fwd[c] = m;
+    }
+    return true;
+}
+
+extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, const int64_t *ids,
+                               int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int64_t *n_hits,
+                               int64_t *counts) {
+    if (!h || !n_hits) return fail(FX_EINVAL, "null argument");
+    *n_hits = 0;
+    if (rec) *rec = nullptr; if (start) *start = nullptr; if (strand) *strand = nullptr;
+    if (plen < 1 || plen > 64) return fail(FX_EINVAL, "pattern length %d outside 1..64", (int)plen);
+    if (!(mode & (FX_SEARCH_PLUS | FX_SEARCH_MINUS))) return fail(FX_EINVAL, "no strand selected");
+    if (((mode & FX_SEARCH_PLUS) && !pat) || ((mode & FX_SEARCH_MINUS) && !rpat)) return fail(FX_EINVAL, "null pattern");
+    const bool counts_only = cap == 0 && counts;
+    if (cap < 0 || (!counts_only && (!rec || !start || !strand))) return fail(FX_EINVAL, "null output");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for hits across its cuts");
+    int rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (rc) return rc;
+    std::vector<ulonglong2> masks(256);
+    {
+        std::vector<uint64_t> f(256, 0), r(256, 0);
+        if (((mode & FX_SEARCH_PLUS) && !search_masks(pat, plen, mode, f.data())) ||
+            ((mode & FX_SEARCH_MINUS) && !search_masks(rpat, plen, mode, r.data())))
+            return fail(FX_EINVAL, "a pattern letter is not an IUPAC code");
+        for (int c = 0; c < 256; ++c) masks[c] = make_ulonglong2(f[c], r[c]);
+    }
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    for (int64_t k = 0; ids && k < n_ids; ++k)
+        if (ids[k] < 0 || ids[k] >= h->n_hdr) return fail(FX_ERANGE, "record id %lld outside the table", (long long)ids[k]);
+    if (n_sel == 0) return FX_OK;
+    Staged st(h);
+    SearchPlan P;
+    P.mis = (int64_t)((uintptr_t)h->d_data & 15);
+    P.base = h->d_data - P.mis;
+    P.n = h->n;
+    P.boff = h->fa_boff.p; P.blen = h->fa_blen.p; P.slen = h->fa_slen.p;
+    P.n_sel = n_sel; P.plen = plen;
+    P.sel = nullptr; P.run0 = nullptr; P.n_runs = 0;
+    const ulonglong2 *d_masks = nullptr;
+    if ((rc = st.up(h, masks.data(), 256, &d_masks)) || (rc = st.up(h, ids, n_ids, &P.sel))) return rc;
+    P.masks = d_masks;
+    const bool wide = plen > 32;
+    int64_t *tot = (int64_t *)fx_pinned_alloc(64);
+    if (!tot) return FX_ENOMEM;
+    std::unique_ptr<int64_t, void (*)(int64_t *)> tot_guard(tot, [](int64_t *p) { fx_pinned_free(p); });
+    int64_t *d_tot = nullptr;
+    if ((rc = st.scratch<int64_t>(8, &d_tot))) return rc;
+    // an exclusive scan of C components over n elements -> out (C arrays of n + 1), totals -> d_tot
+    auto scan = [&](auto ld, auto cc, int64_t n, int64_t *out) -> int {
+        constexpr int C = decltype(cc)::value;
+        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
+        int64_t *sums = nullptr;
+        int r2 = st.scratch<int64_t>(nch * C, &sums);
+        if (r2) return r2;
+        FX_LAUNCH(h, K_SEARCH_SCAN, (k_sscan_sums<C, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums);
+        FX_LAUNCH(h, K_SEARCH_SCAN, (k_sscan_top<C>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
+        FX_LAUNCH(h, K_SEARCH_SCAN, (k_sscan_apply<C, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, (const int64_t *)sums, out);
+        HIPCHK(hipGetLastError());
+        return FX_OK;
+    };
+    using C1 = std::integral_constant<int, 1>;
+    using C3 = std::integral_constant<int, 3>;
+    auto read_tot = [&](int k) -> int {
+        HIPCHK(hipMemcpyAsync(tot, d_tot, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return FX_OK;
+    };
+    // 1. runs of every selected record -> run0
+    int64_t *run0 = nullptr;
+    if ((rc = st.scratch<int64_t>(n_sel + 1, &run0))) return rc;
+    if ((rc = scan(SrchLdRuns{P}, C1{}, n_sel, run0)) || (rc = read_tot(1))) return rc;
+    P.run0 = run0;
+    P.n_runs = tot[0];
+    if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one search grid");
+    int64_t *cnt_dev = nullptr;
+    if (P.n_runs == 0) {                       // nothing but empty records
+        if (counts) memset(counts, 0, (size_t)n_sel * 16);
+        return FX_OK;
+    }
+    // 2. count pass, kept-byte scan, the cut at slen, hit scans
+    ScratchBuf<uint32_t> packed;
+    ScratchBuf<int64_t> pref;                  // K, Pp, Pm, NZ: 4 x (n_runs + 1)
+    const int64_t nr1 = P.n_runs + 1;
+    if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, 4 * nr1, h->stream))) return rc;
+    int64_t *K = pref.p, *Pp = pref.p + nr1, *Pm = pref.p + 2 * nr1, *NZ = pref.p + 3 * nr1;
+    const unsigned grid_runs = nblocks(P.n_runs, BLOCK), grid_sel = nblocks(n_sel, BLOCK);
+    if (wide) FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<true>, dim3(grid_runs), dim3(BLOCK), P, packed.p);
+    else      FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<false>, dim3(grid_runs), dim3(BLOCK), P, packed.p);
+    if ((rc = scan(SrchLdKept{packed.p}, C1{}, P.n_runs, K))) return rc;
+    if (wide) FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<true>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p);
+    else      FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<false>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p);
+    if ((rc = scan(SrchLdHits{packed.p}, C3{}, P.n_runs, Pp))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
+    if (counts) {
+        if ((rc = st.scratch<int64_t>(2 * n_sel, &cnt_dev))) return rc;
+        FX_LAUNCH(h, K_SEARCH_SCAN, k_search_rec_counts, dim3(grid_sel), dim3(BLOCK), (const int64_t *)run0, n_sel, (const int64_t *)Pp,
+                  (const int64_t *)Pm, cnt_dev);
+        HIPCHK(hipMemcpyAsync(counts, cnt_dev, (size_t)n_sel * 16, hipMemcpyDeviceToHost, h->stream));
+    }
+    if ((rc = read_tot(3))) return rc;
+    const int64_t total = tot[0] + tot[1], n_list = tot[2];
+    *n_hits = total;
+    if (counts_only) { h->prof.drain(); return FX_OK; }
+    if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
+    // 3. emit: the runs with hits, at their offsets; the answers home by DMA into pinned blocks
+    int64_t *p_rec = (int64_t *)fx_pinned_alloc(std::max<int64_t>(total, 1) * 8), *p_start = (int64_t *)fx_pinned_alloc(std::max<int64_t>(total, 1) * 8);
+    uint8_t *p_strand = (uint8_t *)fx_pinned_alloc(std::max<int64_t>(total, 1));
+    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_rec); fx_pinned_free(p_start); fx_pinned_free(p_strand); return code; };
+    if (!p_rec || !p_start || !p_strand) return bail(fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total));
+    if (total > 0) {
+        ScratchBuf<int64_t> out64, list;
+        ScratchBuf<uint8_t> out8;
+        if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out8.alloc(h->device, total, h->stream)) ||
+            (rc = list.alloc(h->device, n_list, h->stream)))
+            return bail(rc);
+        hipLaunchKernelGGL(k_search_list, dim3(grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
+        if (wide) FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<true>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
+                            (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
+        else      FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<false>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
+                            (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(p_rec, out64.p, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(p_start, out64.p + total, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(p_strand, out8.p, (size_t)total, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "search emit: %s", hipGetErrorString(e)));
+    }
+    h->prof.drain();
+    *rec = p_rec; *start = p_start; *strand = p_strand;
     return FX_OK;
 }
 

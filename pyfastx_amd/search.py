@@ -1,0 +1,95 @@
+"""Genome-wide motif search on the resident stream (extension; the reference only has Sequence.search, sequence.c:519-558).
+
+Fasta.search_all / search_counts check the pattern here and hand it to fx_fasta_search (csrc/fx_search.hpp): every
+overlapping hit in the `seq` of the records, on one or both strands, exact or with IUPAC codes."""
+from collections import namedtuple
+
+import numpy as np
+
+from . import _lib
+
+SearchHits = namedtuple("SearchHits", ["ids", "starts", "stops", "strands"])
+
+MAX_PATTERN = 64
+
+# the base set of every IUPAC letter (U is T)
+IUPAC = {k: frozenset(v) for k, v in {
+    "A": "A", "C": "C", "G": "G", "T": "T", "U": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC",
+    "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}.items()}
+_IUPAC_COMP = {"A": "T", "T": "A", "U": "A", "C": "G", "G": "C", "R": "Y", "Y": "R", "K": "M", "M": "K", "B": "V", "V": "B",
+               "D": "H", "H": "D", "S": "S", "W": "W", "N": "N"}
+_STRANDS = {"+": _lib.FX_SEARCH_PLUS, "-": _lib.FX_SEARCH_MINUS, "both": _lib.FX_SEARCH_PLUS | _lib.FX_SEARCH_MINUS}
+_SPACE = frozenset(b" \t\n\r\v\f")
+
+
+def iupac_set(letter):
+    """Base set of one IUPAC letter (any case) -> frozenset of 'ACGT'; KeyError for anything else."""
+    return IUPAC[letter.upper()]
+
+
+def iupac_revcomp(pattern):
+    """The '-' strand of a degenerate pattern: the reverse of its IUPAC complement (upper case)."""
+    return "".join(_IUPAC_COMP[c] for c in reversed(pattern.upper()))
+
+
+def _as_text(pattern):
+    return pattern.decode("latin-1") if isinstance(pattern, (bytes, bytearray)) else str(pattern)
+
+
+def compile_pattern(pattern, strand="both", degenerate=False, device=0):
+    """Check a pattern -> (mode bits, bytes searched on +, bytes searched on -); ValueError for a length outside 1..64, a
+    white-space byte in an exact pattern, a non-IUPAC letter in a degenerate one, or a bad strand.  The '-' pattern of an
+    exact search is made by fx_revcomp, as Sequence.search makes it."""
+    if strand not in _STRANDS:
+        raise ValueError("strand must be '+', '-' or 'both', not %r" % (strand,))
+    text = _as_text(pattern)
+    if not 1 <= len(text) <= MAX_PATTERN:
+        raise ValueError("pattern length %d outside 1..%d" % (len(text), MAX_PATTERN))
+    mode = _STRANDS[strand]
+    if degenerate:
+        bad = [c for c in text if c.upper() not in IUPAC]
+        if bad:
+            raise ValueError("%r is not an IUPAC nucleotide code" % bad[0])
+        fwd = text.upper().encode("latin-1")
+        rev = iupac_revcomp(text).encode("latin-1") if mode & _lib.FX_SEARCH_MINUS else None
+        return mode | _lib.FX_SEARCH_DEGENERATE, fwd, rev
+    try:
+        fwd = text.encode("latin-1")
+    except UnicodeEncodeError:
+        raise ValueError("pattern holds a character outside latin-1")
+    if any(b in _SPACE for b in fwd):
+        raise ValueError("white space in an exact pattern never matches `seq`")
+    rev = _lib.revcomp_bytes(fwd, _lib.FX_REVERSE | _lib.FX_COMPLEMENT, device) if mode & _lib.FX_SEARCH_MINUS else None
+    return mode, fwd, rev
+
+
+def search_blob(blob, pattern, strand="both", degenerate=False, uppercase=False, ids=None, max_hits=10**8, device=0):
+    """Every hit on a Blob whose FASTA table is resident -> SearchHits (arrays in pinned memory).  ids: ascending 0-based
+    record ids or None for all."""
+    mode, fwd, rev = compile_pattern(pattern, strand, degenerate, device)
+    if uppercase:
+        mode |= _lib.FX_SEARCH_UPPER
+    if max_hits < 0:
+        raise ValueError("max_hits must not be negative")
+    try:
+        total, hits, _ = blob.fasta_search(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, ids=ids, cap=int(max_hits))
+    except _lib.FxError as e:
+        if e.code == _lib.FX_ERANGE and getattr(e, "n_hits", 0) > max_hits:
+            raise ValueError("%d hits, more than max_hits=%d" % (e.n_hits, max_hits))
+        raise
+    if hits is None:
+        z = np.zeros(0, dtype=np.int64)
+        return SearchHits(z, z.copy(), z.copy(), np.zeros(0, dtype=np.uint8))
+    rec, starts, strands = hits
+    stops = _lib.pinned_empty(total, np.int64)
+    np.add(starts, len(fwd), out=stops)
+    return SearchHits(rec, starts, stops, strands)
+
+
+def count_blob(blob, pattern, strand="both", degenerate=False, uppercase=False, device=0):
+    """Hits per record on + and on - -> int64[n_records, 2]; the hits themselves never leave the device."""
+    mode, fwd, rev = compile_pattern(pattern, strand, degenerate, device)
+    if uppercase:
+        mode |= _lib.FX_SEARCH_UPPER
+    _, _, counts = blob.fasta_search(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, cap=0, counts=True)
+    return counts
