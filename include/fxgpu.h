@@ -346,6 +346,36 @@ int fx_fastq_fetch(fx_handle *h, int where, int64_t n, const int64_t *read_id,
 int fx_fastq_fetch_alloc(fx_handle *h, int64_t n, const int64_t *read_id, int phred, int seq_flags, int want,
                          uint8_t **seq, uint8_t **qual, int8_t **quali, int64_t **dst_off, int64_t *first_bad);
 
+/* ------------------------------------------------------------------ FASTQ quality control
+ * Extension (the reference answers whole-file questions only: composition, the quality range, the length range,
+ * fastq.c:715-753).  Three passes over the resident stream and its read table (pyfastx_amd/csrc/fx_fastq_qc.hpp).  For read i
+ * they look at the rlen bytes s at soff and the rlen bytes q at qoff -- what fx_fastq_fetch returns as seq and qual, a byte
+ * past the end of the stream reads as 0 -- and at nothing else; q[j] is an unsigned byte and p = phred (0 -> 33, read.c:268;
+ * 0..255).  Base classes are the composition's: upper-case A C G T, every other byte of s is "other".  All results are
+ * integers.  Whole streams only: a byte-range shard (fx_set_shard, fx_open_file_range) gives FX_EINVAL; before
+ * fx_fastq_build: FX_ESTATE; a null handle or output pointer: FX_EINVAL, nothing touched.  Every output is a pinned block
+ * of fx_pinned_alloc that belongs to the caller (fx_pinned_free each; never NULL after FX_OK, even for 0 rows).
+ *
+ * fx_fastq_read_stats: one row per read, in the order of ids (0-based, any order, repeats allowed; ids = NULL: every read in
+ *   read order, n_ids ignored).  length = rlen; qsum = sum of q[j] - p; qmin / qmax = the smallest / largest q[j] - p (0 for
+ *   an empty read); n_low = bytes with q[j] - p < low_qual (0..255); n_gc = G and C in s; n_other = bytes of s outside A C G T.
+ *   *n_rows = the number of rows.  An id outside the table: *first_bad = its position in ids, FX_ERANGE, nothing allocated. */
+int fx_fastq_read_stats(fx_handle *h, const int64_t *ids, int64_t n_ids, int phred, int low_qual, int64_t **length, int64_t **qsum,
+                        int16_t **qmin, int16_t **qmax, int32_t **n_low, int32_t **n_gc, int32_t **n_other, int64_t *n_rows,
+                        int64_t *first_bad);
+/* fx_fastq_cycle_hist: per position j < cycles (1..65536) over all reads with rlen > j: qual[j][b] (cycles x 256) = reads
+ *   whose RAW quality byte q[j] is b; base[j][c] (cycles x 5) = reads whose s[j] is A, C, G, T, other; depth[j] = reads with
+ *   rlen > j.  Positions at or beyond `cycles` are not counted; rows beyond the longest read are zero. */
+int fx_fastq_cycle_hist(fx_handle *h, int32_t cycles, int64_t **qual, int64_t **base, int64_t **depth);
+/* fx_fastq_select: the ascending 0-based ids of the reads that pass every criterion asked for -- min_len <= rlen (min_len
+ *   < 0: not asked), rlen <= max_len (< 0: not asked), qsum * mq_den >= mq_num * rlen (mean quality >= mq_num / mq_den;
+ *   mq_den = 0: not asked), n_low * lf_den <= lf_num * rlen (fraction of bytes below low_qual <= lf_num / lf_den; lf_den =
+ *   0: not asked), n_other <= max_other (< 0: not asked) -- in int64, so an empty read passes both ratio tests.  Numerators
+ *   and denominators within 0..10^9.  Predicate, count, scan and emit run on the device; only the ids come to the host.
+ *   *n_ids = how many; they are what fx_fastq_fetch_alloc takes. */
+int fx_fastq_select(fx_handle *h, int phred, int low_qual, int64_t min_len, int64_t max_len, int64_t mq_num, int64_t mq_den,
+                    int64_t lf_num, int64_t lf_den, int64_t max_other, int64_t **ids, int64_t *n_ids);
+
 /* ------------------------------------------------------------------ Fastx
  * Replaces kseq_read (kseq.c:138-179) as pyfastx_fastx_next drives it (fastx.c:124-130): index-free iteration over a
  * file with kseq's own record rules -- FASTA and FASTQ records mixed, sequence / quality over any number of lines,

@@ -49,7 +49,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -225,6 +225,9 @@ def lib():
     L.fx_fasta_search.argtypes = [vp, vp, vp, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
     L.fx_fastq_fetch_alloc.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     L.fx_fetch_phases.argtypes = [C.POINTER(C.c_double), i32]
+    L.fx_fastq_read_stats.argtypes = [vp, vp, i64, i32, i32] + [C.POINTER(vp)] * 7 + [C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_cycle_hist.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.fx_fastq_select.argtypes = [vp, i32, i32, i64, i64, i64, i64, i64, i64, i64, C.POINTER(vp), C.POINTER(i64)]
     L.fx_names_build.argtypes = [vp, i32]
     L.fx_names_lookup.argtypes = [vp, i32, i64, vp, vp, vp]
     L.fx_revcomp.argtypes = [i32, i32, vp, i64, i32]
@@ -1044,6 +1047,40 @@ class Blob:
         qual = pinned_array(pq.value, max(tot, 1))[:tot] if pq.value else None
         qi = pinned_array(pi.value, max(tot, 1), np.int8)[:tot] if pi.value else None
         return seq, qual, qi, o
+
+    def fastq_read_stats(self, ids=None, phred=0, low_qual=20):
+        """Per-read quality statistics (fx_fastq_read_stats) -> dict of pinned columns length, qsum, qmin, qmax, n_low, n_gc,
+        n_other in the order of ids (None: every read); an id outside the table raises FxError(FX_ERANGE) with .first_bad."""
+        ids = None if ids is None else self._i64(ids)
+        cols = [C.c_void_p() for _ in range(7)]
+        n, bad = C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_read_stats(self._h, _ptr(ids), 0 if ids is None else ids.size, int(phred), int(low_qual),
+                                       *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
+        if rc:
+            e = FxError(rc, lib().fx_last_error().decode())
+            e.first_bad = int(bad.value)
+            raise e
+        m = int(n.value)
+        names = (("length", np.int64), ("qsum", np.int64), ("qmin", np.int16), ("qmax", np.int16), ("n_low", np.int32),
+                 ("n_gc", np.int32), ("n_other", np.int32))
+        return {k: pinned_array(c.value, max(m, 1), dt)[:m] for (k, dt), c in zip(names, cols)}
+
+    def fastq_cycle_hist(self, cycles):
+        """Per-cycle histograms (fx_fastq_cycle_hist) -> (qual int64[cycles, 256], base int64[cycles, 5], depth int64[cycles]), pinned."""
+        cycles = int(cycles)
+        pq, pb, pd = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().fx_fastq_cycle_hist(self._h, cycles, C.byref(pq), C.byref(pb), C.byref(pd)))
+        return (pinned_array(pq.value, cycles * 256, np.int64).reshape(cycles, 256), pinned_array(pb.value, cycles * 5, np.int64).reshape(cycles, 5),
+                pinned_array(pd.value, cycles, np.int64))
+
+    def fastq_select(self, phred=0, low_qual=20, min_len=-1, max_len=-1, mean_qual=(0, 0), low_frac=(0, 0), max_other=-1):
+        """Ascending ids of the reads that pass (fx_fastq_select); mean_qual / low_frac are (numerator, denominator) pairs, a
+        denominator of 0 and a bound of -1 mean "not asked" -> int64 array in pinned memory."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        check(lib().fx_fastq_select(self._h, int(phred), int(low_qual), int(min_len), int(max_len), int(mean_qual[0]), int(mean_qual[1]),
+                                    int(low_frac[0]), int(low_frac[1]), int(max_other), C.byref(p), C.byref(n)))
+        m = int(n.value)
+        return pinned_array(p.value, max(m, 1), np.int64)[:m]
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)

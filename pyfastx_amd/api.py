@@ -1832,6 +1832,47 @@ class Fastq(_fxobj.FastqCore):
             raise
         return {"seq": seq, "qual": qual, "quali": qi, "offsets": offs}
 
+    def _qc_blob(self):
+        """The blob with the read table resident, for the quality-control passes; they run over one whole stream."""
+        if self._sharded:
+            raise NotImplementedError("quality control on a sharded or windowed stream")
+        return self._dev()
+
+    @property
+    def _sharded(self):
+        """Several devices or several windows: the stream is not one resident blob (windows.WindowedFastq)."""
+        return self._st.md is not None
+
+    def read_stats(self, ids=None, low_qual=20):
+        """Extension: per-read quality statistics, computed on the GPU from the resident stream (csrc/fx_fastq_qc.hpp) ->
+        dict of numpy columns in pinned memory, one row per id (0-based, any order, repeats allowed; None: every read in
+        read order).  With s = fq[i].seq, q = fq[i].qual as bytes and p = fq.phred (33 when 0): length = len(s); qsum = sum
+        of q[j] - p; qmin / qmax = its smallest / largest term (0 for an empty read); n_low = terms below low_qual
+        (0..255); n_gc = G and C in s; n_other = bytes of s outside upper-case A C G T.  A bad id: IndexError."""
+        from . import qc
+        return qc.read_stats_blob(self._qc_blob(), self._rlen_host.size, ids, self.phred, low_qual)
+
+    def cycle_profile(self, cycles=None):
+        """Extension: quality and base histograms per cycle (position in the read) over all reads -> qc.CycleProfile with
+        qual int64[cycles, 256] (reads per raw quality byte), base int64[cycles, 5] (A C G T other), depth int64[cycles]
+        (reads longer than the cycle), and the derived qual_scores / mean_qual.  cycles: 1..65536, default fq.maxlen;
+        positions at or beyond it are not counted, rows beyond the longest read are zero."""
+        from . import qc
+        if cycles is not None:
+            cycles = qc.check_cycles(cycles)
+        blob = self._qc_blob()
+        return qc.cycle_profile_blob(blob, max(int(self.maxlen), 1) if cycles is None else cycles, self.phred)
+
+    def select(self, min_len=None, max_len=None, min_mean_qual=None, max_low_frac=None, max_other=None, low_qual=20):
+        """Extension: the ascending 0-based ids (int64, pinned memory) of the reads that pass every criterion given, with the
+        columns of read_stats: min_len <= length <= max_len; mean of q - p at least min_mean_qual; at most the fraction
+        max_low_frac of the terms below low_qual; at most max_other bytes outside A C G T.  The two ratios are taken as
+        fractions with a denominator <= 1000 and compared in integers on the device (an empty read passes both); only the
+        ids come to the host, and fetch_many / raw_many take them as they are."""
+        from . import qc
+        args = qc.select_args(min_len, max_len, min_mean_qual, max_low_frac, max_other, low_qual)
+        return self._qc_blob().fastq_select(phred=self.phred, **args)
+
 
     def raw_many(self, ids_or_names):
         """Batched `Read.raw` (read.c:124-150): whole four-line records, one gather for all of them.

@@ -43,6 +43,7 @@
 #include "fx_sort.hpp"
 #include "fx_kseq.hpp"
 #include "fx_search.hpp"
+#include "fx_fastq_qc.hpp"
 
 using namespace fx;
 
@@ -319,10 +320,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist"};
 
 struct Prof {
     bool on = false;
@@ -3665,6 +3666,158 @@ extern "C" int fx_fastq_fetch_alloc(fx_handle *h, int64_t n, const int64_t *read
     if (w_qi) *quali = (int8_t *)outs[2];
     *dst_off = offs;
     pc.done();
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ FASTQ quality control (fx_fastq_qc.hpp)
+// What the three entry points share: the state checks, the offset and threshold in the form the kernels take them, lanes per read
+// from the mean read length (as fx_fastq_comp picks them), a grid of the workgroups that are resident at once.
+struct QcLaunch { int phred, thr, lpr; };
+static int qc_prepare(fx_handle *h, int phred, int low_qual, QcLaunch *q) {
+    if (phred < 0 || phred > 255) return fail(FX_EINVAL, "phred %d outside 0..255", phred);
+    if (low_qual < 0 || low_qual > 255) return fail(FX_EINVAL, "low_qual %d outside 0..255", low_qual);
+    if (!h->fastq_built) return fail(FX_ESTATE, "fx_fastq_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "quality control runs on whole streams, not on a byte-range shard");
+    int rc = use_device(h);
+    if (rc) return rc;
+    q->phred = phred ? phred : 33;                         // read.c:268
+    q->thr = std::min(q->phred + low_qual, 256);
+    const int64_t mean_len = h->n_reads > 0 ? (h->fq_size + h->n_reads - 1) / h->n_reads : 1;
+    q->lpr = (int)std::clamp<int64_t>((mean_len + 15) / 16, 1, 64);
+    return FX_OK;
+}
+template <class K> static int64_t qc_resident(fx_handle *h, K kern) {
+    int per_cu = 0, n_cu = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BLOCK, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
+    return (int64_t)per_cu * std::max(n_cu, 1);
+}
+template <bool SELECT>
+static void qc_launch_reads(fx_handle *h, const QcLaunch &q, const int64_t *d_ids, int64_t nq, const QcCols &cols, const QcSel &sel, uint8_t *pass) {
+    static const int64_t resident = qc_resident(h, k_fq_read_stats<SELECT>);
+    const unsigned nb = (unsigned)std::min<int64_t>(nblocks(nq, (BLOCK / 64) * (64 / q.lpr)), resident);
+    FX_LAUNCH(h, SELECT ? K_FQ_SELECT : K_FQ_READ_STATS, k_fq_read_stats<SELECT>, dim3(nb), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
+              (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, d_ids, nq, q.phred, q.thr, q.lpr, cols, sel, pass);
+}
+
+extern "C" int fx_fastq_read_stats(fx_handle *h, const int64_t *ids, int64_t n_ids, int phred, int low_qual, int64_t **length, int64_t **qsum,
+                                   int16_t **qmin, int16_t **qmax, int32_t **n_low, int32_t **n_gc, int32_t **n_other, int64_t *n_rows,
+                                   int64_t *first_bad) {
+    if (!h || !length || !qsum || !qmin || !qmax || !n_low || !n_gc || !n_other || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
+    *length = *qsum = nullptr; *qmin = *qmax = nullptr; *n_low = *n_gc = *n_other = nullptr;
+    *n_rows = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    QcLaunch q;
+    int rc = qc_prepare(h, phred, low_qual, &q);
+    if (rc) return rc;
+    const int64_t n = ids ? n_ids : h->n_reads;
+    for (int64_t k = 0; ids && k < n_ids; ++k)
+        if (ids[k] < 0 || ids[k] >= h->n_reads) { *first_bad = k; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[k]); }
+    const int64_t m = std::max<int64_t>(n, 1);
+    static const int width[7] = {8, 8, 2, 2, 4, 4, 4};
+    void *outs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); for (void *p : outs) fx_pinned_free(p); return code; };
+    for (int c = 0; c < 7; ++c)
+        if (!(outs[c] = fx_pinned_alloc(m * width[c]))) return bail(fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n));
+    if (n > 0) {
+        Staged st(h);
+        st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+        const int64_t *d_ids = nullptr;
+        if ((rc = st.up(h, ids, ids ? n_ids : 0, &d_ids))) return bail(rc);
+        ScratchBuf<uint8_t> dev;                           // the seven columns, each from a 256-byte boundary
+        int64_t at[8] = {0};
+        for (int c = 0; c < 7; ++c) at[c + 1] = at[c] + ((n * width[c] + 255) & ~255ll);
+        if ((rc = dev.alloc(h->device, at[7], h->stream))) return bail(rc);
+        QcCols cols{(int64_t *)(dev.p + at[0]), (int64_t *)(dev.p + at[1]), (int16_t *)(dev.p + at[2]), (int16_t *)(dev.p + at[3]),
+                    (int32_t *)(dev.p + at[4]), (int32_t *)(dev.p + at[5]), (int32_t *)(dev.p + at[6])};
+        qc_launch_reads<false>(h, q, d_ids, n, cols, QcSel{-1, -1, 0, 0, 0, 0, -1}, nullptr);
+        hipError_t e = hipGetLastError();
+        for (int c = 0; c < 7 && e == hipSuccess; ++c) e = hipMemcpyAsync(outs[c], dev.p + at[c], (size_t)(n * width[c]), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "read statistics: %s", hipGetErrorString(e)));
+        h->prof.drain();
+    }
+    *length = (int64_t *)outs[0]; *qsum = (int64_t *)outs[1]; *qmin = (int16_t *)outs[2]; *qmax = (int16_t *)outs[3];
+    *n_low = (int32_t *)outs[4]; *n_gc = (int32_t *)outs[5]; *n_other = (int32_t *)outs[6];
+    *n_rows = n;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_select(fx_handle *h, int phred, int low_qual, int64_t min_len, int64_t max_len, int64_t mq_num, int64_t mq_den,
+                               int64_t lf_num, int64_t lf_den, int64_t max_other, int64_t **ids, int64_t *n_ids) {
+    if (!h || !ids || !n_ids) return fail(FX_EINVAL, "null argument");
+    *ids = nullptr; *n_ids = 0;
+    const int64_t lim = 1000000000ll;
+    if (mq_num < 0 || mq_num > lim || mq_den < 0 || mq_den > lim || lf_num < 0 || lf_num > lim || lf_den < 0 || lf_den > lim)
+        return fail(FX_EINVAL, "a ratio outside 0..10^9");
+    QcLaunch q;
+    int rc = qc_prepare(h, phred, low_qual, &q);
+    if (rc) return rc;
+    const int64_t n = h->n_reads;
+    int64_t total = 0;
+    int64_t *p_ids = nullptr;
+    if (n > 0) {
+        Staged st(h);
+        ScratchBuf<uint8_t> pass;
+        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
+        int64_t *sums = nullptr, *d_tot = nullptr;
+        if ((rc = pass.alloc(h->device, n, h->stream)) || (rc = st.scratch<int64_t>(nch, &sums)) || (rc = st.scratch<int64_t>(1, &d_tot))) return rc;
+        qc_launch_reads<true>(h, q, nullptr, n, QcCols{}, QcSel{min_len, max_len, mq_num, mq_den, lf_num, lf_den, max_other}, pass.p);
+        FX_LAUNCH(h, K_FQ_SELECT_SCAN, (k_sscan_sums<1, QcLdPass>), dim3((unsigned)nch), dim3(BLOCK), QcLdPass{pass.p}, n, sums);
+        FX_LAUNCH(h, K_FQ_SELECT_SCAN, (k_sscan_top<1>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&total, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (!(p_ids = (int64_t *)fx_pinned_alloc(std::max<int64_t>(total, 1) * 8))) return fail(FX_ENOMEM, "pinned block for %lld ids", (long long)total);
+        if (total > 0) {
+            ScratchBuf<int64_t> out;
+            hipError_t e = hipSuccess;
+            if ((rc = out.alloc(h->device, total, h->stream))) { fx_pinned_free(p_ids); return rc; }
+            FX_LAUNCH(h, K_FQ_SELECT_EMIT, k_fq_select_emit, dim3((unsigned)nch), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, out.p);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(p_ids, out.p, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_ids); return fail(FX_EDEVICE, "select emit: %s", hipGetErrorString(e)); }
+        }
+        h->prof.drain();
+    } else if (!(p_ids = (int64_t *)fx_pinned_alloc(8))) return FX_ENOMEM;
+    *ids = p_ids; *n_ids = total;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_cycle_hist(fx_handle *h, int32_t cycles, int64_t **qual, int64_t **base, int64_t **depth) {
+    if (!h || !qual || !base || !depth) return fail(FX_EINVAL, "null argument");
+    *qual = *base = *depth = nullptr;
+    if (cycles < 1 || cycles > 65536) return fail(FX_EINVAL, "cycles %d outside 1..65536", (int)cycles);
+    QcLaunch q;
+    int rc = qc_prepare(h, 0, 0, &q);
+    if (rc) return rc;
+    const int64_t nq = (int64_t)cycles * 256, nb = (int64_t)cycles * 5;
+    int64_t *p_qual = (int64_t *)fx_pinned_alloc(nq * 8), *p_base = (int64_t *)fx_pinned_alloc(nb * 8), *p_depth = (int64_t *)fx_pinned_alloc((int64_t)cycles * 8);
+    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_qual); fx_pinned_free(p_base); fx_pinned_free(p_depth); return code; };
+    if (!p_qual || !p_base || !p_depth) return bail(fail(FX_ENOMEM, "pinned blocks for %d cycles", (int)cycles));
+    {
+        ScratchBuf<unsigned long long> cnt;                 // qual, then base
+        if ((rc = cnt.alloc(h->device, nq + nb, h->stream))) return bail(rc);
+        hipError_t e = hipMemsetAsync(cnt.p, 0, (size_t)(nq + nb) * 8, h->stream);
+        if (e == hipSuccess && h->n_reads > 0) {
+            // the waves are dealt over the tiles of 64 cycles: at least one wave per tile, else the workgroups resident at once
+            static const int64_t resident = qc_resident(h, k_fq_cycle_hist);
+            const int n_tiles = (cycles + 63) / 64;
+            const int64_t blocks = std::max<int64_t>(resident, (n_tiles + BLOCK / 64 - 1) / (BLOCK / 64));
+            FX_LAUNCH(h, K_FQ_CYCLE_HIST, k_fq_cycle_hist, dim3((unsigned)blocks), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
+                      (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, h->n_reads, (int)cycles, n_tiles,
+                      cnt.p, cnt.p + nq);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(p_qual, cnt.p, (size_t)nq * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(p_base, cnt.p + nq, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "cycle histogram: %s", hipGetErrorString(e)));
+        h->prof.drain();
+    }
+    for (int64_t j = 0; j < cycles; ++j) p_depth[j] = p_base[j * 5] + p_base[j * 5 + 1] + p_base[j * 5 + 2] + p_base[j * 5 + 3] + p_base[j * 5 + 4];
+    *qual = p_qual; *base = p_base; *depth = p_depth;
     return FX_OK;
 }
 
