@@ -376,6 +376,40 @@ int fx_fastq_cycle_hist(fx_handle *h, int32_t cycles, int64_t **qual, int64_t **
 int fx_fastq_select(fx_handle *h, int phred, int low_qual, int64_t min_len, int64_t max_len, int64_t mq_num, int64_t mq_den,
                     int64_t lf_num, int64_t lf_den, int64_t max_other, int64_t **ids, int64_t *n_ids);
 
+/* ------------------------------------------------------------------ FASTQ trimming and trimmed records (extension)
+ * The reference has no counterpart: it trims nothing and writes verbatim copies only (Read.raw, read.c:124-150).  s, q, L =
+ * rlen and d[j] = q[j] - p as for the quality-control entries above (a byte past the end of the stream reads as 0); states
+ * and errors as theirs (null handle / output: FX_EINVAL; before fx_fastq_build: FX_ESTATE; a byte-range shard: FX_EINVAL; an
+ * id outside the table: *first_bad = its position, FX_ERANGE, nothing allocated); outputs are pinned blocks of
+ * fx_pinned_alloc that belong to the caller, never NULL after FX_OK.
+ *
+ * fx_fastq_trim: per read (in the order of ids; ids = NULL: every read) the interval [start, end) that survives these steps,
+ *   run in this order, each on what the one before left (a = start, b = end; always 0 <= a <= b <= L):
+ *   1 fixed clip      a = min(clip_front, L); b = max(a, L - clip_tail)                                (both >= 0)
+ *   2 3' adapter      adapter = NULL: not asked.  adapter_len 1..64 letters of A C G T N (upper case; N matches any byte),
+ *                     1 <= min_overlap <= adapter_len.  For j = a, a + 1, ...: m = min(adapter_len, b - j); stop when m <
+ *                     min_overlap; mm = the k < m with adapter[k] != 'N' and s[j + k] != adapter[k] (read bytes as they
+ *                     are: lower case, N, IUPAC codes mismatch); the FIRST j with mm * err_den <= err_num * m: b = j.
+ *   3 5' quality      front_qual < 0: not asked (else 0..255).  While a < b and d[a] < front_qual: a += 1.
+ *   4 sliding window  win_len = 0: not asked.  If b > a: we = min(win_len, b - a); the first j in [a, b - we] with
+ *                     (d[j] + ... + d[j + we - 1]) * win_den < win_num * we: b = j.
+ *   5 3' quality      tail_qual < 0: not asked (else 0..255).  While b > a and d[b - 1] < tail_qual: b -= 1.
+ *   Ratios within 0..10^9, denominators >= 1.  *n_rows = the number of rows.
+ * fx_fastq_format_alloc: the four-line records of the queries, back to back: H "\n" s[a:b] "\n+\n" q[a:b] "\n", H = the dlen
+ *   bytes at soff - dlen - 1 (they begin with '@') without one trailing '\r'; bytes are copied as they are.  start = end =
+ *   NULL: whole reads (a = 0, b = L); else row k of both belongs to query k (what fx_fastq_trim returned for the same
+ *   ids), and an interval outside 0 <= start <= end <= rlen gives *first_bad = the first such query, FX_ERANGE, nothing
+ *   allocated.  A query with b - a < min_len (>= 0) produces no bytes.  Record k is dst[dst_off[k] .. dst_off[k + 1]);
+ *   dst_off has *n_rows + 1 entries, *n_kept = the records that produced bytes.  Sizes, offsets and bytes are made on the
+ *   device; only the finished bytes and the offsets come to the host. */
+int fx_fastq_trim(fx_handle *h, const int64_t *ids, int64_t n_ids, int phred, int64_t clip_front, int64_t clip_tail,
+                  const uint8_t *adapter, int32_t adapter_len, int32_t min_overlap, int64_t err_num, int64_t err_den,
+                  int32_t front_qual, int32_t win_len, int64_t win_num, int64_t win_den, int32_t tail_qual,
+                  int64_t **start, int64_t **end, int64_t *n_rows, int64_t *first_bad);
+int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                          int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept,
+                          int64_t *first_bad);
+
 /* ------------------------------------------------------------------ Fastx
  * Replaces kseq_read (kseq.c:138-179) as pyfastx_fastx_next drives it (fastx.c:124-130): index-free iteration over a
  * file with kseq's own record rules -- FASTA and FASTQ records mixed, sequence / quality over any number of lines,

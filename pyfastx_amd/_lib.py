@@ -49,7 +49,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -228,6 +228,9 @@ def lib():
     L.fx_fastq_read_stats.argtypes = [vp, vp, i64, i32, i32] + [C.POINTER(vp)] * 7 + [C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_cycle_hist.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.fx_fastq_select.argtypes = [vp, i32, i32, i64, i64, i64, i64, i64, i64, i64, C.POINTER(vp), C.POINTER(i64)]
+    L.fx_fastq_trim.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i64, i64, i32, i32, i64, i64, i32,
+                                C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_format_alloc.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.fx_names_build.argtypes = [vp, i32]
     L.fx_names_lookup.argtypes = [vp, i32, i64, vp, vp, vp]
     L.fx_revcomp.argtypes = [i32, i32, vp, i64, i32]
@@ -1081,6 +1084,45 @@ class Blob:
                                     int(low_frac[0]), int(low_frac[1]), int(max_other), C.byref(p), C.byref(n)))
         m = int(n.value)
         return pinned_array(p.value, max(m, 1), np.int64)[:m]
+
+    def fastq_trim(self, ids=None, phred=0, clip_front=0, clip_tail=0, adapter=None, min_overlap=1, err=(0, 1), front_qual=None,
+                   window=None, tail_qual=None):
+        """Per-read surviving interval (fx_fastq_trim) -> (start, end), int64 in pinned memory, in the order of ids (None:
+        every read).  adapter: upper-case bytes of A C G T N or None; err = (num, den); window = (length, num, den) or None;
+        a threshold None is a step not asked for.  An id outside the table raises FxError(FX_ERANGE) with .first_bad."""
+        ids = None if ids is None else self._i64(ids)
+        ad = None if adapter is None else bytes(adapter)
+        w = (0, 0, 1) if window is None else window
+        ps, pe, n, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_trim(self._h, _ptr(ids), 0 if ids is None else ids.size, int(phred), int(clip_front), int(clip_tail),
+                                 ad, 0 if ad is None else len(ad), int(min_overlap), int(err[0]), int(err[1]),
+                                 -1 if front_qual is None else int(front_qual), int(w[0]), int(w[1]), int(w[2]),
+                                 -1 if tail_qual is None else int(tail_qual), C.byref(ps), C.byref(pe), C.byref(n), C.byref(bad))
+        if rc:
+            e = FxError(rc, lib().fx_last_error().decode())
+            e.first_bad = int(bad.value)
+            raise e
+        m = int(n.value)
+        return pinned_array(ps.value, max(m, 1), np.int64)[:m], pinned_array(pe.value, max(m, 1), np.int64)[:m]
+
+    def fastq_format_alloc(self, ids=None, start=None, end=None, min_len=0):
+        """Four-line records of the queries cut to [start, end) (fx_fastq_format_alloc; start = end = None: whole reads) ->
+        (uint8 buffer, int64 offsets[n + 1], records kept), pinned.  A bad id or interval raises FxError(FX_ERANGE) with
+        .first_bad."""
+        ids = None if ids is None else self._i64(ids)
+        start = None if start is None else self._i64(start)
+        end = None if end is None else self._i64(end)
+        pd, po, n, kept, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_format_alloc(self._h, _ptr(ids), 0 if ids is None else ids.size, _ptr(start), _ptr(end), int(min_len),
+                                         C.byref(pd), C.byref(po), C.byref(n), C.byref(kept), C.byref(bad))
+        if rc:
+            e = FxError(rc, lib().fx_last_error().decode())
+            e.first_bad = int(bad.value)
+            raise e
+        m = int(n.value)
+        o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
+        tot = int(o[m])
+        return pinned_array(pd.value, max(tot, 1))[:tot], o, int(kept.value)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)

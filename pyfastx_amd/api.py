@@ -1873,6 +1873,54 @@ class Fastq(_fxobj.FastqCore):
         args = qc.select_args(min_len, max_len, min_mean_qual, max_low_frac, max_other, low_qual)
         return self._qc_blob().fastq_select(phred=self.phred, **args)
 
+    def trim(self, ids=None, clip_front=0, clip_tail=0, adapter=None, min_overlap=3, max_error_rate=0.1, front_qual=None,
+             window=None, tail_qual=None):
+        """Extension: per read the interval [start, end) that survives trimming, computed on the GPU from the resident stream
+        (csrc/fx_fastq_trim.hpp) -> {"start": int64[n], "end": int64[n]} in pinned memory; row k belongs to ids[k] (0-based,
+        any order, repeats allowed), or to read k.  The steps run in this order, each on what the one before left, with s =
+        fq[i].seq, q = fq[i].qual as bytes, d = q - fq.phred (33 when 0): 1 clip_front / clip_tail bases off the ends; 2 the
+        3' adapter (1..64 letters of A C G T N, N matches anything; read bytes as they are): cut at the first position where
+        the adapter -- or, at the read's end, its first min_overlap or more letters -- matches with at most max_error_rate
+        mismatches per compared letter (no indels); 3 front_qual: bases with d below it off the 5' end; 4 window = (length,
+        mean): cut at the start of the first window of that many bases (the whole read, if shorter) whose mean d is below
+        mean; 5 tail_qual: bases with d below it off the 3' end.  A step that is not given does nothing.  A bad id:
+        IndexError; a bad argument: ValueError."""
+        from . import trim as _trim
+        args = _trim.trim_args(clip_front, clip_tail, adapter, min_overlap, max_error_rate, front_qual, window, tail_qual)
+        return _trim.trim_blob(self._qc_blob(), self._rlen_host.size, ids, self.phred, args)
+
+    def records(self, ids=None, start=None, end=None, min_len=0):
+        """Extension: four-line FASTQ records of the reads `ids` (None: every read), cut to [start, end) -- what trim returned
+        for the same ids; both None: whole reads -- formatted and laid out back to back on the GPU -> (uint8 buffer, int64
+        offsets[n + 1]) in pinned memory.  A record is header + "\\n" + seq[a:b] + "\\n+\\n" + qual[a:b] + "\\n", the header as
+        Read.description shows it; a read with fewer than min_len bases left produces no bytes (an empty range)."""
+        from . import trim as _trim
+        buf, offs, _ = _trim.records_blob(self._qc_blob(), self._rlen_host.size, ids, start, end, min_len)
+        return buf, offs
+
+    def write(self, path, ids=None, start=None, end=None, min_len=0, batch_bytes=1 << 30):
+        """Extension: the records of `records` written to the plain file `path`, in batches of consecutive queries whose
+        upper bound fits batch_bytes of pinned memory -> {"reads": records written, "bases": their bases, "dropped": queries
+        that fell below min_len}."""
+        from . import trim as _trim
+        blob = self._qc_blob()
+        n_reads = self._rlen_host.size
+        ids = _trim.check_ids(ids, n_reads)
+        n = n_reads if ids is None else ids.size
+        start, end = _trim.check_intervals(start, end, n)
+        kept = bases = 0
+        with open(path, "wb") as f:
+            for lo, hi in _trim.batches(self._tab_host, ids, n_reads, batch_bytes):
+                q = np.arange(lo, hi, dtype=np.int64) if ids is None else ids[lo:hi]
+                a, b = (None, None) if start is None else (start[lo:hi], end[lo:hi])
+                buf, offs, k = _trim.records_blob(blob, n_reads, q, a, b, min_len)
+                f.write(memoryview(buf))
+                kept += k
+                there = np.diff(offs) > 0
+                ln = self._rlen_host[q].astype(np.int64) if a is None else b - a
+                bases += int(ln[there].sum())
+        return {"reads": int(kept), "bases": int(bases), "dropped": int(n - kept)}
+
 
     def raw_many(self, ids_or_names):
         """Batched `Read.raw` (read.c:124-150): whole four-line records, one gather for all of them.

@@ -44,6 +44,7 @@
 #include "fx_kseq.hpp"
 #include "fx_search.hpp"
 #include "fx_fastq_qc.hpp"
+#include "fx_fastq_trim.hpp"
 
 using namespace fx;
 
@@ -320,10 +321,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit"};
 
 struct Prof {
     bool on = false;
@@ -341,7 +342,7 @@ struct Prof {
     }
     bool hit = false;
     void begin(int id, hipStream_t s) {
-        hit = on && ((mask >> id) & 1u);
+        hit = on && (id < 32 ? ((mask >> id) & 1u) != 0 : mask == ~0u);       // ids past the mask's width: timed when everything is
         if (!hit) return;
         Span sp{id, get(), get()};
         (void)hipEventRecord(sp.a, s);
@@ -3818,6 +3819,155 @@ extern "C" int fx_fastq_cycle_hist(fx_handle *h, int32_t cycles, int64_t **qual,
     }
     for (int64_t j = 0; j < cycles; ++j) p_depth[j] = p_base[j * 5] + p_base[j * 5 + 1] + p_base[j * 5 + 2] + p_base[j * 5 + 3] + p_base[j * 5 + 4];
     *qual = p_qual; *base = p_base; *depth = p_depth;
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ FASTQ trimming and trimmed records (fx_fastq_trim.hpp)
+// Extension: the reference has no counterpart (it writes verbatim copies only, read.c:124-150).
+template <int NW>
+static void trim_launch(fx_handle *h, int lpr, const int64_t *d_ids, int64_t nq, const TrimPar &P, int64_t *d_start, int64_t *d_end) {
+    static const int64_t resident = qc_resident(h, k_fq_trim<NW>);
+    const unsigned nb = (unsigned)std::min<int64_t>(nblocks(nq, (BLOCK / 64) * (64 / lpr)), resident);
+    FX_LAUNCH(h, K_FQ_TRIM, k_fq_trim<NW>, dim3(nb), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n, (const int64_t *)h->fq_rlen.p,
+              (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, d_ids, nq, lpr, P, d_start, d_end);
+}
+
+extern "C" int fx_fastq_trim(fx_handle *h, const int64_t *ids, int64_t n_ids, int phred, int64_t clip_front, int64_t clip_tail,
+                             const uint8_t *adapter, int32_t adapter_len, int32_t min_overlap, int64_t err_num, int64_t err_den,
+                             int32_t front_qual, int32_t win_len, int64_t win_num, int64_t win_den, int32_t tail_qual,
+                             int64_t **start, int64_t **end, int64_t *n_rows, int64_t *first_bad) {
+    if (!h || !start || !end || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
+    *start = *end = nullptr; *n_rows = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    const int64_t lim = 1000000000ll;
+    if (clip_front < 0 || clip_tail < 0) return fail(FX_EINVAL, "a negative clip");
+    if (front_qual > 255 || tail_qual > 255) return fail(FX_EINVAL, "a quality threshold above 255");
+    if (win_len < 0 || (win_len > 0 && (win_num < 0 || win_num > lim || win_den < 1 || win_den > lim))) return fail(FX_EINVAL, "window: length >= 0, ratio within 0..10^9");
+    TrimPar P{};
+    if (adapter) {
+        if (adapter_len < 1 || adapter_len > 64) return fail(FX_EINVAL, "adapter length %d outside 1..64", (int)adapter_len);
+        if (min_overlap < 1 || min_overlap > adapter_len) return fail(FX_EINVAL, "min_overlap %d outside 1..%d", (int)min_overlap, (int)adapter_len);
+        if (err_num < 0 || err_num > lim || err_den < 1 || err_den > lim) return fail(FX_EINVAL, "error ratio outside 0..10^9");
+        for (int k = 0; k < adapter_len; ++k) {
+            const uint8_t c = adapter[k];
+            if (c != 'A' && c != 'C' && c != 'G' && c != 'T' && c != 'N') return fail(FX_EINVAL, "adapter letter %d is not one of A C G T N", k);
+            if (c != 'N') {
+                P.acode[k >> 4] |= (uint32_t)((c >> 1) & 3) << (2 * (k & 15));
+                P.acare[k >> 4] |= 1u << (2 * (k & 15));
+            }
+        }
+        P.alen = adapter_len; P.min_overlap = min_overlap; P.err_num = err_num; P.err_den = err_den;
+    }
+    QcLaunch q;
+    int rc = qc_prepare(h, phred, 0, &q);
+    if (rc) return rc;
+    P.phred = q.phred; P.clip_front = clip_front; P.clip_tail = clip_tail;
+    P.front_thr = front_qual < 0 ? -1 : std::min(q.phred + front_qual, 256);
+    P.tail_thr = tail_qual < 0 ? -1 : std::min(q.phred + tail_qual, 256);
+    P.win_len = win_len; P.win_num = win_num; P.win_den = win_len > 0 ? win_den : 1;
+    const int64_t n = ids ? n_ids : h->n_reads;
+    for (int64_t k = 0; ids && k < n_ids; ++k)
+        if (ids[k] < 0 || ids[k] >= h->n_reads) { *first_bad = k; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[k]); }
+    const int64_t m = std::max<int64_t>(n, 1);
+    int64_t *p_start = (int64_t *)fx_pinned_alloc(m * 8), *p_end = (int64_t *)fx_pinned_alloc(m * 8);
+    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_start); fx_pinned_free(p_end); return code; };
+    if (!p_start || !p_end) return bail(fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n));
+    if (n > 0) {
+        Staged st(h);
+        st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+        const int64_t *d_ids = nullptr;
+        if ((rc = st.up(h, ids, ids ? n_ids : 0, &d_ids))) return bail(rc);
+        ScratchBuf<int64_t> dev;                           // start, then end
+        if ((rc = dev.alloc(h->device, 2 * n, h->stream))) return bail(rc);
+        // a lane group holds the longest read at once (up to 1024 bytes; a longer one is walked by one lane)
+        const int lpr = (int)std::clamp<int64_t>(((int64_t)h->fq_maxlen + 15) / 16, 1, 64);
+        switch ((P.alen + 15) / 16) {
+            case 0: trim_launch<0>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
+            case 1: trim_launch<1>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
+            case 2: trim_launch<2>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
+            case 3: trim_launch<3>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
+            default: trim_launch<4>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
+        }
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(p_start, dev.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(p_end, dev.p + n, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "trim: %s", hipGetErrorString(e)));
+        h->prof.drain();
+    }
+    *start = p_start; *end = p_end; *n_rows = n;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                                     int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept, int64_t *first_bad) {
+    if (!h || !dst || !dst_off || !n_rows || !n_kept || !first_bad) return fail(FX_EINVAL, "null argument");
+    *dst = nullptr; *dst_off = nullptr; *n_rows = 0; *n_kept = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    if (min_len < 0) return fail(FX_EINVAL, "negative min_len");
+    QcLaunch q;
+    int rc = qc_prepare(h, 0, 0, &q);
+    if (rc) return rc;
+    const int64_t n = ids ? n_ids : h->n_reads;
+    for (int64_t k = 0; ids && k < n_ids; ++k)
+        if (ids[k] < 0 || ids[k] >= h->n_reads) { *first_bad = k; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[k]); }
+    uint8_t *p_dst = nullptr;
+    int64_t *p_off = nullptr;
+    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_dst); fx_pinned_free(p_off); return code; };
+    int64_t kept = 0;
+    if (n == 0) {
+        p_dst = (uint8_t *)fx_pinned_alloc(1); p_off = (int64_t *)fx_pinned_alloc(16);
+        if (!p_dst || !p_off) return bail(FX_ENOMEM);
+        p_off[0] = 0;
+    } else {
+        Staged st(h);
+        st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
+        const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
+        if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
+        ScratchBuf<int64_t> cnt, offs;                     // record sizes; exclusive offsets (n + 1), then the kept counts (n + 1)
+        int64_t *sums = nullptr, *d_tot = nullptr;
+        unsigned long long *d_bad = nullptr;
+        if ((rc = cnt.alloc(h->device, n, h->stream)) || (rc = offs.alloc(h->device, 2 * (n + 1), h->stream)) ||
+            (rc = st.scratch<int64_t>(nch * 2, &sums)) || (rc = st.scratch<int64_t>(2, &d_tot)) || (rc = st.scratch<unsigned long long>(1, &d_bad))) return rc;
+        HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
+        FX_LAUNCH(h, K_FQ_FORMAT_COUNT, k_fq_format_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
+                  (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, (const int32_t *)h->fq_dlen.p, d_ids, n, d_start, d_end, min_len, cnt.p, d_bad);
+        FX_LAUNCH(h, K_FQ_FORMAT_SCAN, (k_sscan_sums<2, FmtLdCnt>), dim3((unsigned)nch), dim3(BLOCK), FmtLdCnt{cnt.p}, n, sums);
+        FX_LAUNCH(h, K_FQ_FORMAT_SCAN, (k_sscan_top<2>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
+        FX_LAUNCH(h, K_FQ_FORMAT_SCAN, (k_sscan_apply<2, FmtLdCnt>), dim3((unsigned)nch), dim3(BLOCK), FmtLdCnt{cnt.p}, n, (const int64_t *)sums, offs.p);
+        HIPCHK(hipGetLastError());
+        int64_t tot[2] = {0, 0};
+        unsigned long long bad = ~0ull;
+        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (bad != ~0ull) {
+            *first_bad = (int64_t)bad;
+            h->prof.drain();
+            return fail(FX_ERANGE, "the interval of query %lld lies outside its read", (long long)bad);
+        }
+        const int64_t total = tot[0];
+        kept = tot[1];
+        p_dst = (uint8_t *)fx_pinned_alloc(std::max<int64_t>(total, 1)); p_off = (int64_t *)fx_pinned_alloc((n + 1) * 8);
+        if (!p_dst || !p_off) return bail(fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total));
+        ScratchBuf<uint8_t> out;
+        if ((rc = out.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return bail(rc);
+        hipError_t e = hipSuccess;
+        if (total > 0) {
+            FX_LAUNCH(h, K_FQ_FORMAT_EMIT, k_fq_format_emit, dim3(nblocks(n, (BLOCK / 64) * (64 / q.lpr))), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
+                      (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, (const int32_t *)h->fq_dlen.p, d_ids, n, d_start,
+                      (const int64_t *)offs.p, q.lpr, out.p);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(p_dst, out.p, (size_t)total, hipMemcpyDeviceToHost, h->stream);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(p_off, offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "format: %s", hipGetErrorString(e)));
+        h->prof.drain();
+    }
+    *dst = p_dst; *dst_off = p_off; *n_rows = n; *n_kept = kept;
     return FX_OK;
 }
 
