@@ -410,6 +410,36 @@ int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const
                           int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept,
                           int64_t *first_bad);
 
+/* ------------------------------------------------------------------ k-mer spectra (extension)
+ * The reference counts single letters only (composition); these count every window of k bases, 1 <= k <= 13, into a dense
+ * table of 4^k exact int64 counters on the device (pyfastx_amd/csrc/fx_kmer.hpp).  Larger k needs a sparse form and is not
+ * offered.
+ *   alphabet     A C G T and a c g t, case-insensitive: A = 0, C = 1, G = 2, T = 3.  Every other byte (N, U, IUPAC codes,
+ *                '-', '*', digits, bytes >= 128) is invalid, and a window that holds one is not counted.
+ *   code         of the window b0 b1 .. b(k-1): sum of code(bj) * 4^(k-1-j) -- the first base is the most significant digit.
+ *   flags        FX_KMER_CANONICAL: a window counts under min(code, code of its reverse complement); a window that is its
+ *                own reverse complement (even k only) counts once; entries whose index is no canonical code stay 0.  The
+ *                table has 4^k entries in both forms, and its sum is the number of valid windows.
+ * fx_fasta_kmers: the windows are the len(s) - k + 1 windows of the `seq` s of every selected record -- the bytes
+ *   fx_fasta_search walks: bytes 10 / 13 / 32 dropped, windows run across line ends, never from one record into the next and
+ *   never past slen.  ids, n_ids: the records (0-based, any order, a record listed twice counts twice; ids = NULL: all of
+ *   them; a non-NULL ids with n_ids = 0: none, the table is zero).  per_record = 0: one table, *n_rows = 1.  per_record != 0
+ *   (k <= 6 only): one table per selected record in the order of ids, *n_rows = their number, counts[row * 4^k + code].
+ * fx_fastq_kmers: the windows of s[a:b] of every selected read, s = the rlen bytes at soff (what fx_fastq_fetch returns;
+ *   no line rule of its own), a = 0 and b = rlen unless start / end are given: row j of both belongs to query j, as for
+ *   fx_fastq_format_alloc (what fx_fastq_trim returned for the same ids).  One table.
+ * *counts is a pinned block of fx_pinned_alloc that belongs to the caller (fx_pinned_free), never NULL after FX_OK.
+ * Errors: a null handle or output pointer, start without end: FX_EINVAL, nothing touched; before fx_fasta_build /
+ * fx_fastq_build: FX_ESTATE; a byte-range shard (fx_set_shard, fx_open_file_range; a window across a cut has no halo):
+ * FX_EINVAL; unknown flag bits, k outside 1..13 (1..6 with per_record): FX_EINVAL; an id outside the table, or an interval
+ * outside 0 <= start <= end <= rlen: *first_bad = its position among the queries, FX_ERANGE, nothing allocated; no device:
+ * FX_EDEVICE (there is no CPU path). */
+enum { FX_KMER_CANONICAL = 1 };
+int fx_fasta_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, int per_record, int64_t **counts,
+                   int64_t *n_rows, int64_t *first_bad);
+int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                   int64_t **counts, int64_t *first_bad);
+
 /* ------------------------------------------------------------------ Fastx
  * Replaces kseq_read (kseq.c:138-179) as pyfastx_fastx_next drives it (fastx.c:124-130): index-free iteration over a
  * file with kseq's own record rules -- FASTA and FASTQ records mixed, sequence / quality over any number of lines,

@@ -13,6 +13,7 @@ _LIB = None
 FX_HOST, FX_DEVICE = 0, 1
 FX_UPPER, FX_REVERSE, FX_COMPLEMENT, FX_RAW = 1, 2, 4, 8
 FX_SEARCH_DEGENERATE, FX_SEARCH_UPPER, FX_SEARCH_PLUS, FX_SEARCH_MINUS = 1, 2, 4, 8
+FX_KMER_CANONICAL = 1
 FX_OK, FX_ENOENT, FX_EFORMAT, FX_EIO, FX_EDEVICE, FX_ENOMEM, FX_ERANGE, FX_EINVAL, FX_ESTATE = \
     0, -1, -2, -3, -4, -5, -6, -7, -8
 
@@ -49,7 +50,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -231,6 +232,8 @@ def lib():
     L.fx_fastq_trim.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i64, i64, i32, i32, i64, i64, i32,
                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_format_alloc.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fasta_kmers.argtypes = [vp, i32, i32, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_kmers.argtypes = [vp, i32, i32, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(i64)]
     L.fx_names_build.argtypes = [vp, i32]
     L.fx_names_lookup.argtypes = [vp, i32, i64, vp, vp, vp]
     L.fx_revcomp.argtypes = [i32, i32, vp, i64, i32]
@@ -1123,6 +1126,48 @@ class Blob:
         o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
         tot = int(o[m])
         return pinned_array(pd.value, max(tot, 1))[:tot], o, int(kept.value)
+
+    @staticmethod
+    def _kmer_ids(ids):
+        """ids for the k-mer entries: None stays NULL (everything); an empty selection still hands over a valid pointer."""
+        if ids is None:
+            return None, 0, None
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        return (ids if ids.size else np.zeros(1, dtype=np.int64)), ids.size, ids
+
+    def fasta_kmers(self, k, canonical=False, ids=None, per_record=False):
+        """k-mer spectrum of the resident FASTA table (fx_fasta_kmers) -> int64[4**k], or int64[n_sel, 4**k] with per_record
+        (k <= 6), in pinned memory.  ids: 0-based record ids, any order, repeats count again; None: every record.  An id
+        outside the table raises FxError(FX_ERANGE) with .first_bad."""
+        buf, n_ids, _ = self._kmer_ids(ids)
+        p, rows, bad = C.c_void_p(), C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fasta_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, 1 if per_record else 0,
+                                  C.byref(p), C.byref(rows), C.byref(bad))
+        if rc:
+            e = FxError(rc, lib().fx_last_error().decode())
+            e.first_bad = int(bad.value)
+            raise e
+        m, w = int(rows.value), 4 ** int(k)
+        a = pinned_array(p.value, max(m * w, 1), np.int64)[:m * w]
+        return a.reshape(m, w) if per_record else a
+
+    def fastq_kmers(self, k, canonical=False, ids=None, start=None, end=None):
+        """k-mer spectrum of the reads `ids` (None: every read) cut to [start, end) (both None: whole reads) of the resident
+        FASTQ table (fx_fastq_kmers) -> int64[4**k] in pinned memory.  A bad id or interval raises FxError(FX_ERANGE) with
+        .first_bad."""
+        buf, n_ids, _ = self._kmer_ids(ids)
+        start = None if start is None else self._i64(start)
+        end = None if end is None else self._i64(end)
+        if start is not None and start.size == 0:
+            start = end = None                                 # no query, no interval
+        p, bad = C.c_void_p(), C.c_int64(-1)
+        rc = lib().fx_fastq_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, _ptr(start), _ptr(end),
+                                  C.byref(p), C.byref(bad))
+        if rc:
+            e = FxError(rc, lib().fx_last_error().decode())
+            e.first_bad = int(bad.value)
+            raise e
+        return pinned_array(p.value, 4 ** int(k), np.int64)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)

@@ -841,6 +841,28 @@ class Fasta(_fxobj.FastaCore):
         blob = self._search_blob()
         return search.count_blob(blob, pattern, strand, degenerate, self._uppercase, self._st.device)
 
+    def kmer_counts(self, k, canonical=False, ids=None):
+        """Extension: the k-mer spectrum of the `seq` of every record -> int64[4**k] in pinned memory, counted on the GPU
+        from the resident stream (csrc/fx_kmer.hpp).  Letters A C G T in either case (A = 0, C = 1, G = 2, T = 3; uppercase=
+        plays no part); the index of a k-mer is its base-4 number, first base most significant; a window that holds any
+        other byte (N, IUPAC codes, ...) is not counted; windows run across line ends, never across records.  canonical=True
+        counts a window under the smaller of its code and its reverse complement's (a palindrome once); the other entries
+        stay 0.  ids: restrict to these records (names or 0-based ids; a record listed twice counts twice).  1 <= k <= 13:
+        the dense table is 8 * 4**k bytes, 512 MiB at k = 13; larger k needs a sparse form and is out of scope."""
+        from . import kmer
+        k = kmer.check_k(k)
+        sel = None if ids is None else self._ids_of(ids)
+        return kmer.fasta_counts_blob(self._search_blob(), k, canonical, sel)
+
+    def kmer_profile(self, k, canonical=False, ids=None, max_bytes=1 << 30):
+        """Extension: one k-mer spectrum per record -> int64[n_sel, 4**k] in pinned memory, rows in the order of ids (all
+        records in file order when None); the definition is kmer_counts'.  1 <= k <= 6; rows that would take more than
+        max_bytes: ValueError with the size, nothing allocated."""
+        from . import kmer
+        sel = None if ids is None else self._ids_of(ids)
+        kmer.check_profile(k, self._seq_counts if sel is None else len(sel), max_bytes)
+        return kmer.fasta_profile_blob(self._search_blob(), k, canonical, sel, self._seq_counts, max_bytes)
+
     def _search_blob(self):
         """The blob with the record table resident (installed once from the .fxi, as fetch_many does); a sharded or windowed
         stream has no halo for hits that straddle its cuts."""
@@ -1888,6 +1910,16 @@ class Fastq(_fxobj.FastqCore):
         from . import trim as _trim
         args = _trim.trim_args(clip_front, clip_tail, adapter, min_overlap, max_error_rate, front_qual, window, tail_qual)
         return _trim.trim_blob(self._qc_blob(), self._rlen_host.size, ids, self.phred, args)
+
+    def kmer_counts(self, k, canonical=False, ids=None, start=None, end=None):
+        """Extension: the k-mer spectrum of seq[start:end] of the reads `ids` -> int64[4**k] in pinned memory, counted on the
+        GPU from the resident stream (csrc/fx_kmer.hpp); the definition is Fasta.kmer_counts' (1 <= k <= 13).  ids, start and
+        end follow the rules of records: ids 0-based, any order, repeats allowed, None for every read; start / end both
+        None (whole reads) or what trim returned for the same ids -- fq.kmer_counts(11, ids=keep, start=iv["start"],
+        end=iv["end"]) is the spectrum of the selected, trimmed reads without a byte of them leaving the device."""
+        from . import kmer
+        k = kmer.check_k(k)
+        return kmer.fastq_counts_blob(self._qc_blob(), self._rlen_host.size, k, canonical, ids, start, end)
 
     def records(self, ids=None, start=None, end=None, min_len=0):
         """Extension: four-line FASTQ records of the reads `ids` (None: every read), cut to [start, end) -- what trim returned

@@ -45,6 +45,7 @@
 #include "fx_search.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
+#include "fx_kmer.hpp"
 
 using namespace fx;
 
@@ -321,10 +322,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq"};
 
 struct Prof {
     bool on = false;
@@ -3968,6 +3969,186 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
         h->prof.drain();
     }
     *dst = p_dst; *dst_off = p_off; *n_rows = n; *n_kept = kept;
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ k-mer spectra (fx_kmer.hpp)
+// Extension: the reference counts single letters only (composition).
+// `rows` spectra of 4^k counters on the device, cleared; the pinned block they come home to.
+struct KmerOut {
+    ScratchBuf<unsigned long long> dev;
+    int64_t *pin = nullptr;
+    int64_t words = 0;
+    int prepare(fx_handle *h, int k, int64_t rows, bool on_device) {
+        words = rows << (2 * k);
+        if (!(pin = (int64_t *)fx_pinned_alloc(std::max<int64_t>(words, 1) * 8))) return fail(FX_ENOMEM, "pinned block for %lld counters", (long long)words);
+        if (!on_device) { memset(pin, 0, (size_t)std::max<int64_t>(words, 1) * 8); return FX_OK; }
+        int rc = dev.alloc(h->device, words, h->stream);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(dev.p, 0, (size_t)words * 8, h->stream));
+        return FX_OK;
+    }
+    int home(fx_handle *h) {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(pin, dev.p, (size_t)words * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return fail(FX_EDEVICE, "k-mer count: %s", hipGetErrorString(e));
+        h->prof.drain();
+        return FX_OK;
+    }
+    int64_t *take() { int64_t *p = pin; pin = nullptr; return p; }
+    ~KmerOut() { if (pin) { (void)hipStreamSynchronize(dev.stream); fx_pinned_free(pin); } }
+};
+
+template <bool CANON, int MODE>
+static void kmer_fasta_launch(fx_handle *h, const SearchPlan &P, int k, unsigned long long *table, uint32_t *packed) {
+    static const int64_t resident = qc_resident(h, k_kmer_fasta<CANON, MODE>);
+    const int64_t per = KMER_MAX_WINDOWS / SRCH_RUN;          // runs per launch: no 32-bit counter of a workgroup can wrap
+    for (int64_t g0 = 0; g0 < P.n_runs; g0 += per) {
+        const int64_t g1 = std::min(g0 + per, P.n_runs);
+        const unsigned nb = (unsigned)std::min<int64_t>(nblocks(g1 - g0, BLOCK), MODE == 1 ? (int64_t)1 << 30 : resident);
+        FX_LAUNCH(h, K_KMER_FASTA, (k_kmer_fasta<CANON, MODE>), dim3(nb), dim3(BLOCK), P, k, g0, g1, table, packed);
+    }
+}
+
+extern "C" int fx_fasta_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, int per_record, int64_t **counts,
+                              int64_t *n_rows, int64_t *first_bad) {
+    if (!h || !counts || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
+    *counts = nullptr; *n_rows = 0; *first_bad = -1;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
+    if (flags & ~FX_KMER_CANONICAL) return fail(FX_EINVAL, "unknown flag bits %d", flags);
+    const int kmax = per_record ? KMER_LDS_K : KMER_MAX_K;
+    if (k < 1 || k > kmax) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, kmax);
+    int rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (rc) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    for (int64_t j = 0; ids && j < n_ids; ++j)
+        if (ids[j] < 0 || ids[j] >= h->n_hdr) { *first_bad = j; return fail(FX_ERANGE, "record id %lld outside the table", (long long)ids[j]); }
+    const int64_t rows = per_record ? n_sel : 1;
+    KmerOut out;
+    if (n_sel == 0) {
+        if ((rc = out.prepare(h, k, rows, false))) return rc;
+        *counts = out.take(); *n_rows = rows;
+        return FX_OK;
+    }
+    Staged st(h);
+    st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+    SearchPlan P;
+    P.mis = (int64_t)((uintptr_t)h->d_data & 15);
+    P.base = h->d_data - P.mis;
+    P.n = h->n;
+    P.boff = h->fa_boff.p; P.blen = h->fa_blen.p; P.slen = h->fa_slen.p;
+    P.n_sel = n_sel; P.plen = k;
+    P.sel = nullptr; P.run0 = nullptr; P.n_runs = 0; P.masks = nullptr;
+    if ((rc = st.up(h, ids, n_ids, &P.sel))) return rc;
+    int64_t *d_tot = nullptr;
+    if ((rc = st.scratch<int64_t>(8, &d_tot))) return rc;
+    auto scan = [&](auto ld, int64_t n, int64_t *dst) -> int {
+        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
+        int64_t *sums = nullptr;
+        int r2 = st.scratch<int64_t>(nch, &sums);
+        if (r2) return r2;
+        FX_LAUNCH(h, K_KMER_SCAN, (k_sscan_sums<1, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums);
+        FX_LAUNCH(h, K_KMER_SCAN, (k_sscan_top<1>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
+        FX_LAUNCH(h, K_KMER_SCAN, (k_sscan_apply<1, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, (const int64_t *)sums, dst);
+        HIPCHK(hipGetLastError());
+        return FX_OK;
+    };
+    // 1. runs of every selected record -> run0
+    int64_t *run0 = nullptr;
+    if ((rc = st.scratch<int64_t>(n_sel + 1, &run0)) || (rc = scan(SrchLdRuns{P}, n_sel, run0))) return rc;
+    int64_t n_runs = 0;
+    HIPCHK(hipMemcpyAsync(&n_runs, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    P.run0 = run0;
+    P.n_runs = n_runs;
+    if ((rc = out.prepare(h, k, rows, n_runs > 0))) return rc;
+    if (n_runs > 0) {
+        // 2. the count pass, the scan of the kept bytes, the windows past slen taken off again
+        ScratchBuf<uint32_t> packed;
+        ScratchBuf<int64_t> K;
+        if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
+        const bool canon = flags & FX_KMER_CANONICAL;
+        const int mode = per_record ? 2 : k <= KMER_LDS_K ? 0 : 1;
+        switch (mode * 2 + (canon ? 1 : 0)) {
+            case 0: kmer_fasta_launch<false, 0>(h, P, k, out.dev.p, packed.p); break;
+            case 1: kmer_fasta_launch<true, 0>(h, P, k, out.dev.p, packed.p); break;
+            case 2: kmer_fasta_launch<false, 1>(h, P, k, out.dev.p, packed.p); break;
+            case 3: kmer_fasta_launch<true, 1>(h, P, k, out.dev.p, packed.p); break;
+            case 4: kmer_fasta_launch<false, 2>(h, P, k, out.dev.p, packed.p); break;
+            default: kmer_fasta_launch<true, 2>(h, P, k, out.dev.p, packed.p); break;
+        }
+        if ((rc = scan(SrchLdKept{packed.p}, n_runs, K.p))) return rc;
+        const int64_t stride = per_record ? (int64_t)1 << (2 * k) : 0;
+        if (canon) FX_LAUNCH(h, K_KMER_FIX, k_kmer_fix<true>, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), P, (int)k, (const int64_t *)K.p, stride, out.dev.p);
+        else       FX_LAUNCH(h, K_KMER_FIX, k_kmer_fix<false>, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), P, (int)k, (const int64_t *)K.p, stride, out.dev.p);
+        if ((rc = out.home(h))) return rc;
+    }
+    *counts = out.take(); *n_rows = rows;
+    return FX_OK;
+}
+
+template <bool CANON, bool LDS>
+static void kmer_fastq_launch(fx_handle *h, int lpr, const int64_t *d_ids, int64_t nq, const int64_t *d_start, const int64_t *d_end, int k,
+                              unsigned long long *table) {
+    static const int64_t resident = qc_resident(h, k_kmer_fastq<CANON, LDS>);
+    // queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
+    const int64_t per = std::max<int64_t>(KMER_MAX_WINDOWS / std::max<int64_t>((int64_t)h->fq_maxlen, 1), 1);
+    for (int64_t q0 = 0; q0 < nq; q0 += per) {
+        const int64_t q1 = std::min(q0 + per, nq);
+        const unsigned nb = (unsigned)std::min<int64_t>(nblocks(q1 - q0, (BLOCK / 64) * (64 / lpr)), resident);
+        FX_LAUNCH(h, K_KMER_FASTQ, (k_kmer_fastq<CANON, LDS>), dim3(nb), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
+                  (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, d_ids, q0, q1, d_start, d_end, lpr, k, table);
+    }
+}
+
+extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start,
+                              const int64_t *end, int64_t **counts, int64_t *first_bad) {
+    if (!h || !counts || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    *counts = nullptr; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    QcLaunch q;
+    int rc = qc_prepare(h, 0, 0, &q);                          // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+    if (rc) return rc;
+    if (flags & ~FX_KMER_CANONICAL) return fail(FX_EINVAL, "unknown flag bits %d", flags);
+    if (k < 1 || k > KMER_MAX_K) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, KMER_MAX_K);
+    const int64_t n = ids ? n_ids : h->n_reads;
+    for (int64_t j = 0; ids && j < n_ids; ++j)
+        if (ids[j] < 0 || ids[j] >= h->n_reads) { *first_bad = j; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[j]); }
+    KmerOut out;
+    if (n == 0) {
+        if ((rc = out.prepare(h, k, 1, false))) return rc;
+        *counts = out.take();
+        return FX_OK;
+    }
+    Staged st(h);
+    st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
+    const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
+    if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+    if (start) {
+        unsigned long long *d_bad = nullptr, bad = ~0ull;
+        if ((rc = st.scratch<unsigned long long>(1, &d_bad))) return rc;
+        HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
+        FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)h->fq_rlen.p, d_ids, n, d_start, d_end, d_bad);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (bad != ~0ull) {
+            *first_bad = (int64_t)bad;
+            h->prof.drain();
+            return fail(FX_ERANGE, "the interval of query %lld lies outside its read", (long long)bad);
+        }
+    }
+    if ((rc = out.prepare(h, k, 1, true))) return rc;
+    const bool canon = flags & FX_KMER_CANONICAL, lds = k <= KMER_LDS_K;
+    if (canon) { if (lds) kmer_fastq_launch<true, true>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); else kmer_fastq_launch<true, false>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); }
+    else       { if (lds) kmer_fastq_launch<false, true>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); else kmer_fastq_launch<false, false>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); }
+    if ((rc = out.home(h))) return rc;
+    *counts = out.take();
     return FX_OK;
 }
 
