@@ -397,6 +397,14 @@ def check(rc):
         raise FxError(rc, lib().fx_last_error().decode("utf-8", "replace"))
 
 
+def _raise(rc, **attrs):
+    """FxError of a failed call, with what the call reported beside its code (first_bad=...) as attributes."""
+    e = FxError(rc, lib().fx_last_error().decode())
+    for k, v in attrs.items():
+        setattr(e, k, v)
+    raise e
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data
 
@@ -999,9 +1007,7 @@ class Blob:
         rc = lib().fx_fasta_fetch_alloc(self._h, n, _ptr(seq_id), _ptr(start), _ptr(stop), int(flags), _ptr(fpq),
                                         C.byref(dst), C.byref(offs), C.byref(bad))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.first_bad = int(bad.value)
-            raise e
+            _raise(rc, first_bad=int(bad.value))
         o = pinned_array(offs.value, n + 2, np.int64)[:n + 1]
         return pinned_array(dst.value, max(int(o[n]), 1))[:int(o[n])], o
 
@@ -1025,9 +1031,7 @@ class Blob:
         rc = lib().fx_fasta_search(self._h, _ptr(pat), _ptr(rpat), plen, int(mode), _ptr(ids), 0 if ids is None else ids.size,
                                    int(cap), C.byref(rec), C.byref(st), C.byref(sd), C.byref(n), _ptr(cnt))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.n_hits = int(n.value)
-            raise e
+            _raise(rc, n_hits=int(n.value))
         total = int(n.value)
         hits = None
         if rec.value:
@@ -1044,9 +1048,7 @@ class Blob:
         rc = lib().fx_fastq_fetch_alloc(self._h, n, _ptr(read_id), int(phred), int(seq_flags), w, C.byref(ps), C.byref(pq),
                                         C.byref(pi), C.byref(po), C.byref(bad))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.first_bad = int(bad.value)
-            raise e
+            _raise(rc, first_bad=int(bad.value))
         o = pinned_array(po.value, n + 2, np.int64)[:n + 1]
         tot = int(o[n])
         seq = pinned_array(ps.value, max(tot, 1))[:tot] if ps.value else None
@@ -1063,9 +1065,7 @@ class Blob:
         rc = lib().fx_fastq_read_stats(self._h, _ptr(ids), 0 if ids is None else ids.size, int(phred), int(low_qual),
                                        *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.first_bad = int(bad.value)
-            raise e
+            _raise(rc, first_bad=int(bad.value))
         m = int(n.value)
         names = (("length", np.int64), ("qsum", np.int64), ("qmin", np.int16), ("qmax", np.int16), ("n_low", np.int32),
                  ("n_gc", np.int32), ("n_other", np.int32))
@@ -1102,9 +1102,7 @@ class Blob:
                                  -1 if front_qual is None else int(front_qual), int(w[0]), int(w[1]), int(w[2]),
                                  -1 if tail_qual is None else int(tail_qual), C.byref(ps), C.byref(pe), C.byref(n), C.byref(bad))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.first_bad = int(bad.value)
-            raise e
+            _raise(rc, first_bad=int(bad.value))
         m = int(n.value)
         return pinned_array(ps.value, max(m, 1), np.int64)[:m], pinned_array(pe.value, max(m, 1), np.int64)[:m]
 
@@ -1119,9 +1117,7 @@ class Blob:
         rc = lib().fx_fastq_format_alloc(self._h, _ptr(ids), 0 if ids is None else ids.size, _ptr(start), _ptr(end), int(min_len),
                                          C.byref(pd), C.byref(po), C.byref(n), C.byref(kept), C.byref(bad))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.first_bad = int(bad.value)
-            raise e
+            _raise(rc, first_bad=int(bad.value))
         m = int(n.value)
         o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
         tot = int(o[m])
@@ -1144,9 +1140,7 @@ class Blob:
         rc = lib().fx_fasta_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, 1 if per_record else 0,
                                   C.byref(p), C.byref(rows), C.byref(bad))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.first_bad = int(bad.value)
-            raise e
+            _raise(rc, first_bad=int(bad.value))
         m, w = int(rows.value), 4 ** int(k)
         a = pinned_array(p.value, max(m * w, 1), np.int64)[:m * w]
         return a.reshape(m, w) if per_record else a
@@ -1164,9 +1158,7 @@ class Blob:
         rc = lib().fx_fastq_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, _ptr(start), _ptr(end),
                                   C.byref(p), C.byref(bad))
         if rc:
-            e = FxError(rc, lib().fx_last_error().decode())
-            e.first_bad = int(bad.value)
-            raise e
+            _raise(rc, first_bad=int(bad.value))
         return pinned_array(p.value, 4 ** int(k), np.int64)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):

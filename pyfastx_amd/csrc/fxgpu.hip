@@ -3452,6 +3452,142 @@ extern "C" int fx_fasta_fetch_alloc(fx_handle *h, int64_t n, const int64_t *seq_
     return FX_OK;
 }
 
+// ------------------------------------------------------------------ what the entries on the resident stream are built from
+// (search, FASTQ quality control, trimming and records, k-mer spectra: each is a kernel header plus an entry made of these)
+
+// One call per value of a template parameter: the launch is written once, in a generic lambda that takes the constant.
+template <class F> static void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int MAX, class F> static void with_int(int v, F &&f) {              // v in 0..MAX (a larger one counts as MAX)
+    if constexpr (MAX > 0) { if (v < MAX) return with_int<MAX - 1>(v, f); }
+    f(std::integral_constant<int, MAX>{});
+}
+
+// ids (null: the whole table) against the rows of the table; *first_bad (where asked for) = index of the first one outside
+static const char kBadRead[] = "read id %lld out of range", kBadRecord[] = "record id %lld outside the table";
+static int check_ids(const int64_t *ids, int64_t n_ids, int64_t limit, int64_t *first_bad, const char *fmt) {
+    for (int64_t k = 0; ids && k < n_ids; ++k)
+        if (ids[k] < 0 || ids[k] >= limit) { if (first_bad) *first_bad = k; return fail(FX_ERANGE, fmt, (long long)ids[k]); }
+    return FX_OK;
+}
+
+// The pinned result blocks of one call.  Unless release() has handed them to the caller they go back to the pool when the call
+// ends -- and a copy into them may still be in flight when something fails, so the stream is waited for first.
+template <int N> struct PinnedOut {
+    fx_handle *h;
+    void *p[N] = {};
+    explicit PinnedOut(fx_handle *hh) : h(hh) {}
+    bool alloc(int i, int64_t bytes) { return (p[i] = fx_pinned_alloc(bytes)) != nullptr; }
+    template <class T> T *as(int i) const { return (T *)p[i]; }
+    template <class... T> void release(T **...out) {       // block i -> *out[i] (an out that is null: not asked for, nothing allocated)
+        static_assert(sizeof...(T) == N, "one out-parameter per block");
+        int i = 0;
+        ((out ? (void)(*out = (T *)p[i++]) : (void)++i), ...);
+        for (void *&q : p) q = nullptr;
+    }
+    ~PinnedOut() {
+        if (std::all_of(p, p + N, [](void *q) { return !q; })) return;
+        (void)hipStreamSynchronize(h->stream);
+        for (void *q : p) fx_pinned_free(q);
+    }
+};
+
+// "copy a few totals home and wait"
+static int read_home(fx_handle *h, void *dst, const void *d_src, int64_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return FX_OK;
+}
+// The results home: the launches before it checked, the copies (one of no bytes is left out), one wait, the timings collected.
+struct D2H { void *dst; const void *src; int64_t bytes; };
+static int home(fx_handle *h, const char *what, const D2H *c, size_t n) {
+    hipError_t e = hipGetLastError();
+    for (size_t i = 0; i < n && e == hipSuccess; ++i)
+        if (c[i].bytes > 0) e = hipMemcpyAsync(c[i].dst, c[i].src, (size_t)c[i].bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(FX_EDEVICE, "%s: %s", what, hipGetErrorString(e));
+    h->prof.drain();
+    return FX_OK;
+}
+static int home(fx_handle *h, const char *what, std::initializer_list<D2H> c) { return home(h, what, c.begin(), c.size()); }
+
+// An exclusive scan of the C components ld(i, v) gives, over n elements, in chunks of SRCH_CHUNK (fx_search.hpp): the chunk sums
+// (arena; *sums_out) become the chunk offsets, the totals go to d_tot[0..C), out gets C arrays of n + 1 (out = nullptr: the
+// caller's own kernel applies the offsets, and no k_sscan_apply is made for this Ld).  Timed under `id`.
+template <int C, class Ld, class Out>
+static int sscan(fx_handle *h, Staged &st, int id, Ld ld, int64_t n, Out out, int64_t *d_tot, int64_t **sums_out = nullptr) {
+    const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
+    int64_t *sums = nullptr;
+    int rc = st.scratch<int64_t>(nch * C, &sums);
+    if (rc) return rc;
+    FX_LAUNCH(h, id, (k_sscan_sums<C, Ld>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums);
+    FX_LAUNCH(h, id, (k_sscan_top<C>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
+    if constexpr (!std::is_same_v<Out, std::nullptr_t>)
+        FX_LAUNCH(h, id, (k_sscan_apply<C, Ld>), dim3((unsigned)nch), dim3(BLOCK), ld, n, (const int64_t *)sums, (int64_t *)out);
+    HIPCHK(hipGetLastError());
+    if (sums_out) *sums_out = sums;
+    return FX_OK;
+}
+
+// The device's "first bad query" flag: kernels atomicMin the index of a query they reject into *d.
+struct BadFlag {
+    unsigned long long *d = nullptr;
+    int arm(fx_handle *h, Staged &st) {
+        int rc = st.scratch<unsigned long long>(1, &d);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(d, 0xFF, 8, h->stream));
+        return FX_OK;
+    }
+    // waits for the stream; *first = the index, or -1 (with an index the call is over: the timings are collected here)
+    int read(fx_handle *h, int64_t *first) {
+        unsigned long long bad = ~0ull;
+        int rc = read_home(h, &bad, d, 8);
+        if (rc) return rc;
+        *first = bad == ~0ull ? -1 : (int64_t)bad;
+        if (*first >= 0) h->prof.drain();
+        return FX_OK;
+    }
+};
+static const char kBadInterval[] = "the interval of query %lld lies outside its read";
+
+// The FASTQ stream and its table as the kernels take them.
+struct FqView { const uint8_t *data; int64_t base, n; const int64_t *rlen, *soff, *qoff; const int32_t *dlen; };
+static FqView fq_view(const fx_handle *h) { return {h->d_data, h->base, h->n, h->fq_rlen.p, h->fq_soff.p, h->fq_qoff.p, h->fq_dlen.p}; }
+
+// Workgroups of `kern` that are resident at once; the grid of a kernel that gives a group of lpr lanes to each of nq queries
+// and strides: enough workgroups for all of them, at most the resident ones (asked for once per kernel).
+template <class K> static int64_t resident_blocks(fx_handle *h, K kern) {
+    int per_cu = 0, n_cu = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BLOCK, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
+    return (int64_t)per_cu * std::max(n_cu, 1);
+}
+static int lane_groups(int lpr) { return (BLOCK / 64) * (64 / lpr); }           // queries a workgroup takes at a time
+template <auto KERN> static unsigned lane_group_grid(fx_handle *h, int64_t nq, int lpr) {
+    static const int64_t resident = resident_blocks(h, KERN);
+    return (unsigned)std::min<int64_t>(nblocks(nq, lane_groups(lpr)), resident);
+}
+
+// The plan of a pass over the runs of the selected FASTA records (fx_search.hpp): the 16-byte aligned view of the blob, the table,
+// the selection on the device, run0 = the exclusive scan of every record's runs (timed under `id`), their number read home into
+// *land (-> P->n_runs).  *d_tot: 8 words of the arena for the totals of this and later scans.
+static int fasta_run_plan(fx_handle *h, Staged &st, int id, const int64_t *ids, int64_t n_ids, int plen, SearchPlan *P, int64_t **d_tot,
+                          int64_t *land) {
+    int rc;
+    P->mis = (int64_t)((uintptr_t)h->d_data & 15);
+    P->base = h->d_data - P->mis;
+    P->n = h->n;
+    P->boff = h->fa_boff.p; P->blen = h->fa_blen.p; P->slen = h->fa_slen.p;
+    P->n_sel = ids ? n_ids : h->n_hdr; P->plen = plen;
+    P->sel = nullptr; P->run0 = nullptr; P->n_runs = 0;
+    int64_t *run0 = nullptr;
+    if ((rc = st.up(h, ids, n_ids, &P->sel)) || (rc = st.scratch<int64_t>(8, d_tot)) || (rc = st.scratch<int64_t>(P->n_sel + 1, &run0)) ||
+        (rc = sscan<1>(h, st, id, SrchLdRuns{*P}, P->n_sel, run0, *d_tot)) || (rc = read_home(h, land, *d_tot, 8)))
+        return rc;
+    P->run0 = run0;
+    P->n_runs = *land;
+    return FX_OK;
+}
+
 // ------------------------------------------------------------------ search (fx_search.hpp)
 // Shift-And masks of every byte value: bit j of .x (.y) is set when the byte matches letter j of the forward (reverse)
 // pattern.  Exact: byte equality with the byte as `seq` presents it (Py_TOUPPER first under FX_SEARCH_UPPER).  Degenerate:
@@ -3506,52 +3642,19 @@ extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *
         for (int c = 0; c < 256; ++c) masks[c] = make_ulonglong2(f[c], r[c]);
     }
     const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    for (int64_t k = 0; ids && k < n_ids; ++k)
-        if (ids[k] < 0 || ids[k] >= h->n_hdr) return fail(FX_ERANGE, "record id %lld outside the table", (long long)ids[k]);
+    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
     if (n_sel == 0) return FX_OK;
     Staged st(h);
     SearchPlan P;
-    P.mis = (int64_t)((uintptr_t)h->d_data & 15);
-    P.base = h->d_data - P.mis;
-    P.n = h->n;
-    P.boff = h->fa_boff.p; P.blen = h->fa_blen.p; P.slen = h->fa_slen.p;
-    P.n_sel = n_sel; P.plen = plen;
-    P.sel = nullptr; P.run0 = nullptr; P.n_runs = 0;
     const ulonglong2 *d_masks = nullptr;
-    if ((rc = st.up(h, masks.data(), 256, &d_masks)) || (rc = st.up(h, ids, n_ids, &P.sel))) return rc;
+    if ((rc = st.up(h, masks.data(), 256, &d_masks))) return rc;
     P.masks = d_masks;
     const bool wide = plen > 32;
-    int64_t *tot = (int64_t *)fx_pinned_alloc(64);
+    int64_t *tot = (int64_t *)fx_pinned_alloc(64), *d_tot = nullptr;        // tot: where the totals of the scans land
     if (!tot) return FX_ENOMEM;
     std::unique_ptr<int64_t, void (*)(int64_t *)> tot_guard(tot, [](int64_t *p) { fx_pinned_free(p); });
-    int64_t *d_tot = nullptr;
-    if ((rc = st.scratch<int64_t>(8, &d_tot))) return rc;
-    // an exclusive scan of C components over n elements -> out (C arrays of n + 1), totals -> d_tot
-    auto scan = [&](auto ld, auto cc, int64_t n, int64_t *out) -> int {
-        constexpr int C = decltype(cc)::value;
-        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
-        int64_t *sums = nullptr;
-        int r2 = st.scratch<int64_t>(nch * C, &sums);
-        if (r2) return r2;
-        FX_LAUNCH(h, K_SEARCH_SCAN, (k_sscan_sums<C, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums);
-        FX_LAUNCH(h, K_SEARCH_SCAN, (k_sscan_top<C>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
-        FX_LAUNCH(h, K_SEARCH_SCAN, (k_sscan_apply<C, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, (const int64_t *)sums, out);
-        HIPCHK(hipGetLastError());
-        return FX_OK;
-    };
-    using C1 = std::integral_constant<int, 1>;
-    using C3 = std::integral_constant<int, 3>;
-    auto read_tot = [&](int k) -> int {
-        HIPCHK(hipMemcpyAsync(tot, d_tot, (size_t)k * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return FX_OK;
-    };
     // 1. runs of every selected record -> run0
-    int64_t *run0 = nullptr;
-    if ((rc = st.scratch<int64_t>(n_sel + 1, &run0))) return rc;
-    if ((rc = scan(SrchLdRuns{P}, C1{}, n_sel, run0)) || (rc = read_tot(1))) return rc;
-    P.run0 = run0;
-    P.n_runs = tot[0];
+    if ((rc = fasta_run_plan(h, st, K_SEARCH_SCAN, ids, n_ids, plen, &P, &d_tot, tot))) return rc;
     if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one search grid");
     int64_t *cnt_dev = nullptr;
     if (P.n_runs == 0) {                       // nothing but empty records
@@ -3565,48 +3668,40 @@ extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *
     if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, 4 * nr1, h->stream))) return rc;
     int64_t *K = pref.p, *Pp = pref.p + nr1, *Pm = pref.p + 2 * nr1, *NZ = pref.p + 3 * nr1;
     const unsigned grid_runs = nblocks(P.n_runs, BLOCK), grid_sel = nblocks(n_sel, BLOCK);
-    if (wide) FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<true>, dim3(grid_runs), dim3(BLOCK), P, packed.p);
-    else      FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<false>, dim3(grid_runs), dim3(BLOCK), P, packed.p);
-    if ((rc = scan(SrchLdKept{packed.p}, C1{}, P.n_runs, K))) return rc;
-    if (wide) FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<true>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p);
-    else      FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<false>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p);
-    if ((rc = scan(SrchLdHits{packed.p}, C3{}, P.n_runs, Pp))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
+    with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<W()>, dim3(grid_runs), dim3(BLOCK), P, packed.p); });
+    if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{packed.p}, P.n_runs, K, d_tot))) return rc;
+    with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<W()>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p); });
+    if ((rc = sscan<3>(h, st, K_SEARCH_SCAN, SrchLdHits{packed.p}, P.n_runs, Pp, d_tot))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
     if (counts) {
         if ((rc = st.scratch<int64_t>(2 * n_sel, &cnt_dev))) return rc;
-        FX_LAUNCH(h, K_SEARCH_SCAN, k_search_rec_counts, dim3(grid_sel), dim3(BLOCK), (const int64_t *)run0, n_sel, (const int64_t *)Pp,
+        FX_LAUNCH(h, K_SEARCH_SCAN, k_search_rec_counts, dim3(grid_sel), dim3(BLOCK), (const int64_t *)P.run0, n_sel, (const int64_t *)Pp,
                   (const int64_t *)Pm, cnt_dev);
         HIPCHK(hipMemcpyAsync(counts, cnt_dev, (size_t)n_sel * 16, hipMemcpyDeviceToHost, h->stream));
     }
-    if ((rc = read_tot(3))) return rc;
+    if ((rc = read_home(h, tot, d_tot, 24))) return rc;
     const int64_t total = tot[0] + tot[1], n_list = tot[2];
     *n_hits = total;
     if (counts_only) { h->prof.drain(); return FX_OK; }
     if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
     // 3. emit: the runs with hits, at their offsets; the answers home by DMA into pinned blocks
-    int64_t *p_rec = (int64_t *)fx_pinned_alloc(std::max<int64_t>(total, 1) * 8), *p_start = (int64_t *)fx_pinned_alloc(std::max<int64_t>(total, 1) * 8);
-    uint8_t *p_strand = (uint8_t *)fx_pinned_alloc(std::max<int64_t>(total, 1));
-    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_rec); fx_pinned_free(p_start); fx_pinned_free(p_strand); return code; };
-    if (!p_rec || !p_start || !p_strand) return bail(fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total));
-    if (total > 0) {
+    PinnedOut<3> out(h);
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m)) return fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total);
+    if (total == 0) h->prof.drain();
+    else {
         ScratchBuf<int64_t> out64, list;
         ScratchBuf<uint8_t> out8;
         if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out8.alloc(h->device, total, h->stream)) ||
             (rc = list.alloc(h->device, n_list, h->stream)))
-            return bail(rc);
+            return rc;
         hipLaunchKernelGGL(k_search_list, dim3(grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
-        if (wide) FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<true>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
-                            (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
-        else      FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<false>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
-                            (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(p_rec, out64.p, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(p_start, out64.p + total, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(p_strand, out8.p, (size_t)total, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "search emit: %s", hipGetErrorString(e)));
+        with_bool(wide, [&](auto W) {
+            FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<W()>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
+                      (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
+        });
+        if ((rc = home(h, "search emit", {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], out8.p, total}}))) return rc;
     }
-    h->prof.drain();
-    *rec = p_rec; *start = p_start; *strand = p_strand;
+    out.release(rec, start, strand);
     return FX_OK;
 }
 
@@ -3623,12 +3718,10 @@ extern "C" int fx_fastq_fetch_alloc(fx_handle *h, int64_t n, const int64_t *read
     const bool w_seq = (want & 1) && seq, w_qual = (want & 2) && qual, w_qi = (want & 4) && quali;
     Staged st(h);
     PhaseClock pc;
-    int64_t *offs = nullptr;
-    void *outs[3] = {nullptr, nullptr, nullptr};
-    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(offs); for (void *p : outs) fx_pinned_free(p); return code; };
+    PinnedOut<4> out(h);                                   // seq, qual, quali, the offsets
     if (n == 0) {
-        if (!(offs = (int64_t *)fx_pinned_alloc(16))) return FX_ENOMEM;
-        offs[0] = 0;
+        if (!out.alloc(3, 16)) return FX_ENOMEM;
+        out.as<int64_t>(3)[0] = 0;
     } else {
         st.reserve_pin(n * 8 + 512);
         const int64_t *d_ids = nullptr;
@@ -3639,43 +3732,41 @@ extern "C" int fx_fastq_fetch_alloc(fx_handle *h, int64_t n, const int64_t *read
         HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
         hipLaunchKernelGGL(k_q_counts_fastq, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const int64_t *)h->fq_rlen.p, h->n_reads, d_ids, n, d_cnt, d_bad);
         pc.lap(0);
-        int64_t *d_off = nullptr;
+        int64_t *d_off = nullptr, *offs = nullptr;
         if ((rc = offsets_of_counts(h, st, d_cnt, d_bad, n, &d_off, &offs, first_bad))) return rc;
+        out.p[3] = offs;
         pc.lap(1);
-        if (*first_bad >= 0) return bail(fail(FX_ERANGE, "read id %lld out of range", (long long)read_id[*first_bad]));
+        if (*first_bad >= 0) return fail(FX_ERANGE, kBadRead, (long long)read_id[*first_bad]);
         const int64_t total = std::max<int64_t>(offs[n], 1);
         uint8_t *d_out[3] = {nullptr, nullptr, nullptr};
         const bool w[3] = {w_seq, w_qual, w_qi};
         for (int k = 0; k < 3; ++k)
             if (w[k]) {
-                if (!(outs[k] = fx_pinned_alloc(total))) return bail(FX_ENOMEM);
-                if ((rc = st.scratch<uint8_t>(total, &d_out[k]))) return bail(rc);
+                if (!out.alloc(k, total)) return FX_ENOMEM;
+                if ((rc = st.scratch<uint8_t>(total, &d_out[k]))) return rc;
             }
         pc.lap(2);
         FX_LAUNCH(h, K_FASTQ_FETCH, k_fastq_fetch, dim3(fetch_grid((n + 3) / 4)), dim3(BLOCK), h->d_data, h->base, h->n, h->fq_rlen.p,
                   h->fq_soff.p, h->fq_qoff.p, h->n_reads, d_ids, n, phred, seq_flags, d_out[0], d_out[1], (int8_t *)d_out[2], (const int64_t *)d_off);
-        if (hipGetLastError() != hipSuccess) return bail(fail(FX_EDEVICE, "launch failed"));
+        if (hipGetLastError() != hipSuccess) return fail(FX_EDEVICE, "launch failed");
         for (int k = 0; k < 3; ++k)
-            if (w[k] && hipMemcpyAsync(outs[k], d_out[k], (size_t)offs[n], hipMemcpyDeviceToHost, h->stream) != hipSuccess) return bail(fail(FX_EDEVICE, "D2H failed"));
+            if (w[k] && hipMemcpyAsync(out.p[k], d_out[k], (size_t)offs[n], hipMemcpyDeviceToHost, h->stream) != hipSuccess) return fail(FX_EDEVICE, "D2H failed");
         pc.lap(3);
-        if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(FX_EDEVICE, "stream synchronisation failed"));
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(FX_EDEVICE, "stream synchronisation failed");
         pc.lap(4);
         h->prof.drain();
     }
-    if (n == 0) for (int k = 0; k < 3; ++k) { const bool w[3] = {w_seq, w_qual, w_qi}; if (w[k] && !(outs[k] = fx_pinned_alloc(1))) return bail(FX_ENOMEM); }
-    if (w_seq) *seq = (uint8_t *)outs[0];
-    if (w_qual) *qual = (uint8_t *)outs[1];
-    if (w_qi) *quali = (int8_t *)outs[2];
-    *dst_off = offs;
+    if (n == 0) for (int k = 0; k < 3; ++k) { const bool w[3] = {w_seq, w_qual, w_qi}; if (w[k] && !out.alloc(k, 1)) return FX_ENOMEM; }
+    out.release(seq, qual, quali, dst_off);
     pc.done();
     return FX_OK;
 }
 
 // ------------------------------------------------------------------ FASTQ quality control (fx_fastq_qc.hpp)
-// What the three entry points share: the state checks, the offset and threshold in the form the kernels take them, lanes per read
-// from the mean read length (as fx_fastq_comp picks them), a grid of the workgroups that are resident at once.
-struct QcLaunch { int phred, thr, lpr; };
-static int qc_prepare(fx_handle *h, int phred, int low_qual, QcLaunch *q) {
+// What the entries on the FASTQ table share: the state checks, the offset and threshold in the form the kernels take them, lanes
+// per read from the mean read length (as fx_fastq_comp picks them).
+struct FqLaunch { int phred, thr, lpr; };
+static int fq_prepare(fx_handle *h, int phred, int low_qual, FqLaunch *q) {
     if (phred < 0 || phred > 255) return fail(FX_EINVAL, "phred %d outside 0..255", phred);
     if (low_qual < 0 || low_qual > 255) return fail(FX_EINVAL, "low_qual %d outside 0..255", low_qual);
     if (!h->fastq_built) return fail(FX_ESTATE, "fx_fastq_build has not run");
@@ -3688,18 +3779,11 @@ static int qc_prepare(fx_handle *h, int phred, int low_qual, QcLaunch *q) {
     q->lpr = (int)std::clamp<int64_t>((mean_len + 15) / 16, 1, 64);
     return FX_OK;
 }
-template <class K> static int64_t qc_resident(fx_handle *h, K kern) {
-    int per_cu = 0, n_cu = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BLOCK, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
-    return (int64_t)per_cu * std::max(n_cu, 1);
-}
 template <bool SELECT>
-static void qc_launch_reads(fx_handle *h, const QcLaunch &q, const int64_t *d_ids, int64_t nq, const QcCols &cols, const QcSel &sel, uint8_t *pass) {
-    static const int64_t resident = qc_resident(h, k_fq_read_stats<SELECT>);
-    const unsigned nb = (unsigned)std::min<int64_t>(nblocks(nq, (BLOCK / 64) * (64 / q.lpr)), resident);
-    FX_LAUNCH(h, SELECT ? K_FQ_SELECT : K_FQ_READ_STATS, k_fq_read_stats<SELECT>, dim3(nb), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
-              (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, d_ids, nq, q.phred, q.thr, q.lpr, cols, sel, pass);
+static void qc_launch_reads(fx_handle *h, const FqLaunch &q, const int64_t *d_ids, int64_t nq, const QcCols &cols, const QcSel &sel, uint8_t *pass) {
+    const FqView v = fq_view(h);
+    FX_LAUNCH(h, SELECT ? K_FQ_SELECT : K_FQ_READ_STATS, k_fq_read_stats<SELECT>, dim3(lane_group_grid<k_fq_read_stats<SELECT>>(h, nq, q.lpr)), dim3(BLOCK),
+              v.data, v.base, v.n, v.rlen, v.soff, v.qoff, d_ids, nq, q.phred, q.thr, q.lpr, cols, sel, pass);
 }
 
 extern "C" int fx_fastq_read_stats(fx_handle *h, const int64_t *ids, int64_t n_ids, int phred, int low_qual, int64_t **length, int64_t **qsum,
@@ -3709,38 +3793,33 @@ extern "C" int fx_fastq_read_stats(fx_handle *h, const int64_t *ids, int64_t n_i
     *length = *qsum = nullptr; *qmin = *qmax = nullptr; *n_low = *n_gc = *n_other = nullptr;
     *n_rows = 0; *first_bad = -1;
     if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
-    QcLaunch q;
-    int rc = qc_prepare(h, phred, low_qual, &q);
+    FqLaunch q;
+    int rc = fq_prepare(h, phred, low_qual, &q);
+    if (!rc) rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
     if (rc) return rc;
     const int64_t n = ids ? n_ids : h->n_reads;
-    for (int64_t k = 0; ids && k < n_ids; ++k)
-        if (ids[k] < 0 || ids[k] >= h->n_reads) { *first_bad = k; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[k]); }
     const int64_t m = std::max<int64_t>(n, 1);
     static const int width[7] = {8, 8, 2, 2, 4, 4, 4};
-    void *outs[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); for (void *p : outs) fx_pinned_free(p); return code; };
+    PinnedOut<7> out(h);
     for (int c = 0; c < 7; ++c)
-        if (!(outs[c] = fx_pinned_alloc(m * width[c]))) return bail(fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n));
+        if (!out.alloc(c, m * width[c])) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n);
     if (n > 0) {
         Staged st(h);
         st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
         const int64_t *d_ids = nullptr;
-        if ((rc = st.up(h, ids, ids ? n_ids : 0, &d_ids))) return bail(rc);
+        if ((rc = st.up(h, ids, ids ? n_ids : 0, &d_ids))) return rc;
         ScratchBuf<uint8_t> dev;                           // the seven columns, each from a 256-byte boundary
         int64_t at[8] = {0};
         for (int c = 0; c < 7; ++c) at[c + 1] = at[c] + ((n * width[c] + 255) & ~255ll);
-        if ((rc = dev.alloc(h->device, at[7], h->stream))) return bail(rc);
+        if ((rc = dev.alloc(h->device, at[7], h->stream))) return rc;
         QcCols cols{(int64_t *)(dev.p + at[0]), (int64_t *)(dev.p + at[1]), (int16_t *)(dev.p + at[2]), (int16_t *)(dev.p + at[3]),
                     (int32_t *)(dev.p + at[4]), (int32_t *)(dev.p + at[5]), (int32_t *)(dev.p + at[6])};
         qc_launch_reads<false>(h, q, d_ids, n, cols, QcSel{-1, -1, 0, 0, 0, 0, -1}, nullptr);
-        hipError_t e = hipGetLastError();
-        for (int c = 0; c < 7 && e == hipSuccess; ++c) e = hipMemcpyAsync(outs[c], dev.p + at[c], (size_t)(n * width[c]), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "read statistics: %s", hipGetErrorString(e)));
-        h->prof.drain();
+        D2H col[7];
+        for (int c = 0; c < 7; ++c) col[c] = {out.p[c], dev.p + at[c], n * width[c]};
+        if ((rc = home(h, "read statistics", col, 7))) return rc;
     }
-    *length = (int64_t *)outs[0]; *qsum = (int64_t *)outs[1]; *qmin = (int16_t *)outs[2]; *qmax = (int16_t *)outs[3];
-    *n_low = (int32_t *)outs[4]; *n_gc = (int32_t *)outs[5]; *n_other = (int32_t *)outs[6];
+    out.release(length, qsum, qmin, qmax, n_low, n_gc, n_other);
     *n_rows = n;
     return FX_OK;
 }
@@ -3752,38 +3831,31 @@ extern "C" int fx_fastq_select(fx_handle *h, int phred, int low_qual, int64_t mi
     const int64_t lim = 1000000000ll;
     if (mq_num < 0 || mq_num > lim || mq_den < 0 || mq_den > lim || lf_num < 0 || lf_num > lim || lf_den < 0 || lf_den > lim)
         return fail(FX_EINVAL, "a ratio outside 0..10^9");
-    QcLaunch q;
-    int rc = qc_prepare(h, phred, low_qual, &q);
+    FqLaunch q;
+    int rc = fq_prepare(h, phred, low_qual, &q);
     if (rc) return rc;
     const int64_t n = h->n_reads;
     int64_t total = 0;
-    int64_t *p_ids = nullptr;
+    PinnedOut<1> out(h);
     if (n > 0) {
         Staged st(h);
         ScratchBuf<uint8_t> pass;
-        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
         int64_t *sums = nullptr, *d_tot = nullptr;
-        if ((rc = pass.alloc(h->device, n, h->stream)) || (rc = st.scratch<int64_t>(nch, &sums)) || (rc = st.scratch<int64_t>(1, &d_tot))) return rc;
+        if ((rc = pass.alloc(h->device, n, h->stream)) || (rc = st.scratch<int64_t>(1, &d_tot))) return rc;
         qc_launch_reads<true>(h, q, nullptr, n, QcCols{}, QcSel{min_len, max_len, mq_num, mq_den, lf_num, lf_den, max_other}, pass.p);
-        FX_LAUNCH(h, K_FQ_SELECT_SCAN, (k_sscan_sums<1, QcLdPass>), dim3((unsigned)nch), dim3(BLOCK), QcLdPass{pass.p}, n, sums);
-        FX_LAUNCH(h, K_FQ_SELECT_SCAN, (k_sscan_top<1>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&total, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (!(p_ids = (int64_t *)fx_pinned_alloc(std::max<int64_t>(total, 1) * 8))) return fail(FX_ENOMEM, "pinned block for %lld ids", (long long)total);
-        if (total > 0) {
-            ScratchBuf<int64_t> out;
-            hipError_t e = hipSuccess;
-            if ((rc = out.alloc(h->device, total, h->stream))) { fx_pinned_free(p_ids); return rc; }
-            FX_LAUNCH(h, K_FQ_SELECT_EMIT, k_fq_select_emit, dim3((unsigned)nch), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, out.p);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(p_ids, out.p, (size_t)total * 8, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_ids); return fail(FX_EDEVICE, "select emit: %s", hipGetErrorString(e)); }
+        // the chunk offsets and the total; k_fq_select_emit applies the offsets itself
+        if ((rc = sscan<1>(h, st, K_FQ_SELECT_SCAN, QcLdPass{pass.p}, n, nullptr, d_tot, &sums)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
+        if (!out.alloc(0, std::max<int64_t>(total, 1) * 8)) return fail(FX_ENOMEM, "pinned block for %lld ids", (long long)total);
+        if (total == 0) h->prof.drain();
+        else {
+            ScratchBuf<int64_t> dev;
+            if ((rc = dev.alloc(h->device, total, h->stream))) return rc;
+            FX_LAUNCH(h, K_FQ_SELECT_EMIT, k_fq_select_emit, dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, dev.p);
+            if ((rc = home(h, "select emit", {{out.p[0], dev.p, total * 8}}))) return rc;
         }
-        h->prof.drain();
-    } else if (!(p_ids = (int64_t *)fx_pinned_alloc(8))) return FX_ENOMEM;
-    *ids = p_ids; *n_ids = total;
+    } else if (!out.alloc(0, 8)) return FX_ENOMEM;
+    out.release(ids);
+    *n_ids = total;
     return FX_OK;
 }
 
@@ -3791,48 +3863,36 @@ extern "C" int fx_fastq_cycle_hist(fx_handle *h, int32_t cycles, int64_t **qual,
     if (!h || !qual || !base || !depth) return fail(FX_EINVAL, "null argument");
     *qual = *base = *depth = nullptr;
     if (cycles < 1 || cycles > 65536) return fail(FX_EINVAL, "cycles %d outside 1..65536", (int)cycles);
-    QcLaunch q;
-    int rc = qc_prepare(h, 0, 0, &q);
+    FqLaunch q;
+    int rc = fq_prepare(h, 0, 0, &q);
     if (rc) return rc;
     const int64_t nq = (int64_t)cycles * 256, nb = (int64_t)cycles * 5;
-    int64_t *p_qual = (int64_t *)fx_pinned_alloc(nq * 8), *p_base = (int64_t *)fx_pinned_alloc(nb * 8), *p_depth = (int64_t *)fx_pinned_alloc((int64_t)cycles * 8);
-    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_qual); fx_pinned_free(p_base); fx_pinned_free(p_depth); return code; };
-    if (!p_qual || !p_base || !p_depth) return bail(fail(FX_ENOMEM, "pinned blocks for %d cycles", (int)cycles));
+    PinnedOut<3> out(h);
+    if (!out.alloc(0, nq * 8) || !out.alloc(1, nb * 8) || !out.alloc(2, (int64_t)cycles * 8)) return fail(FX_ENOMEM, "pinned blocks for %d cycles", (int)cycles);
     {
         ScratchBuf<unsigned long long> cnt;                 // qual, then base
-        if ((rc = cnt.alloc(h->device, nq + nb, h->stream))) return bail(rc);
-        hipError_t e = hipMemsetAsync(cnt.p, 0, (size_t)(nq + nb) * 8, h->stream);
-        if (e == hipSuccess && h->n_reads > 0) {
+        if ((rc = cnt.alloc(h->device, nq + nb, h->stream))) return rc;
+        const hipError_t e = hipMemsetAsync(cnt.p, 0, (size_t)(nq + nb) * 8, h->stream);
+        if (e != hipSuccess) return fail(FX_EDEVICE, "cycle histogram: %s", hipGetErrorString(e));
+        if (h->n_reads > 0) {
             // the waves are dealt over the tiles of 64 cycles: at least one wave per tile, else the workgroups resident at once
-            static const int64_t resident = qc_resident(h, k_fq_cycle_hist);
+            static const int64_t resident = resident_blocks(h, k_fq_cycle_hist);
             const int n_tiles = (cycles + 63) / 64;
             const int64_t blocks = std::max<int64_t>(resident, (n_tiles + BLOCK / 64 - 1) / (BLOCK / 64));
-            FX_LAUNCH(h, K_FQ_CYCLE_HIST, k_fq_cycle_hist, dim3((unsigned)blocks), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
-                      (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, h->n_reads, (int)cycles, n_tiles,
-                      cnt.p, cnt.p + nq);
-            e = hipGetLastError();
+            const FqView v = fq_view(h);
+            FX_LAUNCH(h, K_FQ_CYCLE_HIST, k_fq_cycle_hist, dim3((unsigned)blocks), dim3(BLOCK), v.data, v.base, v.n, v.rlen, v.soff, v.qoff, h->n_reads,
+                      (int)cycles, n_tiles, cnt.p, cnt.p + nq);
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(p_qual, cnt.p, (size_t)nq * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(p_base, cnt.p + nq, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "cycle histogram: %s", hipGetErrorString(e)));
-        h->prof.drain();
+        if ((rc = home(h, "cycle histogram", {{out.p[0], cnt.p, nq * 8}, {out.p[1], cnt.p + nq, nb * 8}}))) return rc;
     }
+    int64_t *p_base = out.as<int64_t>(1), *p_depth = out.as<int64_t>(2);
     for (int64_t j = 0; j < cycles; ++j) p_depth[j] = p_base[j * 5] + p_base[j * 5 + 1] + p_base[j * 5 + 2] + p_base[j * 5 + 3] + p_base[j * 5 + 4];
-    *qual = p_qual; *base = p_base; *depth = p_depth;
+    out.release(qual, base, depth);
     return FX_OK;
 }
 
 // ------------------------------------------------------------------ FASTQ trimming and trimmed records (fx_fastq_trim.hpp)
 // Extension: the reference has no counterpart (it writes verbatim copies only, read.c:124-150).
-template <int NW>
-static void trim_launch(fx_handle *h, int lpr, const int64_t *d_ids, int64_t nq, const TrimPar &P, int64_t *d_start, int64_t *d_end) {
-    static const int64_t resident = qc_resident(h, k_fq_trim<NW>);
-    const unsigned nb = (unsigned)std::min<int64_t>(nblocks(nq, (BLOCK / 64) * (64 / lpr)), resident);
-    FX_LAUNCH(h, K_FQ_TRIM, k_fq_trim<NW>, dim3(nb), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n, (const int64_t *)h->fq_rlen.p,
-              (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, d_ids, nq, lpr, P, d_start, d_end);
-}
-
 extern "C" int fx_fastq_trim(fx_handle *h, const int64_t *ids, int64_t n_ids, int phred, int64_t clip_front, int64_t clip_tail,
                              const uint8_t *adapter, int32_t adapter_len, int32_t min_overlap, int64_t err_num, int64_t err_den,
                              int32_t front_qual, int32_t win_len, int64_t win_num, int64_t win_den, int32_t tail_qual,
@@ -3859,44 +3919,36 @@ extern "C" int fx_fastq_trim(fx_handle *h, const int64_t *ids, int64_t n_ids, in
         }
         P.alen = adapter_len; P.min_overlap = min_overlap; P.err_num = err_num; P.err_den = err_den;
     }
-    QcLaunch q;
-    int rc = qc_prepare(h, phred, 0, &q);
+    FqLaunch q;
+    int rc = fq_prepare(h, phred, 0, &q);
     if (rc) return rc;
     P.phred = q.phred; P.clip_front = clip_front; P.clip_tail = clip_tail;
     P.front_thr = front_qual < 0 ? -1 : std::min(q.phred + front_qual, 256);
     P.tail_thr = tail_qual < 0 ? -1 : std::min(q.phred + tail_qual, 256);
     P.win_len = win_len; P.win_num = win_num; P.win_den = win_len > 0 ? win_den : 1;
     const int64_t n = ids ? n_ids : h->n_reads;
-    for (int64_t k = 0; ids && k < n_ids; ++k)
-        if (ids[k] < 0 || ids[k] >= h->n_reads) { *first_bad = k; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[k]); }
+    if ((rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead))) return rc;
     const int64_t m = std::max<int64_t>(n, 1);
-    int64_t *p_start = (int64_t *)fx_pinned_alloc(m * 8), *p_end = (int64_t *)fx_pinned_alloc(m * 8);
-    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_start); fx_pinned_free(p_end); return code; };
-    if (!p_start || !p_end) return bail(fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n));
+    PinnedOut<2> out(h);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n);
     if (n > 0) {
         Staged st(h);
         st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
         const int64_t *d_ids = nullptr;
-        if ((rc = st.up(h, ids, ids ? n_ids : 0, &d_ids))) return bail(rc);
+        if ((rc = st.up(h, ids, ids ? n_ids : 0, &d_ids))) return rc;
         ScratchBuf<int64_t> dev;                           // start, then end
-        if ((rc = dev.alloc(h->device, 2 * n, h->stream))) return bail(rc);
+        if ((rc = dev.alloc(h->device, 2 * n, h->stream))) return rc;
         // a lane group holds the longest read at once (up to 1024 bytes; a longer one is walked by one lane)
         const int lpr = (int)std::clamp<int64_t>(((int64_t)h->fq_maxlen + 15) / 16, 1, 64);
-        switch ((P.alen + 15) / 16) {
-            case 0: trim_launch<0>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
-            case 1: trim_launch<1>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
-            case 2: trim_launch<2>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
-            case 3: trim_launch<3>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
-            default: trim_launch<4>(h, lpr, d_ids, n, P, dev.p, dev.p + n); break;
-        }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(p_start, dev.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(p_end, dev.p + n, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "trim: %s", hipGetErrorString(e)));
-        h->prof.drain();
+        const FqView v = fq_view(h);
+        with_int<4>((P.alen + 15) / 16, [&](auto NW) {      // words of adapter letters the kernel keeps
+            FX_LAUNCH(h, K_FQ_TRIM, k_fq_trim<NW()>, dim3(lane_group_grid<k_fq_trim<NW()>>(h, n, lpr)), dim3(BLOCK), v.data, v.base, v.n, v.rlen, v.soff,
+                      v.qoff, d_ids, n, lpr, P, dev.p, dev.p + n);
+        });
+        if ((rc = home(h, "trim", {{out.p[0], dev.p, n * 8}, {out.p[1], dev.p + n, n * 8}}))) return rc;
     }
-    *start = p_start; *end = p_end; *n_rows = n;
+    out.release(start, end);
+    *n_rows = n;
     return FX_OK;
 }
 
@@ -3907,68 +3959,46 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
     if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     if (min_len < 0) return fail(FX_EINVAL, "negative min_len");
-    QcLaunch q;
-    int rc = qc_prepare(h, 0, 0, &q);
+    FqLaunch q;
+    int rc = fq_prepare(h, 0, 0, &q);
+    if (!rc) rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
     if (rc) return rc;
     const int64_t n = ids ? n_ids : h->n_reads;
-    for (int64_t k = 0; ids && k < n_ids; ++k)
-        if (ids[k] < 0 || ids[k] >= h->n_reads) { *first_bad = k; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[k]); }
-    uint8_t *p_dst = nullptr;
-    int64_t *p_off = nullptr;
-    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(p_dst); fx_pinned_free(p_off); return code; };
+    PinnedOut<2> out(h);                                   // the records, their offsets
     int64_t kept = 0;
     if (n == 0) {
-        p_dst = (uint8_t *)fx_pinned_alloc(1); p_off = (int64_t *)fx_pinned_alloc(16);
-        if (!p_dst || !p_off) return bail(FX_ENOMEM);
-        p_off[0] = 0;
+        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
+        out.as<int64_t>(1)[0] = 0;
     } else {
         Staged st(h);
         st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
         const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
         if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
-        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
         ScratchBuf<int64_t> cnt, offs;                     // record sizes; exclusive offsets (n + 1), then the kept counts (n + 1)
-        int64_t *sums = nullptr, *d_tot = nullptr;
-        unsigned long long *d_bad = nullptr;
-        if ((rc = cnt.alloc(h->device, n, h->stream)) || (rc = offs.alloc(h->device, 2 * (n + 1), h->stream)) ||
-            (rc = st.scratch<int64_t>(nch * 2, &sums)) || (rc = st.scratch<int64_t>(2, &d_tot)) || (rc = st.scratch<unsigned long long>(1, &d_bad))) return rc;
-        HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
-        FX_LAUNCH(h, K_FQ_FORMAT_COUNT, k_fq_format_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
-                  (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, (const int32_t *)h->fq_dlen.p, d_ids, n, d_start, d_end, min_len, cnt.p, d_bad);
-        FX_LAUNCH(h, K_FQ_FORMAT_SCAN, (k_sscan_sums<2, FmtLdCnt>), dim3((unsigned)nch), dim3(BLOCK), FmtLdCnt{cnt.p}, n, sums);
-        FX_LAUNCH(h, K_FQ_FORMAT_SCAN, (k_sscan_top<2>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
-        FX_LAUNCH(h, K_FQ_FORMAT_SCAN, (k_sscan_apply<2, FmtLdCnt>), dim3((unsigned)nch), dim3(BLOCK), FmtLdCnt{cnt.p}, n, (const int64_t *)sums, offs.p);
-        HIPCHK(hipGetLastError());
-        int64_t tot[2] = {0, 0};
-        unsigned long long bad = ~0ull;
-        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (bad != ~0ull) {
-            *first_bad = (int64_t)bad;
-            h->prof.drain();
-            return fail(FX_ERANGE, "the interval of query %lld lies outside its read", (long long)bad);
-        }
+        int64_t *d_tot = nullptr, tot[2] = {0, 0};
+        BadFlag bad;
+        if ((rc = cnt.alloc(h->device, n, h->stream)) || (rc = offs.alloc(h->device, 2 * (n + 1), h->stream)) || (rc = st.scratch<int64_t>(2, &d_tot)) ||
+            (rc = bad.arm(h, st)))
+            return rc;
+        const FqView v = fq_view(h);
+        FX_LAUNCH(h, K_FQ_FORMAT_COUNT, k_fq_format_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.data, v.base, v.n, v.rlen, v.soff, v.dlen, d_ids, n,
+                  d_start, d_end, min_len, cnt.p, bad.d);
+        if ((rc = sscan<2>(h, st, K_FQ_FORMAT_SCAN, FmtLdCnt{cnt.p}, n, offs.p, d_tot))) return rc;
+        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h->stream));             // (lands before the flag does)
+        if ((rc = bad.read(h, first_bad))) return rc;
+        if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
         const int64_t total = tot[0];
         kept = tot[1];
-        p_dst = (uint8_t *)fx_pinned_alloc(std::max<int64_t>(total, 1)); p_off = (int64_t *)fx_pinned_alloc((n + 1) * 8);
-        if (!p_dst || !p_off) return bail(fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total));
-        ScratchBuf<uint8_t> out;
-        if ((rc = out.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return bail(rc);
-        hipError_t e = hipSuccess;
-        if (total > 0) {
-            FX_LAUNCH(h, K_FQ_FORMAT_EMIT, k_fq_format_emit, dim3(nblocks(n, (BLOCK / 64) * (64 / q.lpr))), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
-                      (const int64_t *)h->fq_soff.p, (const int64_t *)h->fq_qoff.p, (const int32_t *)h->fq_dlen.p, d_ids, n, d_start,
-                      (const int64_t *)offs.p, q.lpr, out.p);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(p_dst, out.p, (size_t)total, hipMemcpyDeviceToHost, h->stream);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(p_off, offs.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return bail(fail(FX_EDEVICE, "format: %s", hipGetErrorString(e)));
-        h->prof.drain();
+        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
+        ScratchBuf<uint8_t> dev;
+        if ((rc = dev.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return rc;
+        if (total > 0)                                     // (every record at once: the grid is not capped at the resident workgroups)
+            FX_LAUNCH(h, K_FQ_FORMAT_EMIT, k_fq_format_emit, dim3(nblocks(n, lane_groups(q.lpr))), dim3(BLOCK), v.data, v.base, v.n, v.soff, v.qoff, v.dlen,
+                      d_ids, n, d_start, (const int64_t *)offs.p, q.lpr, dev.p);
+        if ((rc = home(h, "format", {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}}))) return rc;
     }
-    *dst = p_dst; *dst_off = p_off; *n_rows = n; *n_kept = kept;
+    out.release(dst, dst_off);
+    *n_rows = n; *n_kept = kept;
     return FX_OK;
 }
 
@@ -3977,32 +4007,24 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
 // `rows` spectra of 4^k counters on the device, cleared; the pinned block they come home to.
 struct KmerOut {
     ScratchBuf<unsigned long long> dev;
-    int64_t *pin = nullptr;
+    PinnedOut<1> pin;
     int64_t words = 0;
+    explicit KmerOut(fx_handle *h) : pin(h) {}
     int prepare(fx_handle *h, int k, int64_t rows, bool on_device) {
         words = rows << (2 * k);
-        if (!(pin = (int64_t *)fx_pinned_alloc(std::max<int64_t>(words, 1) * 8))) return fail(FX_ENOMEM, "pinned block for %lld counters", (long long)words);
-        if (!on_device) { memset(pin, 0, (size_t)std::max<int64_t>(words, 1) * 8); return FX_OK; }
+        if (!pin.alloc(0, std::max<int64_t>(words, 1) * 8)) return fail(FX_ENOMEM, "pinned block for %lld counters", (long long)words);
+        if (!on_device) { memset(pin.p[0], 0, (size_t)std::max<int64_t>(words, 1) * 8); return FX_OK; }
         int rc = dev.alloc(h->device, words, h->stream);
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(dev.p, 0, (size_t)words * 8, h->stream));
         return FX_OK;
     }
-    int home(fx_handle *h) {
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(pin, dev.p, (size_t)words * 8, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) return fail(FX_EDEVICE, "k-mer count: %s", hipGetErrorString(e));
-        h->prof.drain();
-        return FX_OK;
-    }
-    int64_t *take() { int64_t *p = pin; pin = nullptr; return p; }
-    ~KmerOut() { if (pin) { (void)hipStreamSynchronize(dev.stream); fx_pinned_free(pin); } }
+    int home(fx_handle *h) { return ::home(h, "k-mer count", {{pin.p[0], dev.p, words * 8}}); }
 };
 
 template <bool CANON, int MODE>
 static void kmer_fasta_launch(fx_handle *h, const SearchPlan &P, int k, unsigned long long *table, uint32_t *packed) {
-    static const int64_t resident = qc_resident(h, k_kmer_fasta<CANON, MODE>);
+    static const int64_t resident = resident_blocks(h, k_kmer_fasta<CANON, MODE>);
     const int64_t per = KMER_MAX_WINDOWS / SRCH_RUN;          // runs per launch: no 32-bit counter of a workgroup can wrap
     for (int64_t g0 = 0; g0 < P.n_runs; g0 += per) {
         const int64_t g1 = std::min(g0 + per, P.n_runs);
@@ -4023,86 +4045,40 @@ extern "C" int fx_fasta_kmers(fx_handle *h, int32_t k, int flags, const int64_t 
     if (k < 1 || k > kmax) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, kmax);
     int rc = use_device(h);
     if (!rc) rc = finish_build(h);
+    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, first_bad, kBadRecord);
     if (rc) return rc;
     const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    for (int64_t j = 0; ids && j < n_ids; ++j)
-        if (ids[j] < 0 || ids[j] >= h->n_hdr) { *first_bad = j; return fail(FX_ERANGE, "record id %lld outside the table", (long long)ids[j]); }
     const int64_t rows = per_record ? n_sel : 1;
-    KmerOut out;
-    if (n_sel == 0) {
-        if ((rc = out.prepare(h, k, rows, false))) return rc;
-        *counts = out.take(); *n_rows = rows;
-        return FX_OK;
-    }
-    Staged st(h);
-    st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
-    SearchPlan P;
-    P.mis = (int64_t)((uintptr_t)h->d_data & 15);
-    P.base = h->d_data - P.mis;
-    P.n = h->n;
-    P.boff = h->fa_boff.p; P.blen = h->fa_blen.p; P.slen = h->fa_slen.p;
-    P.n_sel = n_sel; P.plen = k;
-    P.sel = nullptr; P.run0 = nullptr; P.n_runs = 0; P.masks = nullptr;
-    if ((rc = st.up(h, ids, n_ids, &P.sel))) return rc;
-    int64_t *d_tot = nullptr;
-    if ((rc = st.scratch<int64_t>(8, &d_tot))) return rc;
-    auto scan = [&](auto ld, int64_t n, int64_t *dst) -> int {
-        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
-        int64_t *sums = nullptr;
-        int r2 = st.scratch<int64_t>(nch, &sums);
-        if (r2) return r2;
-        FX_LAUNCH(h, K_KMER_SCAN, (k_sscan_sums<1, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums);
-        FX_LAUNCH(h, K_KMER_SCAN, (k_sscan_top<1>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
-        FX_LAUNCH(h, K_KMER_SCAN, (k_sscan_apply<1, decltype(ld)>), dim3((unsigned)nch), dim3(BLOCK), ld, n, (const int64_t *)sums, dst);
-        HIPCHK(hipGetLastError());
-        return FX_OK;
-    };
-    // 1. runs of every selected record -> run0
-    int64_t *run0 = nullptr;
-    if ((rc = st.scratch<int64_t>(n_sel + 1, &run0)) || (rc = scan(SrchLdRuns{P}, n_sel, run0))) return rc;
-    int64_t n_runs = 0;
-    HIPCHK(hipMemcpyAsync(&n_runs, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    P.run0 = run0;
-    P.n_runs = n_runs;
-    if ((rc = out.prepare(h, k, rows, n_runs > 0))) return rc;
-    if (n_runs > 0) {
-        // 2. the count pass, the scan of the kept bytes, the windows past slen taken off again
-        ScratchBuf<uint32_t> packed;
-        ScratchBuf<int64_t> K;
-        if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
-        const bool canon = flags & FX_KMER_CANONICAL;
-        const int mode = per_record ? 2 : k <= KMER_LDS_K ? 0 : 1;
-        switch (mode * 2 + (canon ? 1 : 0)) {
-            case 0: kmer_fasta_launch<false, 0>(h, P, k, out.dev.p, packed.p); break;
-            case 1: kmer_fasta_launch<true, 0>(h, P, k, out.dev.p, packed.p); break;
-            case 2: kmer_fasta_launch<false, 1>(h, P, k, out.dev.p, packed.p); break;
-            case 3: kmer_fasta_launch<true, 1>(h, P, k, out.dev.p, packed.p); break;
-            case 4: kmer_fasta_launch<false, 2>(h, P, k, out.dev.p, packed.p); break;
-            default: kmer_fasta_launch<true, 2>(h, P, k, out.dev.p, packed.p); break;
+    KmerOut out(h);
+    if (n_sel > 0) {
+        Staged st(h);
+        st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+        // 1. runs of every selected record -> run0
+        SearchPlan P;
+        P.masks = nullptr;
+        int64_t *d_tot = nullptr, n_runs = 0;
+        if ((rc = fasta_run_plan(h, st, K_KMER_SCAN, ids, n_ids, k, &P, &d_tot, &n_runs))) return rc;
+        if ((rc = out.prepare(h, k, rows, n_runs > 0))) return rc;
+        if (n_runs > 0) {
+            // 2. the count pass, the scan of the kept bytes, the windows past slen taken off again
+            ScratchBuf<uint32_t> packed;
+            ScratchBuf<int64_t> K;
+            if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
+            const bool canon = flags & FX_KMER_CANONICAL;
+            const int64_t stride = per_record ? (int64_t)1 << (2 * k) : 0;
+            with_bool(canon, [&](auto C) {
+                with_int<2>(per_record ? 2 : k <= KMER_LDS_K ? 0 : 1, [&](auto M) { kmer_fasta_launch<C(), M()>(h, P, k, out.dev.p, packed.p); });
+            });
+            if ((rc = sscan<1>(h, st, K_KMER_SCAN, SrchLdKept{packed.p}, n_runs, K.p, d_tot))) return rc;
+            with_bool(canon, [&](auto C) {
+                FX_LAUNCH(h, K_KMER_FIX, k_kmer_fix<C()>, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), P, (int)k, (const int64_t *)K.p, stride, out.dev.p);
+            });
+            if ((rc = out.home(h))) return rc;
         }
-        if ((rc = scan(SrchLdKept{packed.p}, n_runs, K.p))) return rc;
-        const int64_t stride = per_record ? (int64_t)1 << (2 * k) : 0;
-        if (canon) FX_LAUNCH(h, K_KMER_FIX, k_kmer_fix<true>, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), P, (int)k, (const int64_t *)K.p, stride, out.dev.p);
-        else       FX_LAUNCH(h, K_KMER_FIX, k_kmer_fix<false>, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), P, (int)k, (const int64_t *)K.p, stride, out.dev.p);
-        if ((rc = out.home(h))) return rc;
-    }
-    *counts = out.take(); *n_rows = rows;
+    } else if ((rc = out.prepare(h, k, rows, false))) return rc;
+    out.pin.release(counts);
+    *n_rows = rows;
     return FX_OK;
-}
-
-template <bool CANON, bool LDS>
-static void kmer_fastq_launch(fx_handle *h, int lpr, const int64_t *d_ids, int64_t nq, const int64_t *d_start, const int64_t *d_end, int k,
-                              unsigned long long *table) {
-    static const int64_t resident = qc_resident(h, k_kmer_fastq<CANON, LDS>);
-    // queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
-    const int64_t per = std::max<int64_t>(KMER_MAX_WINDOWS / std::max<int64_t>((int64_t)h->fq_maxlen, 1), 1);
-    for (int64_t q0 = 0; q0 < nq; q0 += per) {
-        const int64_t q1 = std::min(q0 + per, nq);
-        const unsigned nb = (unsigned)std::min<int64_t>(nblocks(q1 - q0, (BLOCK / 64) * (64 / lpr)), resident);
-        FX_LAUNCH(h, K_KMER_FASTQ, (k_kmer_fastq<CANON, LDS>), dim3(nb), dim3(BLOCK), (const uint8_t *)h->d_data, h->base, h->n,
-                  (const int64_t *)h->fq_rlen.p, (const int64_t *)h->fq_soff.p, d_ids, q0, q1, d_start, d_end, lpr, k, table);
-    }
 }
 
 extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start,
@@ -4111,44 +4087,43 @@ extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t 
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     *counts = nullptr; *first_bad = -1;
     if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
-    QcLaunch q;
-    int rc = qc_prepare(h, 0, 0, &q);                          // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+    FqLaunch q;
+    int rc = fq_prepare(h, 0, 0, &q);                          // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
     if (rc) return rc;
     if (flags & ~FX_KMER_CANONICAL) return fail(FX_EINVAL, "unknown flag bits %d", flags);
     if (k < 1 || k > KMER_MAX_K) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, KMER_MAX_K);
     const int64_t n = ids ? n_ids : h->n_reads;
-    for (int64_t j = 0; ids && j < n_ids; ++j)
-        if (ids[j] < 0 || ids[j] >= h->n_reads) { *first_bad = j; return fail(FX_ERANGE, "read id %lld out of range", (long long)ids[j]); }
-    KmerOut out;
-    if (n == 0) {
-        if ((rc = out.prepare(h, k, 1, false))) return rc;
-        *counts = out.take();
-        return FX_OK;
-    }
-    Staged st(h);
-    st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
-    const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
-    if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
-    if (start) {
-        unsigned long long *d_bad = nullptr, bad = ~0ull;
-        if ((rc = st.scratch<unsigned long long>(1, &d_bad))) return rc;
-        HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
-        FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)h->fq_rlen.p, d_ids, n, d_start, d_end, d_bad);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (bad != ~0ull) {
-            *first_bad = (int64_t)bad;
-            h->prof.drain();
-            return fail(FX_ERANGE, "the interval of query %lld lies outside its read", (long long)bad);
+    if ((rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead))) return rc;
+    KmerOut out(h);
+    if (n > 0) {
+        Staged st(h);
+        st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
+        const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
+        if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+        const FqView v = fq_view(h);
+        if (start) {
+            BadFlag bad;
+            if ((rc = bad.arm(h, st))) return rc;
+            FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, d_ids, n, d_start, d_end, bad.d);
+            HIPCHK(hipGetLastError());
+            if ((rc = bad.read(h, first_bad))) return rc;
+            if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
         }
-    }
-    if ((rc = out.prepare(h, k, 1, true))) return rc;
-    const bool canon = flags & FX_KMER_CANONICAL, lds = k <= KMER_LDS_K;
-    if (canon) { if (lds) kmer_fastq_launch<true, true>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); else kmer_fastq_launch<true, false>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); }
-    else       { if (lds) kmer_fastq_launch<false, true>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); else kmer_fastq_launch<false, false>(h, q.lpr, d_ids, n, d_start, d_end, k, out.dev.p); }
-    if ((rc = out.home(h))) return rc;
-    *counts = out.take();
+        if ((rc = out.prepare(h, k, 1, true))) return rc;
+        // queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
+        const int64_t per = std::max<int64_t>(KMER_MAX_WINDOWS / std::max<int64_t>((int64_t)h->fq_maxlen, 1), 1);
+        with_bool(flags & FX_KMER_CANONICAL, [&](auto C) {
+            with_bool(k <= KMER_LDS_K, [&](auto L) {
+                for (int64_t q0 = 0; q0 < n; q0 += per) {
+                    const int64_t q1 = std::min(q0 + per, n);
+                    FX_LAUNCH(h, K_KMER_FASTQ, (k_kmer_fastq<C(), L()>), dim3(lane_group_grid<k_kmer_fastq<C(), L()>>(h, q1 - q0, q.lpr)), dim3(BLOCK), v.data,
+                              v.base, v.n, v.rlen, v.soff, d_ids, q0, q1, d_start, d_end, q.lpr, k, out.dev.p);
+                }
+            });
+        });
+        if ((rc = out.home(h))) return rc;
+    } else if ((rc = out.prepare(h, k, 1, false))) return rc;
+    out.pin.release(counts);
     return FX_OK;
 }
 
