@@ -932,6 +932,15 @@ static int to_host_any(fx_handle *h, void *dst, const void *d_src, int64_t bytes
 
 static inline unsigned nblocks(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
 
+// off[0..n] = exclusive prefix sums of the 32-bit counts cnt[0..n) (fx_comp.hpp), n > 0; sums: ceil(n / SCAN_CHUNK) + 1 words of
+// scratch.  Three untimed launches; the caller checks hipGetLastError where it did before.
+static void cnt_scan(hipStream_t s, const int32_t *cnt, int64_t n, int64_t *sums, int64_t *off) {
+    const int64_t nchunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, s, cnt, n, sums);
+    hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, s, sums, nchunks);
+    hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, s, cnt, n, (const int64_t *)sums, off);
+}
+
 // ------------------------------------------------------------------- BGZF
 // Member walk (SAM spec 4.1): gzip header with FEXTRA and a 'B','C' subfield whose
 // value is BSIZE = total member size - 1; trailer = CRC32, ISIZE.
@@ -1350,9 +1359,7 @@ static int bgzf_open_pipelined(fx_handle *h, int fd, int64_t fsize, const char *
         if ((rc = d_i64.alloc(h->device, ng + 1 + nchunks + 1, h->stream)) || (rc = d_cnt.alloc(h->device, ng, h->stream))) return give_up(rc);
         int64_t *d_off = d_i64.p, *d_sums = d_i64.p + ng + 1;
         hipLaunchKernelGGL(k_bgzf_sig_count, dim3(nblocks(ng, BLOCK / 64)), dim3(BLOCK), 0, h->stream, (const uint8_t *)d_c.p, fsize, ga, ng, d_cnt.p);
-        hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_cnt.p, ng, d_sums);
-        hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, d_sums, nchunks);
-        hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_cnt.p, ng, (const int64_t *)d_sums, d_off);
+        cnt_scan(h->stream, d_cnt.p, ng, d_sums, d_off);
         int64_t found = 0;
         if (hipMemcpyAsync(&found, d_off + ng, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
             return give_up(fail(FX_EDEVICE, "BGZF member search failed on the device"));
@@ -1382,9 +1389,7 @@ static int bgzf_open_pipelined(fx_handle *h, int fd, int64_t fsize, const char *
         }
         hipLaunchKernelGGL(k_bgzf_member_rows, dim3(nblocks(nmem, BLOCK)), dim3(BLOCK), 0, h->stream, (const uint8_t *)d_c.p, fsize, (const int64_t *)d_mstart, nmem,
                            nstarts, first_start, d_coff, d_clen, d_isize, (int *)d_flags, d_flags + 1);
-        hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)mchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_isize, nmem, d_msums);
-        hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, d_msums, mchunks);
-        hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)mchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_isize, nmem, (const int64_t *)d_msums, d_uoff);
+        cnt_scan(h->stream, d_isize, nmem, d_msums, d_uoff);
         if (U) hipLaunchKernelGGL(k_add_base, dim3(nblocks(nmem + 1, BLOCK)), dim3(BLOCK), 0, h->stream, d_uoff, nmem + 1, U);
         int32_t flags[2] = {0, 0};
         int64_t u_end = 0;
@@ -1463,9 +1468,7 @@ static int bgzf_open_on_device(fx_handle *h, int fd, int64_t fsize, const char *
     if ((rc = d_i64.alloc(h->device, ngran + 1 + nchunks + 1, h->stream)) || (rc = d_cnt.alloc(h->device, ngran, h->stream))) return rc;
     int64_t *d_off = d_i64.p, *d_sums = d_i64.p + ngran + 1;
     hipLaunchKernelGGL(k_bgzf_sig_count, dim3(nblocks(ngran, BLOCK / 64)), dim3(BLOCK), 0, h->stream, (const uint8_t *)d_c.p, fsize, (int64_t)0, ngran, d_cnt.p);
-    hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_cnt.p, ngran, d_sums);
-    hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, d_sums, nchunks);
-    hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_cnt.p, ngran, (const int64_t *)d_sums, d_off);
+    cnt_scan(h->stream, d_cnt.p, ngran, d_sums, d_off);
     int64_t nmem = 0;
     HIPCHK(hipMemcpyAsync(&nmem, d_off + ngran, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1481,9 +1484,7 @@ static int bgzf_open_on_device(fx_handle *h, int fd, int64_t fsize, const char *
     hipLaunchKernelGGL(k_bgzf_sig_emit, dim3(nblocks(ngran, BLOCK / 64)), dim3(BLOCK), 0, h->stream, (const uint8_t *)d_c.p, fsize, (int64_t)0, ngran, (const int64_t *)d_off, d_mstart);
     hipLaunchKernelGGL(k_bgzf_member_rows, dim3(nblocks(nmem, BLOCK)), dim3(BLOCK), 0, h->stream, (const uint8_t *)d_c.p, fsize, (const int64_t *)d_mstart, nmem,
                        nmem, (int64_t)0, d_coff, d_clen, d_isize, (int *)d_flags, d_flags + 1);
-    hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)mchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_isize, nmem, d_msums);
-    hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, d_msums, mchunks);
-    hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)mchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_isize, nmem, (const int64_t *)d_msums, d_uoff);
+    cnt_scan(h->stream, d_isize, nmem, d_msums, d_uoff);
     HIPCHK(hipGetLastError());
     int32_t flags[2] = {0, 0};
     int64_t total = 0;
@@ -2410,9 +2411,7 @@ extern "C" int fx_fasta_comp_sparse(fx_handle *h, int where, int64_t cap, int64_
     if (n) {
         const unsigned nb = (unsigned)std::min<int64_t>(nblocks(n, BLOCK / 64), 2048);
         hipLaunchKernelGGL(k_comp_count, dim3(nb), dim3(BLOCK), 0, h->stream, dense.p, n, cnt.p, tot.p);
-        hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, cnt.p, n, sums.p);
-        hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, sums.p, nchunks);
-        hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, cnt.p, n, sums.p, off.p);
+        cnt_scan(h->stream, cnt.p, n, sums.p, off.p);
         HIPCHK(hipGetLastError());
     }
     int64_t count = 0;
@@ -2793,15 +2792,8 @@ extern "C" int fx_kseq_scan(fx_handle *h, int64_t *n_records, int64_t *n_lines, 
             return rc;
         HIPCHK(hipMemsetAsync(ctl.p, 0, 16 * sizeof(unsigned long long), h->stream));
         const unsigned wide = (unsigned)std::min<int64_t>(nblocks(ntiles, BLOCK / 64), 256 * 8);
-        // exclusive prefix sums of a column of counts (fx_comp.hpp: three small kernels)
-        auto scan = [&](const int32_t *c, int64_t m, int64_t *sums_p, int64_t *o) {
-            const int64_t nch = (m + SCAN_CHUNK - 1) / SCAN_CHUNK;
-            hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nch), dim3(BLOCK), 0, h->stream, c, m, sums_p);
-            hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, sums_p, nch);
-            hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nch), dim3(BLOCK), 0, h->stream, c, m, sums_p, o);
-        };
         FX_LAUNCH(h, K_KQ_LINES, k_kq_count, dim3(wide), dim3(BLOCK), h->d_data, n, ntiles, cnt.p, ctl.p);
-        scan(cnt.p, ntiles, sums.p, off.p);
+        cnt_scan(h->stream, cnt.p, ntiles, sums.p, off.p);
         HIPCHK(hipGetLastError());
         int64_t n_nl = 0;
         unsigned long long hdrchars = 0;
@@ -2845,7 +2837,7 @@ extern "C" int fx_kseq_scan(fx_handle *h, int64_t *n_records, int64_t *n_lines, 
                 const unsigned g = (unsigned)std::min<int64_t>(nblocks(R, BLOCK), 256 * 16);
                 h->prof.begin(K_KQ_PREFIX, h->stream);
                 hipLaunchKernelGGL(k_kq_fq_cnt, dim3(g), dim3(BLOCK), 0, h->stream, desc.p, R, c.p);
-                scan(c.p, R, sm.p, o.p);
+                cnt_scan(h->stream, c.p, R, sm.p, o.p);
                 hipLaunchKernelGGL(k_kq_fq_emit, dim3(g), dim3(BLOCK), 0, h->stream, desc.p, R, o.p, h->kq_recs.p, h->kq_ldst.p, h->kq_lcon.p, init);
                 h->prof.end(h->stream);
                 HIPCHK(hipGetLastError());
@@ -2860,8 +2852,8 @@ extern "C" int fx_kseq_scan(fx_handle *h, int64_t *n_records, int64_t *n_lines, 
                 const unsigned g = (unsigned)std::min<int64_t>(nblocks(na, BLOCK), 256 * 16);
                 h->prof.begin(K_KQ_PREFIX, h->stream);
                 hipLaunchKernelGGL(k_kq_fa_cnt, dim3(g), dim3(BLOCK), 0, h->stream, desc.p, na, hf.p, cn.p);
-                scan(hf.p, na, sm.p, ho.p);
-                scan(cn.p, na, sm.p, co.p);
+                cnt_scan(h->stream, hf.p, na, sm.p, ho.p);
+                cnt_scan(h->stream, cn.p, na, sm.p, co.p);
                 h->prof.end(h->stream);
                 HIPCHK(hipGetLastError());
                 int64_t nh = 0;
@@ -3333,127 +3325,9 @@ extern "C" int fx_fasta_fetch(fx_handle *h, int where, int64_t n, const int64_t 
     return fetch_common(h, where, n, true, seq_id, start, stop, nullptr, flags, flags_per_query, dst, dst_off, out_len, ext);
 }
 
-// ---- batches whose answers the library lays out itself (fx_*_fetch_alloc)
-// Host-side phases of the last fx_*_fetch_alloc call of this thread, in milliseconds: 0 query arrays staged and their
-// copies enqueued, 1 counts + scan + offsets back (first wait), 2 pinned blocks for the answers, 3 kernels enqueued,
-// 4 answers back (second wait), 5 the whole call
-static thread_local double g_fetch_phase[6] = {0, 0, 0, 0, 0, 0};
-extern "C" int fx_fetch_phases(double *ms, int cap) {
-    if (!ms || cap <= 0) return fail(FX_EINVAL, "null argument");
-    for (int i = 0; i < cap && i < 6; ++i) ms[i] = g_fetch_phase[i];
-    return FX_OK;
-}
-struct PhaseClock {
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
-    void lap(int i) { const auto now = std::chrono::steady_clock::now(); g_fetch_phase[i] = std::chrono::duration<double, std::milli>(now - last).count(); last = now; }
-    void done() { g_fetch_phase[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
-
-// cnt[i] = bytes query i will write (0 for a query that is not valid; *bad = index of the first such query)
-__global__ __launch_bounds__(BLOCK) void k_q_counts_fasta(const int64_t *__restrict__ slen, int64_t n_seq, const int64_t *__restrict__ id,
-                                                         const int64_t *__restrict__ a, const int64_t *__restrict__ b, int64_t n,
-                                                         int32_t *__restrict__ cnt, unsigned long long *__restrict__ bad) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int64_t r = id[i], x = a[i], y = b[i];
-    const bool ok = r >= 0 && r < n_seq && x >= 0 && y >= x && y - x <= 0x7FFFFFFFll && y <= slen[r];
-    cnt[i] = ok ? (int32_t)(y - x) : 0;
-    if (!ok) atomicMin(bad, (unsigned long long)i);
-}
-__global__ __launch_bounds__(BLOCK) void k_q_counts_fastq(const int64_t *__restrict__ rlen, int64_t n_reads, const int64_t *__restrict__ id, int64_t n,
-                                                         int32_t *__restrict__ cnt, unsigned long long *__restrict__ bad) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int64_t r = id[i];
-    const bool ok = r >= 0 && r < n_reads && rlen[r] >= 0 && rlen[r] <= 0x7FFFFFFFll;
-    cnt[i] = ok ? (int32_t)rlen[r] : 0;
-    if (!ok) atomicMin(bad, (unsigned long long)i);
-}
-
-// cnt[0..n) on the device -> exclusive offsets d_off[0..n] on the device, and in *offs_out a pinned host copy (fx_pinned_free)
-// with the index of the first invalid query in *first_bad (-1: none); one wait
-static int offsets_of_counts(fx_handle *h, Staged &st, const int32_t *d_cnt, unsigned long long *d_bad, int64_t n, int64_t **d_off_out,
-                             int64_t **offs_out, int64_t *first_bad) {
-    int rc;
-    const int64_t nchunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    int64_t *d_sums = nullptr, *d_off = nullptr;
-    if ((rc = st.scratch<int64_t>(nchunks + 1, &d_sums)) || (rc = st.scratch<int64_t>(n + 1, &d_off))) return rc;
-    hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, d_cnt, n, d_sums);
-    hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, d_sums, nchunks);
-    hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, d_cnt, n, (const int64_t *)d_sums, d_off);
-    HIPCHK(hipGetLastError());
-    int64_t *offs = (int64_t *)fx_pinned_alloc((n + 2) * 8);            // one more word: the first invalid query
-    if (!offs) return FX_ENOMEM;
-    hipError_t e = hipMemcpyAsync(offs, d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(offs + n + 1, d_bad, 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { fx_pinned_free(offs); return fail(FX_EDEVICE, "offsets of a batch: %s", hipGetErrorString(e)); }
-    const unsigned long long bad = (unsigned long long)offs[n + 1];
-    *first_bad = bad == ~0ull ? -1 : (int64_t)bad;
-    *d_off_out = d_off;
-    *offs_out = offs;
-    return FX_OK;
-}
-
-extern "C" int fx_fasta_fetch_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop, int flags,
-                                    const uint8_t *flags_per_query, uint8_t **dst, int64_t **dst_off, int64_t *first_bad) {
-    if (!h || !dst || !dst_off || !first_bad) return fail(FX_EINVAL, "null argument");
-    *dst = nullptr; *dst_off = nullptr; *first_bad = -1;
-    if (n < 0 || (n > 0 && (!seq_id || !start || !stop))) return fail(FX_EINVAL, "null query array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (rc) return rc;
-    if (n >= 0x7FFFFFFFll * (int64_t)SCAN_CHUNK) return fail(FX_ERANGE, "too many queries in one batch");
-    Staged st(h);
-    PhaseClock pc;
-    FetchQ q;
-    memset(&q, 0, sizeof q);
-    int64_t *offs = nullptr;
-    if (n == 0) {
-        if (!(offs = (int64_t *)fx_pinned_alloc(16)) || !(*dst = (uint8_t *)fx_pinned_alloc(1))) { fx_pinned_free(offs); return FX_ENOMEM; }
-        offs[0] = 0; *dst_off = offs;
-        return FX_OK;
-    }
-    st.reserve_pin(n * 8 * 3 + (flags_per_query ? n : 0) + 5 * 256);
-    if ((rc = st.up(h, seq_id, n, &q.seq_id)) || (rc = st.up(h, start, n, &q.start)) || (rc = st.up(h, stop, n, &q.stop)) ||
-        (rc = st.up(h, flags_per_query, n, &q.qflags)))
-        return rc;
-    int32_t *d_cnt = nullptr;
-    unsigned long long *d_bad = nullptr;
-    if ((rc = st.scratch<int32_t>(n, &d_cnt)) || (rc = st.scratch<unsigned long long>(1, &d_bad))) return rc;
-    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
-    hipLaunchKernelGGL(k_q_counts_fasta, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const int64_t *)h->fa_slen.p, h->n_hdr, q.seq_id, q.start,
-                       q.stop, n, d_cnt, d_bad);
-    pc.lap(0);
-    int64_t *d_off = nullptr;
-    if ((rc = offsets_of_counts(h, st, d_cnt, d_bad, n, &d_off, &offs, first_bad))) return rc;
-    pc.lap(1);
-    if (*first_bad >= 0) { fx_pinned_free(offs); return fail(FX_ERANGE, "query %lld: record id or interval outside the sequence", (long long)*first_bad); }
-    const int64_t total = offs[n];
-    uint8_t *out = (uint8_t *)fx_pinned_alloc(std::max<int64_t>(total, 1));
-    uint8_t *d_dst = nullptr;
-    if (!out) { fx_pinned_free(offs); return FX_ENOMEM; }
-    // (a copy into these blocks may still be in flight when something fails: the stream is waited for before they go back to the pool)
-    auto bail = [&](int code) { (void)hipStreamSynchronize(h->stream); fx_pinned_free(offs); fx_pinned_free(out); return code; };
-    if ((rc = st.scratch<uint8_t>(std::max<int64_t>(total, 1), &d_dst))) return bail(rc);
-    pc.lap(2);
-    q.dst_off = d_off;
-    if (total > 0) {
-        if ((rc = fetch_launch(h, st, q, true, (flags & 16) != 0 || total / n > 512, n, flags, d_dst))) return bail(rc);
-        if (hipMemcpyAsync(out, d_dst, (size_t)total, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return bail(fail(FX_EDEVICE, "D2H failed"));
-    }
-    pc.lap(3);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(FX_EDEVICE, "stream synchronisation failed"));
-    pc.lap(4);
-    h->prof.drain();
-    *dst = out; *dst_off = offs;
-    pc.done();
-    return FX_OK;
-}
-
 // ------------------------------------------------------------------ what the entries on the resident stream are built from
-// (search, FASTQ quality control, trimming and records, k-mer spectra: each is a kernel header plus an entry made of these)
+// (the fetch batches below; search, FASTQ quality control, trimming and records, k-mer spectra: each of those is a kernel header
+// plus an entry made of these)
 
 // One call per value of a template parameter: the launch is written once, in a generic lambda that takes the constant.
 template <class F> static void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
@@ -3588,6 +3462,260 @@ static int fasta_run_plan(fx_handle *h, Staged &st, int id, const int64_t *ids, 
     return FX_OK;
 }
 
+// ------------------------------------------------------------------- fetch: batches whose answers the library lays out itself
+// (fx_*_fetch_alloc), the reads of a FASTQ table (fx_fastq_fetch, fx_read_fetch)
+// Host-side phases of the last fx_*_fetch_alloc call of this thread, in milliseconds: 0 query arrays staged and their
+// copies enqueued, 1 counts + scan + offsets back (first wait), 2 pinned blocks for the answers, 3 kernels enqueued,
+// 4 answers back (second wait), 5 the whole call
+static thread_local double g_fetch_phase[6] = {0, 0, 0, 0, 0, 0};
+extern "C" int fx_fetch_phases(double *ms, int cap) {
+    if (!ms || cap <= 0) return fail(FX_EINVAL, "null argument");
+    for (int i = 0; i < cap && i < 6; ++i) ms[i] = g_fetch_phase[i];
+    return FX_OK;
+}
+struct PhaseClock {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
+    void lap(int i) { const auto now = std::chrono::steady_clock::now(); g_fetch_phase[i] = std::chrono::duration<double, std::milli>(now - last).count(); last = now; }
+    void done() { g_fetch_phase[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// cnt[i] = bytes query i will write (0 for a query that is not valid; *bad = index of the first such query)
+__global__ __launch_bounds__(BLOCK) void k_q_counts_fasta(const int64_t *__restrict__ slen, int64_t n_seq, const int64_t *__restrict__ id,
+                                                         const int64_t *__restrict__ a, const int64_t *__restrict__ b, int64_t n,
+                                                         int32_t *__restrict__ cnt, unsigned long long *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int64_t r = id[i], x = a[i], y = b[i];
+    const bool ok = r >= 0 && r < n_seq && x >= 0 && y >= x && y - x <= 0x7FFFFFFFll && y <= slen[r];
+    cnt[i] = ok ? (int32_t)(y - x) : 0;
+    if (!ok) atomicMin(bad, (unsigned long long)i);
+}
+__global__ __launch_bounds__(BLOCK) void k_q_counts_fastq(const int64_t *__restrict__ rlen, int64_t n_reads, const int64_t *__restrict__ id, int64_t n,
+                                                         int32_t *__restrict__ cnt, unsigned long long *__restrict__ bad) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int64_t r = id[i];
+    const bool ok = r >= 0 && r < n_reads && rlen[r] >= 0 && rlen[r] <= 0x7FFFFFFFll;
+    cnt[i] = ok ? (int32_t)rlen[r] : 0;
+    if (!ok) atomicMin(bad, (unsigned long long)i);
+}
+
+// cnt[0..n) on the device -> exclusive offsets d_off[0..n] on the device, and in *offs_out a pinned host copy (fx_pinned_free)
+// with the index of the first invalid query in *first_bad (-1: none); one wait
+static int offsets_of_counts(fx_handle *h, Staged &st, const int32_t *d_cnt, unsigned long long *d_bad, int64_t n, int64_t **d_off_out,
+                             int64_t **offs_out, int64_t *first_bad) {
+    int rc;
+    const int64_t nchunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    int64_t *d_sums = nullptr, *d_off = nullptr;
+    if ((rc = st.scratch<int64_t>(nchunks + 1, &d_sums)) || (rc = st.scratch<int64_t>(n + 1, &d_off))) return rc;
+    cnt_scan(h->stream, d_cnt, n, d_sums, d_off);
+    HIPCHK(hipGetLastError());
+    int64_t *offs = (int64_t *)fx_pinned_alloc((n + 2) * 8);            // one more word: the first invalid query
+    if (!offs) return FX_ENOMEM;
+    hipError_t e = hipMemcpyAsync(offs, d_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(offs + n + 1, d_bad, 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { fx_pinned_free(offs); return fail(FX_EDEVICE, "offsets of a batch: %s", hipGetErrorString(e)); }
+    const unsigned long long bad = (unsigned long long)offs[n + 1];
+    *first_bad = bad == ~0ull ? -1 : (int64_t)bad;
+    *d_off_out = d_off;
+    *offs_out = offs;
+    return FX_OK;
+}
+
+extern "C" int fx_fasta_fetch_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop, int flags,
+                                    const uint8_t *flags_per_query, uint8_t **dst, int64_t **dst_off, int64_t *first_bad) {
+    if (!h || !dst || !dst_off || !first_bad) return fail(FX_EINVAL, "null argument");
+    *dst = nullptr; *dst_off = nullptr; *first_bad = -1;
+    if (n < 0 || (n > 0 && (!seq_id || !start || !stop))) return fail(FX_EINVAL, "null query array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    int rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (rc) return rc;
+    if (n >= 0x7FFFFFFFll * (int64_t)SCAN_CHUNK) return fail(FX_ERANGE, "too many queries in one batch");
+    Staged st(h);
+    PhaseClock pc;
+    FetchQ q;
+    memset(&q, 0, sizeof q);
+    PinnedOut<2> out(h);                                   // the offsets, the bytes
+    if (n == 0) {
+        if (!out.alloc(0, 16) || !out.alloc(1, 1)) return FX_ENOMEM;
+        out.as<int64_t>(0)[0] = 0;
+        out.release(dst_off, dst);
+        return FX_OK;
+    }
+    st.reserve_pin(n * 8 * 3 + (flags_per_query ? n : 0) + 5 * 256);
+    if ((rc = st.up(h, seq_id, n, &q.seq_id)) || (rc = st.up(h, start, n, &q.start)) || (rc = st.up(h, stop, n, &q.stop)) ||
+        (rc = st.up(h, flags_per_query, n, &q.qflags)))
+        return rc;
+    int32_t *d_cnt = nullptr;
+    BadFlag bad;
+    if ((rc = st.scratch<int32_t>(n, &d_cnt)) || (rc = bad.arm(h, st))) return rc;
+    hipLaunchKernelGGL(k_q_counts_fasta, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const int64_t *)h->fa_slen.p, h->n_hdr, q.seq_id, q.start,
+                       q.stop, n, d_cnt, bad.d);
+    pc.lap(0);
+    int64_t *d_off = nullptr, *offs = nullptr;
+    if ((rc = offsets_of_counts(h, st, d_cnt, bad.d, n, &d_off, &offs, first_bad))) return rc;
+    out.p[0] = offs;
+    pc.lap(1);
+    if (*first_bad >= 0) return fail(FX_ERANGE, "query %lld: record id or interval outside the sequence", (long long)*first_bad);
+    const int64_t total = offs[n];
+    uint8_t *d_dst = nullptr;
+    if (!out.alloc(1, std::max<int64_t>(total, 1))) return FX_ENOMEM;
+    if ((rc = st.scratch<uint8_t>(std::max<int64_t>(total, 1), &d_dst))) return rc;
+    pc.lap(2);
+    q.dst_off = d_off;
+    if (total > 0) {
+        if ((rc = fetch_launch(h, st, q, true, (flags & 16) != 0 || total / n > 512, n, flags, d_dst))) return rc;
+        if (hipMemcpyAsync(out.p[1], d_dst, (size_t)total, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return fail(FX_EDEVICE, "D2H failed");
+    }
+    pc.lap(3);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(FX_EDEVICE, "stream synchronisation failed");
+    pc.lap(4);
+    h->prof.drain();
+    out.release(dst_off, dst);
+    pc.done();
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_fetch_alloc(fx_handle *h, int64_t n, const int64_t *read_id, int phred, int seq_flags, int want, uint8_t **seq,
+                                    uint8_t **qual, int8_t **quali, int64_t **dst_off, int64_t *first_bad) {
+    if (!h || !dst_off || !first_bad) return fail(FX_EINVAL, "null argument");
+    if (seq) *seq = nullptr; if (qual) *qual = nullptr; if (quali) *quali = nullptr;
+    *dst_off = nullptr; *first_bad = -1;
+    if (!h->fastq_built) return fail(FX_ESTATE, "fx_fastq_build has not run");
+    if (n < 0 || (n > 0 && !read_id)) return fail(FX_EINVAL, "null query array");
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!phred) phred = 33;                                // read.c:268
+    const bool w_seq = (want & 1) && seq, w_qual = (want & 2) && qual, w_qi = (want & 4) && quali;
+    Staged st(h);
+    PhaseClock pc;
+    PinnedOut<4> out(h);                                   // seq, qual, quali, the offsets
+    if (n == 0) {
+        if (!out.alloc(3, 16)) return FX_ENOMEM;
+        out.as<int64_t>(3)[0] = 0;
+    } else {
+        st.reserve_pin(n * 8 + 512);
+        const int64_t *d_ids = nullptr;
+        if ((rc = st.up(h, read_id, n, &d_ids))) return rc;
+        int32_t *d_cnt = nullptr;
+        BadFlag bad;
+        if ((rc = st.scratch<int32_t>(n, &d_cnt)) || (rc = bad.arm(h, st))) return rc;
+        hipLaunchKernelGGL(k_q_counts_fastq, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const int64_t *)h->fq_rlen.p, h->n_reads, d_ids, n, d_cnt, bad.d);
+        pc.lap(0);
+        int64_t *d_off = nullptr, *offs = nullptr;
+        if ((rc = offsets_of_counts(h, st, d_cnt, bad.d, n, &d_off, &offs, first_bad))) return rc;
+        out.p[3] = offs;
+        pc.lap(1);
+        if (*first_bad >= 0) return fail(FX_ERANGE, kBadRead, (long long)read_id[*first_bad]);
+        const int64_t total = std::max<int64_t>(offs[n], 1);
+        uint8_t *d_out[3] = {nullptr, nullptr, nullptr};
+        const bool w[3] = {w_seq, w_qual, w_qi};
+        for (int k = 0; k < 3; ++k)
+            if (w[k]) {
+                if (!out.alloc(k, total)) return FX_ENOMEM;
+                if ((rc = st.scratch<uint8_t>(total, &d_out[k]))) return rc;
+            }
+        pc.lap(2);
+        FX_LAUNCH(h, K_FASTQ_FETCH, k_fastq_fetch, dim3(fetch_grid((n + 3) / 4)), dim3(BLOCK), h->d_data, h->base, h->n, h->fq_rlen.p,
+                  h->fq_soff.p, h->fq_qoff.p, h->n_reads, d_ids, n, phred, seq_flags, d_out[0], d_out[1], (int8_t *)d_out[2], (const int64_t *)d_off);
+        if (hipGetLastError() != hipSuccess) return fail(FX_EDEVICE, "launch failed");
+        for (int k = 0; k < 3; ++k)
+            if (w[k] && hipMemcpyAsync(out.p[k], d_out[k], (size_t)offs[n], hipMemcpyDeviceToHost, h->stream) != hipSuccess) return fail(FX_EDEVICE, "D2H failed");
+        pc.lap(3);
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(FX_EDEVICE, "stream synchronisation failed");
+        pc.lap(4);
+        h->prof.drain();
+    }
+    if (n == 0) for (int k = 0; k < 3; ++k) { const bool w[3] = {w_seq, w_qual, w_qi}; if (w[k] && !out.alloc(k, 1)) return FX_ENOMEM; }
+    out.release(seq, qual, quali, dst_off);
+    pc.done();
+    return FX_OK;
+}
+
+// What fx_fastq_fetch and fx_read_fetch end in.  The columns (rlen, soff, qoff: n_rows rows) and d_ids (null: row i is query i)
+// are on the device.  A host caller's dst_off goes up and its destinations -- those it gave, `total` bytes each -- come out of
+// the arena; then the one launch, the answers home, one wait.
+static int reads_out(fx_handle *h, Staged &st, int where, int64_t n, const int64_t *rlen, const int64_t *soff, const int64_t *qoff, int64_t n_rows,
+                     const int64_t *d_ids, int phred, int seq_flags, int64_t total, uint8_t *seq, uint8_t *qual, int8_t *quali, const int64_t *dst_off) {
+    int rc;
+    const int64_t *d_off = dst_off;
+    uint8_t *d_seq = seq, *d_qual = qual;
+    int8_t *d_qi = quali;
+    if (where == FX_HOST) {
+        total = std::max<int64_t>(total, 1);
+        if ((rc = st.up(h, dst_off, n, &d_off))) return rc;
+        if (seq && (rc = st.scratch<uint8_t>(total, &d_seq))) return rc;
+        if (qual && (rc = st.scratch<uint8_t>(total, &d_qual))) return rc;
+        if (quali && (rc = st.scratch<int8_t>(total, &d_qi))) return rc;
+    }
+    FX_LAUNCH(h, K_FASTQ_FETCH, k_fastq_fetch, dim3(fetch_grid((n + 3) / 4)), dim3(BLOCK), h->d_data, h->base, h->n, rlen, soff, qoff, n_rows, d_ids, n,
+              phred, seq_flags, d_seq, d_qual, d_qi, d_off);
+    HIPCHK(hipGetLastError());
+    if (where == FX_HOST) {
+        if (seq) HIPCHK(hipMemcpyAsync(seq, d_seq, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+        if (qual) HIPCHK(hipMemcpyAsync(qual, d_qual, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+        if (quali) HIPCHK(hipMemcpyAsync(quali, d_qi, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_fetch(fx_handle *h, int where, int64_t n, const int64_t *read_id, int phred, int seq_flags,
+                              uint8_t *seq, uint8_t *qual, int8_t *quali, const int64_t *dst_off) {
+    if (!h) return fail(FX_EINVAL, "null handle");
+    if (!h->fastq_built) return fail(FX_ESTATE, "fx_fastq_build has not run");
+    if (n < 0 || (n > 0 && (!read_id || !dst_off))) return fail(FX_EINVAL, "null query array");
+    if (n == 0) return FX_OK;
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!phred) phred = 33;                                // read.c:268
+    Staged st(h);
+    const int64_t *d_ids = read_id;
+    int64_t total = 0;
+    std::vector<int64_t> rl;
+    if (where == FX_HOST) {
+        // output extent needs rlen of the requested reads: gather them on the device (n values, not the whole column)
+        if ((rc = st.up(h, read_id, n, &d_ids))) return rc;
+        int64_t *d_rl = nullptr;
+        if ((rc = st.scratch<int64_t>(n, &d_rl))) return rc;
+        hipLaunchKernelGGL(k_gather_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->fq_rlen.p, h->n_reads, d_ids, n, d_rl);
+        rl.resize((size_t)n);
+        HIPCHK(hipMemcpyAsync(rl.data(), d_rl, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; i < n; ++i) {
+            if (rl[(size_t)i] < 0) return fail(FX_ERANGE, kBadRead, (long long)read_id[i]);
+            total = std::max(total, dst_off[i] + rl[(size_t)i]);
+        }
+    }
+    return reads_out(h, st, where, n, h->fq_rlen.p, h->fq_soff.p, h->fq_qoff.p, h->n_reads, d_ids, phred, seq_flags, total, seq, qual, quali, dst_off);
+}
+
+extern "C" int fx_read_fetch(fx_handle *h, int where, int64_t n, const int64_t *soff, const int64_t *qoff,
+                             const int64_t *rlen, int phred, int seq_flags, uint8_t *seq, uint8_t *qual, int8_t *quali,
+                             const int64_t *dst_off) {
+    if (!h) return fail(FX_EINVAL, "null handle");
+    if (n < 0 || (n > 0 && (!soff || !qoff || !rlen || !dst_off))) return fail(FX_EINVAL, "null query array");
+    if (n == 0) return FX_OK;
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (!phred) phred = 33;                                // read.c:268
+    Staged st(h);
+    const int64_t *d_s = soff, *d_q = qoff, *d_r = rlen;
+    int64_t total = 0;
+    if (where == FX_HOST) {
+        for (int64_t i = 0; i < n; ++i) {
+            if (rlen[i] < 0 || soff[i] < h->base || qoff[i] < h->base || soff[i] + rlen[i] > h->base + h->n ||
+                qoff[i] + rlen[i] > h->base + h->n)
+                return fail(FX_ERANGE, "read %lld lies outside the stream", (long long)i);
+            total = std::max(total, dst_off[i] + rlen[i]);
+        }
+        if ((rc = st.up(h, soff, n, &d_s)) || (rc = st.up(h, qoff, n, &d_q)) || (rc = st.up(h, rlen, n, &d_r))) return rc;
+    }
+    return reads_out(h, st, where, n, d_r, d_s, d_q, n, nullptr, phred, seq_flags, total, seq, qual, quali, dst_off);
+}
+
 // ------------------------------------------------------------------ search (fx_search.hpp)
 // Shift-And masks of every byte value: bit j of .x (.y) is set when the byte matches letter j of the forward (reverse)
 // pattern.  Exact: byte equality with the byte as `seq` presents it (Py_TOUPPER first under FX_SEARCH_UPPER).  Degenerate:
@@ -3702,63 +3830,6 @@ extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *
         if ((rc = home(h, "search emit", {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], out8.p, total}}))) return rc;
     }
     out.release(rec, start, strand);
-    return FX_OK;
-}
-
-extern "C" int fx_fastq_fetch_alloc(fx_handle *h, int64_t n, const int64_t *read_id, int phred, int seq_flags, int want, uint8_t **seq,
-                                    uint8_t **qual, int8_t **quali, int64_t **dst_off, int64_t *first_bad) {
-    if (!h || !dst_off || !first_bad) return fail(FX_EINVAL, "null argument");
-    if (seq) *seq = nullptr; if (qual) *qual = nullptr; if (quali) *quali = nullptr;
-    *dst_off = nullptr; *first_bad = -1;
-    if (!h->fastq_built) return fail(FX_ESTATE, "fx_fastq_build has not run");
-    if (n < 0 || (n > 0 && !read_id)) return fail(FX_EINVAL, "null query array");
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!phred) phred = 33;                                // read.c:268
-    const bool w_seq = (want & 1) && seq, w_qual = (want & 2) && qual, w_qi = (want & 4) && quali;
-    Staged st(h);
-    PhaseClock pc;
-    PinnedOut<4> out(h);                                   // seq, qual, quali, the offsets
-    if (n == 0) {
-        if (!out.alloc(3, 16)) return FX_ENOMEM;
-        out.as<int64_t>(3)[0] = 0;
-    } else {
-        st.reserve_pin(n * 8 + 512);
-        const int64_t *d_ids = nullptr;
-        if ((rc = st.up(h, read_id, n, &d_ids))) return rc;
-        int32_t *d_cnt = nullptr;
-        unsigned long long *d_bad = nullptr;
-        if ((rc = st.scratch<int32_t>(n, &d_cnt)) || (rc = st.scratch<unsigned long long>(1, &d_bad))) return rc;
-        HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
-        hipLaunchKernelGGL(k_q_counts_fastq, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const int64_t *)h->fq_rlen.p, h->n_reads, d_ids, n, d_cnt, d_bad);
-        pc.lap(0);
-        int64_t *d_off = nullptr, *offs = nullptr;
-        if ((rc = offsets_of_counts(h, st, d_cnt, d_bad, n, &d_off, &offs, first_bad))) return rc;
-        out.p[3] = offs;
-        pc.lap(1);
-        if (*first_bad >= 0) return fail(FX_ERANGE, kBadRead, (long long)read_id[*first_bad]);
-        const int64_t total = std::max<int64_t>(offs[n], 1);
-        uint8_t *d_out[3] = {nullptr, nullptr, nullptr};
-        const bool w[3] = {w_seq, w_qual, w_qi};
-        for (int k = 0; k < 3; ++k)
-            if (w[k]) {
-                if (!out.alloc(k, total)) return FX_ENOMEM;
-                if ((rc = st.scratch<uint8_t>(total, &d_out[k]))) return rc;
-            }
-        pc.lap(2);
-        FX_LAUNCH(h, K_FASTQ_FETCH, k_fastq_fetch, dim3(fetch_grid((n + 3) / 4)), dim3(BLOCK), h->d_data, h->base, h->n, h->fq_rlen.p,
-                  h->fq_soff.p, h->fq_qoff.p, h->n_reads, d_ids, n, phred, seq_flags, d_out[0], d_out[1], (int8_t *)d_out[2], (const int64_t *)d_off);
-        if (hipGetLastError() != hipSuccess) return fail(FX_EDEVICE, "launch failed");
-        for (int k = 0; k < 3; ++k)
-            if (w[k] && hipMemcpyAsync(out.p[k], d_out[k], (size_t)offs[n], hipMemcpyDeviceToHost, h->stream) != hipSuccess) return fail(FX_EDEVICE, "D2H failed");
-        pc.lap(3);
-        if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(FX_EDEVICE, "stream synchronisation failed");
-        pc.lap(4);
-        h->prof.drain();
-    }
-    if (n == 0) for (int k = 0; k < 3; ++k) { const bool w[3] = {w_seq, w_qual, w_qi}; if (w[k] && !out.alloc(k, 1)) return FX_ENOMEM; }
-    out.release(seq, qual, quali, dst_off);
-    pc.done();
     return FX_OK;
 }
 
@@ -4127,105 +4198,39 @@ extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t 
     return FX_OK;
 }
 
-extern "C" int fx_fastq_fetch(fx_handle *h, int where, int64_t n, const int64_t *read_id, int phred, int seq_flags,
-                              uint8_t *seq, uint8_t *qual, int8_t *quali, const int64_t *dst_off) {
-    if (!h) return fail(FX_EINVAL, "null handle");
-    if (!h->fastq_built) return fail(FX_ESTATE, "fx_fastq_build has not run");
-    if (n < 0 || (n > 0 && (!read_id || !dst_off))) return fail(FX_EINVAL, "null query array");
-    if (n == 0) return FX_OK;
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!phred) phred = 33;                                // read.c:268
-    Staged st(h);
-    const int64_t *d_ids = read_id, *d_off = dst_off;
-    uint8_t *d_seq = seq, *d_qual = qual;
-    int8_t *d_qi = quali;
-    int64_t total = 0;
-    std::vector<int64_t> rl;
-    if (where == FX_HOST) {
-        // output extent needs rlen of the requested reads: gather them on the device (n values, not the whole column)
-        if ((rc = st.up(h, read_id, n, &d_ids))) return rc;
-        int64_t *d_rl = nullptr;
-        if ((rc = st.scratch<int64_t>(n, &d_rl))) return rc;
-        hipLaunchKernelGGL(k_gather_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->fq_rlen.p, h->n_reads, d_ids, n, d_rl);
-        rl.resize((size_t)n);
-        HIPCHK(hipMemcpyAsync(rl.data(), d_rl, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (int64_t i = 0; i < n; ++i) {
-            if (rl[(size_t)i] < 0) return fail(FX_ERANGE, "read id %lld out of range", (long long)read_id[i]);
-            total = std::max(total, dst_off[i] + rl[(size_t)i]);
-        }
-        total = std::max<int64_t>(total, 1);
-        if ((rc = st.up(h, dst_off, n, &d_off))) return rc;
-        if (seq && (rc = st.scratch<uint8_t>(total, &d_seq))) return rc;
-        if (qual && (rc = st.scratch<uint8_t>(total, &d_qual))) return rc;
-        if (quali && (rc = st.scratch<int8_t>(total, &d_qi))) return rc;
-    }
-    FX_LAUNCH(h, K_FASTQ_FETCH, k_fastq_fetch, dim3(fetch_grid((n + 3) / 4)), dim3(BLOCK), h->d_data, h->base, h->n, h->fq_rlen.p,
-                       h->fq_soff.p, h->fq_qoff.p, h->n_reads, d_ids, n, phred, seq_flags, d_seq, d_qual, d_qi, d_off);
-    HIPCHK(hipGetLastError());
-    if (where == FX_HOST) {
-        if (seq) HIPCHK(hipMemcpyAsync(seq, d_seq, (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        if (qual) HIPCHK(hipMemcpyAsync(qual, d_qual, (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        if (quali) HIPCHK(hipMemcpyAsync(quali, d_qi, (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return FX_OK;
-}
-
-extern "C" int fx_read_fetch(fx_handle *h, int where, int64_t n, const int64_t *soff, const int64_t *qoff,
-                             const int64_t *rlen, int phred, int seq_flags, uint8_t *seq, uint8_t *qual, int8_t *quali,
-                             const int64_t *dst_off) {
-    if (!h) return fail(FX_EINVAL, "null handle");
-    if (n < 0 || (n > 0 && (!soff || !qoff || !rlen || !dst_off))) return fail(FX_EINVAL, "null query array");
-    if (n == 0) return FX_OK;
-    int rc = use_device(h);
-    if (rc) return rc;
-    if (!phred) phred = 33;                                // read.c:268
-    Staged st(h);
-    const int64_t *d_s = soff, *d_q = qoff, *d_r = rlen, *d_off = dst_off;
-    uint8_t *d_seq = seq, *d_qual = qual;
-    int8_t *d_qi = quali;
-    int64_t total = 0;
-    if (where == FX_HOST) {
-        for (int64_t i = 0; i < n; ++i) {
-            if (rlen[i] < 0 || soff[i] < h->base || qoff[i] < h->base || soff[i] + rlen[i] > h->base + h->n ||
-                qoff[i] + rlen[i] > h->base + h->n)
-                return fail(FX_ERANGE, "read %lld lies outside the stream", (long long)i);
-            total = std::max(total, dst_off[i] + rlen[i]);
-        }
-        total = std::max<int64_t>(total, 1);
-        if ((rc = st.up(h, soff, n, &d_s)) || (rc = st.up(h, qoff, n, &d_q)) || (rc = st.up(h, rlen, n, &d_r)) ||
-            (rc = st.up(h, dst_off, n, &d_off)))
-            return rc;
-        if (seq && (rc = st.scratch<uint8_t>(total, &d_seq))) return rc;
-        if (qual && (rc = st.scratch<uint8_t>(total, &d_qual))) return rc;
-        if (quali && (rc = st.scratch<int8_t>(total, &d_qi))) return rc;
-    }
-    FX_LAUNCH(h, K_FASTQ_FETCH, k_fastq_fetch, dim3(fetch_grid((n + 3) / 4)), dim3(BLOCK), h->d_data, h->base, h->n, d_r, d_s, d_q, n,
-              (const int64_t *)nullptr, n, phred, seq_flags, d_seq, d_qual, d_qi, d_off);
-    HIPCHK(hipGetLastError());
-    if (where == FX_HOST) {
-        if (seq) HIPCHK(hipMemcpyAsync(seq, d_seq, (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        if (qual) HIPCHK(hipMemcpyAsync(qual, d_qual, (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        if (quali) HIPCHK(hipMemcpyAsync(quali, d_qi, (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-    }
-    return FX_OK;
-}
-
 // ------------------------------------------------------------- names
 __global__ void k_add_i64(const int64_t *__restrict__ a, int64_t add, int64_t n, int64_t *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = a[i] + add;
 }
 
-extern "C" int fx_names_build(fx_handle *h, int kind) {
+// What every entry on the names of a table (kind 0: FASTA records, 1: FASTQ reads) asks first; the table is finished after it.
+static int names_ready(fx_handle *h, int kind) {
     if (!h || (kind != 0 && kind != 1)) return fail(FX_EINVAL, "bad argument");
     if (kind == 0 ? !h->fasta_built : !h->fastq_built) return fail(FX_ESTATE, "the index has not been built");
     if (kind == 0 && !h->hdr.p) return fail(FX_ESTATE, "names need a scanned index (fx_fasta_build), not an installed table");
     int rc = use_device(h);
     if (!rc) rc = finish_build(h);
+    return rc;
+}
+// Where the names of that table begin and how long they are.  FASTA: one byte behind the header offsets, written to h->nm_off
+// on the handle's stream.
+static int name_cols(fx_handle *h, int kind, const int64_t **noff, const int32_t **nlen) {
+    *noff = h->fq_name_off.p; *nlen = h->fq_name_len.p;
+    if (kind != 0) return FX_OK;
+    int rc = h->nm_off.alloc(std::max<int64_t>(h->n_hdr, 1));
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_add_i64, dim3(nblocks(h->n_hdr, BLOCK)), dim3(BLOCK), 0, h->stream, h->hdr.p, (int64_t)1, h->n_hdr, h->nm_off.p);
+    *noff = h->nm_off.p; *nlen = h->fa_name_len.p;
+    return FX_OK;
+}
+// what sort_names and len_stats (fx_sort.hpp) report: a HIP error code and the step it came from
+static int sort_fail(const char *label, int e, const char *what) {
+    return fail(e == (int)hipErrorOutOfMemory ? FX_ENOMEM : FX_EDEVICE, "%s, %s: %s", label, what, hipGetErrorString((hipError_t)e));
+}
+
+extern "C" int fx_names_build(fx_handle *h, int kind) {
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     const int64_t n = kind == 0 ? h->n_hdr : h->n_reads;
     if (n >= 0xFFFFFFFFll) return fail(FX_ERANGE, "too many records for the 32-bit name table");
@@ -4233,13 +4238,9 @@ extern "C" int fx_names_build(fx_handle *h, int kind) {
     while (cap < 2 * n) cap <<= 1;
     if ((rc = h->nm_table.alloc(cap))) return rc;
     HIPCHK(hipMemsetAsync(h->nm_table.p, 0, (size_t)cap * 4, h->stream));
-    const int64_t *noff = h->fq_name_off.p;
-    const int32_t *nlen = h->fq_name_len.p;
-    if (kind == 0) {
-        if ((rc = h->nm_off.alloc(std::max<int64_t>(n, 1)))) return rc;
-        hipLaunchKernelGGL(k_add_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->hdr.p, (int64_t)1, n, h->nm_off.p);
-        noff = h->nm_off.p; nlen = h->fa_name_len.p;
-    }
+    const int64_t *noff;
+    const int32_t *nlen;
+    if ((rc = name_cols(h, kind, &noff, &nlen))) return rc;
     if (n) hipLaunchKernelGGL(k_names_build, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->d_data, h->base, noff, nlen, n,
                               h->nm_table.p, (uint64_t)(cap - 1));
     HIPCHK(hipGetLastError());
@@ -4284,32 +4285,23 @@ __global__ void k_len_clamp(const int32_t *__restrict__ len, int64_t n, int32_t 
 // The record names back to back, straight from the record table in HBM: no query arrays go up (fx_fetch_ranges with
 // host arrays uploads 32 bytes per name and walks them twice on the host: 130 ms for 20 M names, most of it not the names)
 extern "C" int fx_names_pack(fx_handle *h, int kind, uint8_t *dst, int64_t cap, int64_t *name_off, int64_t *total_out) {
-    if (!h || (kind != 0 && kind != 1) || !total_out || !name_off || cap < 0 || (cap > 0 && !dst)) return fail(FX_EINVAL, "bad argument");
-    if (kind == 0 ? !h->fasta_built : !h->fastq_built) return fail(FX_ESTATE, "the index has not been built");
-    if (kind == 0 && !h->hdr.p) return fail(FX_ESTATE, "names need a scanned index (fx_fasta_build), not an installed table");
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
+    if (!total_out || !name_off || cap < 0 || (cap > 0 && !dst)) return fail(FX_EINVAL, "bad argument");
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     const int64_t n = kind == 0 ? h->n_hdr : h->n_reads;
     name_off[0] = 0;
     *total_out = 0;
     if (n == 0) return FX_OK;
-    const int64_t *noff = h->fq_name_off.p;
-    const int32_t *nlen = h->fq_name_len.p;
-    if (kind == 0) {
-        if ((rc = h->nm_off.alloc(n))) return rc;
-        hipLaunchKernelGGL(k_add_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->hdr.p, (int64_t)1, n, h->nm_off.p);
-        noff = h->nm_off.p; nlen = h->fa_name_len.p;
-    }
+    const int64_t *noff;
+    const int32_t *nlen;
+    if ((rc = name_cols(h, kind, &noff, &nlen))) return rc;
     const int64_t nchunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     DevBuf<int32_t> l32;
     DevBuf<int64_t> l64, sums, off;
     DevBuf<uint8_t> out;
     if ((rc = l32.alloc(n)) || (rc = l64.alloc(n)) || (rc = sums.alloc(nchunks + 1)) || (rc = off.alloc(n + 1))) return rc;
     hipLaunchKernelGGL(k_len_clamp, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, nlen, n, l32.p, l64.p);
-    hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, l32.p, n, sums.p);
-    hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, sums.p, nchunks);
-    hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, l32.p, n, sums.p, off.p);
+    cnt_scan(h->stream, l32.p, n, sums.p, off.p);
     HIPCHK(hipGetLastError());
     int64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, off.p + n, 8, hipMemcpyDeviceToHost, h->stream));
@@ -4327,31 +4319,24 @@ extern "C" int fx_names_pack(fx_handle *h, int kind, uint8_t *dst, int64_t cap, 
 }
 
 extern "C" int fx_names_sort(fx_handle *h, int kind, int where, int64_t *order, int64_t *n_dup) {
-    if (!h || (kind != 0 && kind != 1) || !n_dup) return fail(FX_EINVAL, "bad argument");
-    if (kind == 0 ? !h->fasta_built : !h->fastq_built) return fail(FX_ESTATE, "the index has not been built");
-    if (kind == 0 && !h->hdr.p) return fail(FX_ESTATE, "names need a scanned index (fx_fasta_build), not an installed table");
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
+    if (!n_dup) return fail(FX_EINVAL, "bad argument");
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     const int64_t n = kind == 0 ? h->n_hdr : h->n_reads;
     *n_dup = 0;
     if (n == 0) return FX_OK;
     if (!order) return fail(FX_EINVAL, "null order");
     if (n >= 0xFFFFFFFFll) return fail(FX_ERANGE, "too many records for the 32-bit sort index");
-    const int64_t *noff = h->fq_name_off.p;
-    const int32_t *nlen = h->fq_name_len.p;
-    if (kind == 0) {
-        if ((rc = h->nm_off.alloc(n))) return rc;
-        hipLaunchKernelGGL(k_add_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->hdr.p, (int64_t)1, n, h->nm_off.p);
-        noff = h->nm_off.p; nlen = h->fa_name_len.p;
-    }
+    const int64_t *noff;
+    const int32_t *nlen;
+    if ((rc = name_cols(h, kind, &noff, &nlen))) return rc;
     Staged st(h);
     int64_t *d_order = order, *d_ndup = nullptr;
     if (where == FX_HOST && (rc = st.scratch<int64_t>(n, &d_order))) return rc;
     if ((rc = st.scratch<int64_t>(1, &d_ndup))) return rc;
     const char *what = "";
     const int e = sort_names(h->d_data, h->base, noff, nlen, n, d_order, d_ndup, h->stream, &what);
-    if (e) return fail(e == (int)hipErrorOutOfMemory ? FX_ENOMEM : FX_EDEVICE, "name sort, %s: %s", what, hipGetErrorString((hipError_t)e));
+    if (e) return sort_fail("name sort", e, what);
     HIPCHK(hipMemcpyAsync(n_dup, d_ndup, 8, hipMemcpyDeviceToHost, h->stream));
     if (where == FX_HOST && (rc = to_host(h, order, d_order, n * 8))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -4385,7 +4370,7 @@ extern "C" int fx_sort_packed_names(int device, const uint8_t *names, const int6
     if (e != hipSuccess) return done(fail(FX_EDEVICE, "H2D: %s", hipGetErrorString(e)));
     const char *what = "";
     const int se = sort_names(d_names.p, 0, d_off.p, d_len.p, n, d_order.p, d_ndup.p, h->stream, &what);
-    if (se) return done(fail(se == (int)hipErrorOutOfMemory ? FX_ENOMEM : FX_EDEVICE, "name sort, %s: %s", what, hipGetErrorString((hipError_t)se)));
+    if (se) return done(sort_fail("name sort", se, what));
     e = hipMemcpyAsync(n_dup, d_ndup.p, 8, hipMemcpyDeviceToHost, h->stream);
     if (e != hipSuccess) return done(fail(FX_EDEVICE, "D2H: %s", hipGetErrorString(e)));
     if ((rc = to_host(h, order, d_order.p, n * 8))) return done(rc);
@@ -4402,7 +4387,7 @@ extern "C" int fx_fasta_len_stats(fx_handle *h, int64_t count_min, double half, 
     if (rc) return rc;
     const char *what = "";
     const int e = len_stats(h->fa_slen.p, h->n_hdr, count_min, half, reinterpret_cast<LenStats *>(out), h->stream, &what);
-    if (e) return fail(e == (int)hipErrorOutOfMemory ? FX_ENOMEM : FX_EDEVICE, "length statistics, %s: %s", what, hipGetErrorString((hipError_t)e));
+    if (e) return sort_fail("length statistics", e, what);
     return FX_OK;
 }
 
@@ -4747,15 +4732,6 @@ static int64_t fxi_slab_pages() {                          // pages formatted pe
     return ((mb > 0 ? mb : 4096) << 20) / FXI_PAGE;
 }
 
-static int fxi_check_kind(fx_handle *h, int kind) {
-    if (!h || (kind != 0 && kind != 1)) return fail(FX_EINVAL, "bad argument");
-    if (kind == 0 ? !h->fasta_built : !h->fastq_built) return fail(FX_ESTATE, "the index has not been built");
-    if (kind == 0 && !h->hdr.p) return fail(FX_ESTATE, "names need a scanned index (fx_fasta_build), not an installed table");
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    return rc;
-}
-
 // What the kernels of fx_fxi_dev.hpp need, whoever owns the rows and the names: one handle's table and stream
 // (fx_fxi_dev_write), one part of a table that several handles share (fx_fxi_part_*), or the packed names of all parts on
 // the device that writes the index (fx_fxi_join_*).
@@ -4787,9 +4763,7 @@ struct FxiJob {
     int leaf_level(bool idx, ScratchBuf<int64_t> &first, int64_t *nleaf_out) {
         if (idx) hipLaunchKernelGGL((k_fxi_fill<true, false>), dim3((unsigned)nchunks), dim3(64), 0, stream, sz.p, n, FXI_PAGE - 8, pages.p, (const int64_t *)nullptr, (int64_t *)nullptr);
         else hipLaunchKernelGGL((k_fxi_fill<false, false>), dim3((unsigned)nchunks), dim3(64), 0, stream, sz.p, n, FXI_PAGE - 8, pages.p, (const int64_t *)nullptr, (int64_t *)nullptr);
-        hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nsc), dim3(BLOCK), 0, stream, pages.p, nchunks, sums.p);
-        hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, stream, sums.p, nsc);
-        hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nsc), dim3(BLOCK), 0, stream, pages.p, nchunks, sums.p, pbase.p);
+        cnt_scan(stream, pages.p, nchunks, sums.p, pbase.p);
         HIPCHK(hipGetLastError());
         int64_t nleaf = 0;
         int isbad = 0;
@@ -4853,9 +4827,7 @@ struct FxiJob {
         if ((rc = drow.alloc(device, nd, stream)) || (rc = dlen.alloc(device, nd, stream)) || (rc = doff.alloc(device, nd + 1, stream)) ||
             (rc = dsum.alloc(device, ndc + 1, stream))) return rc;
         hipLaunchKernelGGL(k_fxi_divider_rows, dim3(nblocks(nd, BLOCK)), dim3(BLOCK), 0, stream, c, order, first_i, nd, drow.p, dlen.p);
-        hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)ndc), dim3(BLOCK), 0, stream, dlen.p, nd, dsum.p);
-        hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, stream, dsum.p, ndc);
-        hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)ndc), dim3(BLOCK), 0, stream, dlen.p, nd, dsum.p, doff.p);
+        cnt_scan(stream, dlen.p, nd, dsum.p, doff.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(d_off.data(), doff.p, (size_t)(nd + 1) * 8, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(d_rowid.data(), drow.p, (size_t)nd * 8, hipMemcpyDeviceToHost, stream));
@@ -4938,7 +4910,7 @@ static void fxi_unmap_later(fxi::FileMap &map) {
 }
 
 extern "C" int fx_fxi_dev_sort(fx_handle *h, int kind, int64_t *n_dup) {
-    int rc = fxi_check_kind(h, kind);
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     if (!n_dup) return fail(FX_EINVAL, "null n_dup");
     *n_dup = 0;
@@ -4946,20 +4918,15 @@ extern "C" int fx_fxi_dev_sort(fx_handle *h, int kind, int64_t *n_dup) {
     const int64_t n = kind == 0 ? h->n_hdr : h->n_reads;
     if (n == 0) { h->fxi_order_kind = kind; h->fxi_order_n = 0; return FX_OK; }
     if (n >= 0xFFFFFFFFll) return fail(FX_ERANGE, "too many records for the 32-bit sort index");
-    FxiCols c;
-    fxi_cols(h, kind, &c);
-    const int64_t *noff = c.name_off;
-    if (kind == 0) {
-        if ((rc = h->nm_off.alloc(n))) return rc;
-        hipLaunchKernelGGL(k_add_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->hdr.p, (int64_t)1, n, h->nm_off.p);
-        noff = h->nm_off.p;
-    }
+    const int64_t *noff;
+    const int32_t *nlen;
+    if ((rc = name_cols(h, kind, &noff, &nlen))) return rc;
     if ((rc = h->fxi_order.alloc(h->device, n, h->stream)) || (rc = h->fxi_soff.alloc(h->device, n, h->stream)) || (rc = h->fxi_slen.alloc(h->device, n, h->stream))) return rc;
     DevBuf<int64_t> d_ndup;
     if ((rc = d_ndup.alloc(1))) return rc;
     const char *what = "";
-    const int e = sort_names(h->d_data, h->base, noff, c.name_len, n, h->fxi_order.p, d_ndup.p, h->stream, &what, h->fxi_soff.p, h->fxi_slen.p);
-    if (e) return fail(e == (int)hipErrorOutOfMemory ? FX_ENOMEM : FX_EDEVICE, "name sort, %s: %s", what, hipGetErrorString((hipError_t)e));
+    const int e = sort_names(h->d_data, h->base, noff, nlen, n, h->fxi_order.p, d_ndup.p, h->stream, &what, h->fxi_soff.p, h->fxi_slen.p);
+    if (e) return sort_fail("name sort", e, what);
     HIPCHK(hipMemcpyAsync(n_dup, d_ndup.p, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->fxi_order_kind = kind;
@@ -4970,7 +4937,7 @@ extern "C" int fx_fxi_dev_sort(fx_handle *h, int kind, int64_t *n_dup) {
 // laps[8]: [0] table shape, [1] table leaf kernels, [2] table leaves to the file, [3] file grown and allocated (fallocate),
 // [4] index shape + dividers, [5] index leaf kernels, [6] index leaves to the file, [7] rest of the host levels + header
 extern "C" int fx_fxi_dev_write(fx_handle *h, int kind, const char *path, int root_table, int root_index, double *laps) {
-    int rc = fxi_check_kind(h, kind);
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     if (!path || root_table < 2 || (root_index != 0 && root_index < 2)) return fail(FX_EINVAL, "bad argument");
     const int64_t n = kind == 0 ? h->n_hdr : h->n_reads;
@@ -5085,7 +5052,7 @@ extern "C" int fx_fxi_dev_write(fx_handle *h, int kind, const char *path, int ro
 // sort is done -- *n_dup > 0: no index was written, the caller drops the empty one (fastq.c:152-156 / index.c:363-366 ignore the
 // failure of CREATE UNIQUE INDEX).  laps[8] as fx_fxi_dev_write, [4] = what of sort + index shape was NOT hidden.
 extern "C" int fx_fxi_dev_build(fx_handle *h, int kind, const char *path, int root_table, int root_index, int64_t *n_dup, double *laps) {
-    int rc = fxi_check_kind(h, kind);
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     if (!path || !n_dup || root_table < 2 || root_index < 2) return fail(FX_EINVAL, "bad argument");
     *n_dup = 0;
@@ -5134,7 +5101,7 @@ extern "C" int fx_fxi_dev_build(fx_handle *h, int kind, const char *path, int ro
             if (hipSetDevice(h->device) != hipSuccess) return fail(FX_EDEVICE, "hipSetDevice failed");
             int r;
             const int64_t *noff = I.c.name_off;
-            if (kind == 0) {                                 // FASTA: the names begin one byte behind the header offsets
+            if (kind == 0) {                                 // as name_cols, but on the side stream and into a buffer of this call
                 if ((r = noff_fa.alloc(h->device, n, s2))) return r;
                 hipLaunchKernelGGL(k_add_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, s2, h->hdr.p, (int64_t)1, n, noff_fa.p);
                 noff = noff_fa.p;
@@ -5143,7 +5110,7 @@ extern "C" int fx_fxi_dev_build(fx_handle *h, int kind, const char *path, int ro
             if ((r = order.alloc(h->device, n, s2)) || (r = soff.alloc(h->device, n, s2)) || (r = slen.alloc(h->device, n, s2)) || (r = d_nd.alloc(h->device, 1, s2))) return r;
             const char *what = "";
             const int e = sort_names(h->d_data, h->base, noff, I.c.name_len, n, order.p, d_nd.p, s2, &what, soff.p, slen.p);
-            if (e) return fail(e == (int)hipErrorOutOfMemory ? FX_ENOMEM : FX_EDEVICE, "name sort, %s: %s", what, hipGetErrorString((hipError_t)e));
+            if (e) return sort_fail("name sort", e, what);
             if (hipMemcpyAsync(&ndup, d_nd.p, 8, hipMemcpyDeviceToHost, s2) != hipSuccess || hipStreamSynchronize(s2) != hipSuccess) return fail(FX_EDEVICE, "the name sort failed");
             if (ndup) return FX_OK;
             I.order = order.p; I.c.s_off = soff.p; I.c.s_len = slen.p;
@@ -5289,7 +5256,7 @@ struct fx_fxi_join {
 };
 
 extern "C" int fx_fxi_part_shape(fx_handle *h, int kind, int64_t row_base, int64_t *out3) {
-    int rc = fxi_check_kind(h, kind);
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     if (!out3 || row_base < 0) return fail(FX_EINVAL, "bad argument");
     const int64_t n = kind == 0 ? h->n_hdr : h->n_reads;
@@ -5312,9 +5279,7 @@ extern "C" int fx_fxi_part_shape(fx_handle *h, int kind, int64_t row_base, int64
     if ((rc = l32.alloc(h->device, n, h->stream)) || (rc = l64.alloc(h->device, n, h->stream)) || (rc = sums.alloc(h->device, nchunks + 1, h->stream)) ||
         (rc = off.alloc(h->device, n + 1, h->stream))) return rc;
     hipLaunchKernelGGL(k_len_clamp, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, J.c.name_len, n, l32.p, l64.p);
-    hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, l32.p, n, sums.p);
-    hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, sums.p, nchunks);
-    hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, l32.p, n, sums.p, off.p);
+    cnt_scan(h->stream, l32.p, n, sums.p, off.p);
     HIPCHK(hipGetLastError());
     int64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, off.p + n, 8, hipMemcpyDeviceToHost, h->stream));
@@ -5337,26 +5302,19 @@ extern "C" int fx_fxi_part_firsts(fx_handle *h, int64_t *first_rows) {
 }
 
 extern "C" int fx_fxi_part_names(fx_handle *h, int kind, uint8_t *d_names, int32_t *d_lens) {
-    int rc = fxi_check_kind(h, kind);
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     const int64_t n = kind == 0 ? h->n_hdr : h->n_reads;
     if (n == 0) return FX_OK;
     if (!d_names || !d_lens) return fail(FX_EINVAL, "null destination");
-    FxiCols c;
-    fxi_cols(h, kind, &c);
-    const int64_t *noff = c.name_off;
-    if (kind == 0) {
-        if ((rc = h->nm_off.alloc(n))) return rc;
-        hipLaunchKernelGGL(k_add_i64, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, h->hdr.p, (int64_t)1, n, h->nm_off.p);
-        noff = h->nm_off.p;
-    }
+    const int64_t *noff;
+    const int32_t *nlen;
+    if ((rc = name_cols(h, kind, &noff, &nlen))) return rc;
     const int64_t nchunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
     ScratchBuf<int64_t> l64, sums, off;
     if ((rc = l64.alloc(h->device, n, h->stream)) || (rc = sums.alloc(h->device, nchunks + 1, h->stream)) || (rc = off.alloc(h->device, n + 1, h->stream))) return rc;
-    hipLaunchKernelGGL(k_len_clamp, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, c.name_len, n, d_lens, l64.p);
-    hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_lens, n, sums.p);
-    hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, h->stream, sums.p, nchunks);
-    hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, h->stream, (const int32_t *)d_lens, n, sums.p, off.p);
+    hipLaunchKernelGGL(k_len_clamp, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, nlen, n, d_lens, l64.p);
+    cnt_scan(h->stream, d_lens, n, sums.p, off.p);
     HIPCHK(hipGetLastError());
     if ((rc = fetch_common(h, FX_DEVICE, n, false, noff, l64.p, l64.p, nullptr, FX_RAW, nullptr, d_names, off.p, nullptr, 0))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -5365,7 +5323,7 @@ extern "C" int fx_fxi_part_names(fx_handle *h, int kind, uint8_t *d_names, int32
 
 // laps[2]: leaf kernels, leaves to the file
 extern "C" int fx_fxi_part_leaves(fx_handle *h, int kind, const char *path, int64_t first_new_page, int64_t leaf_base, double *laps) {
-    int rc = fxi_check_kind(h, kind);
+    int rc = names_ready(h, kind);
     if (rc) return rc;
     if (!path || first_new_page < 2) return fail(FX_EINVAL, "bad argument");
     if (h->fxi_part_kind != kind) return fail(FX_ESTATE, "fx_fxi_part_shape has not been called for this table");
@@ -5440,13 +5398,11 @@ extern "C" int fx_fxi_join_begin(int device, const uint8_t *d_names, const int32
         ScratchBuf<int64_t> sums, ndup;
         if ((rc = j->noff.alloc(device, n + 1, j->stream)) || (rc = j->order.alloc(device, n, j->stream)) || (rc = j->soff.alloc(device, n, j->stream)) ||
             (rc = j->slen.alloc(device, n, j->stream)) || (rc = sums.alloc(device, nchunks + 1, j->stream)) || (rc = ndup.alloc(device, 1, j->stream))) return bail(rc);
-        hipLaunchKernelGGL(k_cnt_chunk_sums, dim3((unsigned)nchunks), dim3(BLOCK), 0, j->stream, d_lens, n, sums.p);
-        hipLaunchKernelGGL(k_cnt_chunk_bases, dim3(1), dim3(BLOCK), 0, j->stream, sums.p, nchunks);
-        hipLaunchKernelGGL(k_cnt_offsets, dim3((unsigned)nchunks), dim3(BLOCK), 0, j->stream, d_lens, n, sums.p, j->noff.p);
+        cnt_scan(j->stream, d_lens, n, sums.p, j->noff.p);
         if (hipGetLastError() != hipSuccess) return bail(fail(FX_EDEVICE, "offsets of the gathered names"));
         const char *what = "";
         const int e = sort_names(d_names, 0, j->noff.p, d_lens, n, j->order.p, ndup.p, j->stream, &what, j->soff.p, j->slen.p);
-        if (e) return bail(fail(e == (int)hipErrorOutOfMemory ? FX_ENOMEM : FX_EDEVICE, "name sort, %s: %s", what, hipGetErrorString((hipError_t)e)));
+        if (e) return bail(sort_fail("name sort", e, what));
         if (hipMemcpyAsync(&j->n_dup, ndup.p, 8, hipMemcpyDeviceToHost, j->stream) != hipSuccess || hipStreamSynchronize(j->stream) != hipSuccess)
             return bail(fail(FX_EDEVICE, "the name sort failed"));
     }

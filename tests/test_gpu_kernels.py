@@ -947,3 +947,57 @@ def test_fastq_one_read_composition_is_used_where_it_can_be(oracle, L, shape):
     t = b.fastq_table(s.n_reads)
     for col in ("name_off", "name_len", "dlen", "rlen", "soff", "qoff"):
         np.testing.assert_array_equal(t[col], recs[col].astype(t[col].dtype), err_msg=col)
+
+
+def test_count_scan_seams_through_fetch_alloc(L):
+    """The 32-bit count scan (three kernels, chunks of SCAN_CHUNK = 1024) at its seams, through the two entries that lay their
+    answers out with it: n = 1, 1023, 1024, 1025 queries (one chunk, the last lane of one, a full one, one more) and
+    262145 = 256 * 1024 + 1 (the one workgroup that scans the chunk sums walks its loop a second time).  Intervals of 0..4 bases,
+    empty ones among them; offsets against numpy.cumsum, bytes against Python slices of the sequences the test wrote.
+    An invalid query at index 1024 of 1025 is reported as the first bad one.  With a second bad one at index 1030 -- which a
+    batch of 1025 does not have -- the batch is 1031 long, and the first is still the one reported."""
+    seqs = [b"ACGTACGTAC", b"", b"G", b"TTGACCA" * 9, b"NNACGT", b"CATG" * 5 + b"A"]
+    fa = b"".join(b">s%d x\n" % i + b"".join(s[k:k + 7] + b"\n" for k in range(0, len(s), 7)) for i, s in enumerate(seqs))
+    reads = [(b"ACGTN", b"IIII#"), (b"G", b"5"), (b"TTGACCAGT", b"ABCDEFGHI"), (b"CA", b"!~"), (b"ACGTACG", b"0123456")]
+    fq = b"".join(b"@r%d\n" % i + s + b"\n+\n" + q + b"\n" for i, (s, q) in enumerate(reads))
+    assert len(fa) < 400 and len(fq) < 400
+    a = L.Blob.from_bytes(fa)
+    assert a.fasta_build().n_seq == len(seqs)
+    q = L.Blob.from_bytes(fq)
+    assert q.fastq_build().n_reads == len(reads)
+    slen = np.array([len(s) for s in seqs])
+    rlen = np.array([len(s) for s, _ in reads])
+    rng = np.random.default_rng(1024)
+
+    def fasta_queries(n):
+        ids = rng.integers(0, len(seqs), n)
+        st = rng.integers(0, slen[ids] + 1)
+        sp = np.minimum(st + rng.integers(0, 5, n), slen[ids])
+        return ids, st, sp
+
+    for n in (1, 1023, 1024, 1025, 262145):
+        ids, st, sp = fasta_queries(n)
+        if n > 1:
+            assert (sp == st).any() and (sp - st == 4).any() and (ids == 1).any()
+        buf, offs = a.fasta_fetch_alloc(ids, st, sp)
+        np.testing.assert_array_equal(offs, np.concatenate(([0], np.cumsum(sp - st))), err_msg="FASTA offsets, n = %d" % n)
+        assert buf.tobytes() == b"".join(seqs[i][x:y] for i, x, y in zip(ids.tolist(), st.tolist(), sp.tolist())), n
+        rid = rng.integers(0, len(reads), n)
+        s, ql, qi, ro = q.fastq_fetch_alloc(rid, phred=33)
+        np.testing.assert_array_equal(ro, np.concatenate(([0], np.cumsum(rlen[rid]))), err_msg="FASTQ offsets, n = %d" % n)
+        assert s.tobytes() == b"".join(reads[i][0] for i in rid.tolist()), n
+        want_q = b"".join(reads[i][1] for i in rid.tolist())
+        assert ql.tobytes() == want_q, n
+        np.testing.assert_array_equal(qi, np.frombuffer(want_q, dtype=np.uint8).astype(np.int16) - 33, err_msg="quali, n = %d" % n)
+    for n, bad in ((1025, (1024,)), (1031, (1024, 1030))):
+        ids, st, sp = fasta_queries(n)
+        rid = rng.integers(0, len(reads), n)
+        for k in bad:
+            sp[k] = slen[ids[k]] + 1                         # one base past the record's end
+            rid[k] = len(reads)
+        with pytest.raises(L.FxError) as e:
+            a.fasta_fetch_alloc(ids, st, sp)
+        assert (e.value.code, e.value.first_bad) == (L.FX_ERANGE, 1024), n
+        with pytest.raises(L.FxError) as e:
+            q.fastq_fetch_alloc(rid, phred=33)
+        assert (e.value.code, e.value.first_bad) == (L.FX_ERANGE, 1024), n
