@@ -412,8 +412,8 @@ int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const
 
 /* ------------------------------------------------------------------ k-mer spectra (extension)
  * The reference counts single letters only (composition); these count every window of k bases, 1 <= k <= 13, into a dense
- * table of 4^k exact int64 counters on the device (pyfastx_amd/csrc/fx_kmer.hpp).  Larger k needs a sparse form and is not
- * offered.
+ * table of 4^k exact int64 counters on the device (pyfastx_amd/csrc/fx_kmer.hpp).  Larger k, up to 31, has a sparse form:
+ * the k-mer tables below.
  *   alphabet     A C G T and a c g t, case-insensitive: A = 0, C = 1, G = 2, T = 3.  Every other byte (N, U, IUPAC codes,
  *                '-', '*', digits, bytes >= 128) is invalid, and a window that holds one is not counted.
  *   code         of the window b0 b1 .. b(k-1): sum of code(bj) * 4^(k-1-j) -- the first base is the most significant digit.
@@ -439,6 +439,36 @@ int fx_fasta_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64
                    int64_t *n_rows, int64_t *first_bad);
 int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
                    int64_t **counts, int64_t *first_bad);
+
+/* ------------------------------------------------------------------ k-mer tables (extension)
+ * The sparse form of the spectra above for 1 <= k <= 31 (pyfastx_amd/csrc/fx_kmer_table.hpp): alphabet, code, FX_KMER_CANONICAL
+ * and the windows of a selection are those of fx_fasta_kmers / fx_fastq_kmers, word for word.  A code has 2k <= 62 bits and is
+ * an exact non-negative int64.  The table of a selection is the set of codes that occur at least once among its valid
+ * windows, ascending, each with its exact count: codes[i] < codes[i + 1], counts[i] >= 1; with FX_KMER_CANONICAL only
+ * canonical codes appear.  A record or read listed twice counts twice.
+ *   min_count    >= 1: entries whose total count is below it are dropped, on the device, after every contribution to a code
+ *                has been summed.
+ *   *n_windows   the valid windows of the selection, before min_count (= the sum of the counts when min_count is 1).
+ *   *n_parts     the sort-and-reduce rounds that ran: the codes are sorted in ranges of their leading bits, as many at a time
+ *                as the budget holds; a range with more windows than that is taken in pieces whose tables are summed.
+ *   max_bytes    bound on the device working memory of the call beyond the resident stream and its tables (key buffers,
+ *                histograms, partial lists).  0: the default, 8 GiB -- a third of the 24 GiB the library's scratch pool
+ *                keeps, so that the buffers of a call come out of it and go back into it beside the blocks an open leaves
+ *                there.  A value below 1 MiB: FX_EINVAL.  The table does not depend on it, *n_parts does.
+ * *codes / *counts are pinned blocks of fx_pinned_alloc that belong to the caller (fx_pinned_free), *n_distinct entries each,
+ * never NULL after FX_OK; *n_distinct may be 0.
+ * Errors: a null handle or output pointer, start without end: FX_EINVAL, nothing touched; before fx_fasta_build /
+ * fx_fastq_build: FX_ESTATE; a byte-range shard: FX_EINVAL; unknown flag bits, k outside 1..31, min_count < 1, max_bytes
+ * below 1 MiB: FX_EINVAL; an id outside the table, or an interval outside 0 <= start <= end <= rlen: *first_bad = its position
+ * among the queries, FX_ERANGE, nothing allocated; no device: FX_EDEVICE (there is no CPU path); a code range whose table
+ * alone does not fit the budget (or one read with more windows than a key buffer holds): FX_ENOMEM, the message names the
+ * max_bytes that would do. */
+int fx_fasta_kmer_table(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, int64_t min_count, int64_t max_bytes,
+                        int64_t **codes, int64_t **counts, int64_t *n_distinct, int64_t *n_windows, int64_t *n_parts,
+                        int64_t *first_bad);
+int fx_fastq_kmer_table(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                        int64_t min_count, int64_t max_bytes, int64_t **codes, int64_t **counts, int64_t *n_distinct,
+                        int64_t *n_windows, int64_t *n_parts, int64_t *first_bad);
 
 /* ------------------------------------------------------------------ Fastx
  * Replaces kseq_read (kseq.c:138-179) as pyfastx_fastx_next drives it (fastx.c:124-130): index-free iteration over a

@@ -50,7 +50,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -234,6 +234,8 @@ def lib():
     L.fx_fastq_format_alloc.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fasta_kmers.argtypes = [vp, i32, i32, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_kmers.argtypes = [vp, i32, i32, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(i64)]
+    L.fx_fasta_kmer_table.argtypes = [vp, i32, i32, vp, i64, i64, i64] + [C.POINTER(vp)] * 2 + [C.POINTER(i64)] * 4
+    L.fx_fastq_kmer_table.argtypes = [vp, i32, i32, vp, i64, vp, vp, i64, i64] + [C.POINTER(vp)] * 2 + [C.POINTER(i64)] * 4
     L.fx_names_build.argtypes = [vp, i32]
     L.fx_names_lookup.argtypes = [vp, i32, i64, vp, vp, vp]
     L.fx_revcomp.argtypes = [i32, i32, vp, i64, i32]
@@ -1160,6 +1162,33 @@ class Blob:
         if rc:
             _raise(rc, first_bad=int(bad.value))
         return pinned_array(p.value, 4 ** int(k), np.int64)
+
+    def _kmer_table(self, call, head, min_count, max_bytes):
+        pc, pn = C.c_void_p(), C.c_void_p()
+        nd, nw, parts, bad = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+        rc = call(*head, int(min_count), int(max_bytes), C.byref(pc), C.byref(pn), C.byref(nd), C.byref(nw), C.byref(parts), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(nd.value)
+        return pinned_array(pc.value, max(m, 1), np.int64)[:m], pinned_array(pn.value, max(m, 1), np.int64)[:m], int(nw.value), int(parts.value)
+
+    def fasta_kmer_table(self, k, canonical=False, ids=None, min_count=1, max_bytes=0):
+        """Sparse k-mer table of the resident FASTA table (fx_fasta_kmer_table), 1 <= k <= 31 -> (codes int64[n] ascending,
+        counts int64[n], n_windows, n_parts), the arrays in pinned memory.  ids as for fasta_kmers; max_bytes = 0: the
+        library's default budget of device working memory."""
+        buf, n_ids, _ = self._kmer_ids(ids)
+        head = (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids)
+        return self._kmer_table(lib().fx_fasta_kmer_table, head, min_count, max_bytes)
+
+    def fastq_kmer_table(self, k, canonical=False, ids=None, start=None, end=None, min_count=1, max_bytes=0):
+        """Sparse k-mer table of the reads `ids` cut to [start, end) (fx_fastq_kmer_table) -> what fasta_kmer_table returns."""
+        buf, n_ids, _ = self._kmer_ids(ids)
+        start = None if start is None else self._i64(start)
+        end = None if end is None else self._i64(end)
+        if start is not None and start.size == 0:
+            start = end = None                                 # no query, no interval
+        head = (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, _ptr(start), _ptr(end))
+        return self._kmer_table(lib().fx_fastq_kmer_table, head, min_count, max_bytes)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)

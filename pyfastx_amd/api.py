@@ -848,11 +848,22 @@ class Fasta(_fxobj.FastaCore):
         other byte (N, IUPAC codes, ...) is not counted; windows run across line ends, never across records.  canonical=True
         counts a window under the smaller of its code and its reverse complement's (a palindrome once); the other entries
         stay 0.  ids: restrict to these records (names or 0-based ids; a record listed twice counts twice).  1 <= k <= 13:
-        the dense table is 8 * 4**k bytes, 512 MiB at k = 13; larger k needs a sparse form and is out of scope."""
+        the dense table is 8 * 4**k bytes, 512 MiB at k = 13; for larger k see kmer_table."""
         from . import kmer
         k = kmer.check_k(k)
         sel = None if ids is None else self._ids_of(ids)
         return kmer.fasta_counts_blob(self._search_blob(), k, canonical, sel)
+
+    def kmer_table(self, k, canonical=False, ids=None, min_count=1, max_bytes=None):
+        """Extension: the sparse k-mer table of the `seq` of every record, 1 <= k <= 31 -> kmer.KmerTable: the codes that
+        occur (int64, ascending) with their exact counts, by the definition of kmer_counts; sorted and reduced on the GPU from
+        the resident stream (csrc/fx_kmer_table.hpp).  min_count: entries that occur less often are dropped on the device.
+        max_bytes: device working memory of the call (None: the library's default, 8 GiB; at least 1 MiB) -- a smaller budget
+        takes more rounds (KmerTable.n_parts), the table is the same."""
+        from . import kmer
+        kmer.check_table(k, min_count, max_bytes)
+        sel = None if ids is None else self._ids_of(ids)
+        return kmer.fasta_table_blob(self._search_blob(), k, canonical, sel, min_count, max_bytes)
 
     def kmer_profile(self, k, canonical=False, ids=None, max_bytes=1 << 30):
         """Extension: one k-mer spectrum per record -> int64[n_sel, 4**k] in pinned memory, rows in the order of ids (all
@@ -1920,6 +1931,13 @@ class Fastq(_fxobj.FastqCore):
         from . import kmer
         k = kmer.check_k(k)
         return kmer.fastq_counts_blob(self._qc_blob(), self._rlen_host.size, k, canonical, ids, start, end)
+
+    def kmer_table(self, k, canonical=False, ids=None, start=None, end=None, min_count=1, max_bytes=None):
+        """Extension: the sparse k-mer table of seq[start:end] of the reads `ids`, 1 <= k <= 31 -> kmer.KmerTable; the
+        definition and the arguments min_count / max_bytes are Fasta.kmer_table's, ids / start / end follow kmer_counts."""
+        from . import kmer
+        kmer.check_table(k, min_count, max_bytes)
+        return kmer.fastq_table_blob(self._qc_blob(), self._rlen_host.size, k, canonical, ids, start, end, min_count, max_bytes)
 
     def records(self, ids=None, start=None, end=None, min_len=0):
         """Extension: four-line FASTQ records of the reads `ids` (None: every read), cut to [start, end) -- what trim returned

@@ -262,11 +262,13 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_scan(uint32_t *__restrict__ his
 // The tile is put in digit order in LDS first and leaves from there: neighbouring lanes then write neighbouring places of a
 // bucket (a tile holds 16 pairs per digit on average: runs of 128 + 64 bytes) where, straight from the registers, every
 // store instruction went to 64 different places (2.0 ms per pass for 10^8 pairs).
+// VALS = false: keys only (vin / vout unused) -- the sparse k-mer tables of fx_kmer_table.hpp.
+template <bool VALS>
 __global__ __launch_bounds__(RS_BLOCK) void k_rs_scatter(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin,
                                                          uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, int64_t n, int shift,
                                                          int64_t nblk, const uint32_t *__restrict__ offs, const uint32_t *__restrict__ totals) {
     __shared__ uint64_t lk[RS_TILE];
-    __shared__ uint32_t lv[RS_TILE];
+    __shared__ uint32_t lv[VALS ? RS_TILE : 1];
     __shared__ uint32_t cnt[RS_BLOCK / 64][256];          // per wave: pairs seen so far per digit; then: pairs of the digit in the waves before
     __shared__ uint32_t lbase[256];                       // where the digit starts in the tile once it is in digit order
     __shared__ uint32_t gdelta[256];                      // place in the output - place in the ordered tile, per digit
@@ -291,7 +293,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_scatter(const uint64_t *__restr
         const int64_t i = start + r * 64 + lane;
         const bool valid = i < n;
         k[r] = valid ? kin[i] : 0ull;
-        v[r] = valid ? vin[i] : 0u;
+        v[r] = VALS && valid ? vin[i] : 0u;
         const uint32_t d = (uint32_t)(k[r] >> shift) & 255u;
         const uint64_t peers = rs_peers(d, valid);
         const uint32_t below = (uint32_t)__popcll(peers & ((1ull << lane) - 1));
@@ -320,7 +322,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_scatter(const uint64_t *__restr
             const uint32_t d = dr[r] >> 16;
             const uint32_t lp = lbase[d] + cnt[w][d] + (dr[r] & 0xFFFFu);
             lk[lp] = k[r];
-            lv[lp] = v[r];
+            if (VALS) lv[lp] = v[r];
         }
     }
     __syncthreads();
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_scatter(const uint64_t *__restr
         const uint64_t key = lk[j];
         const uint32_t pos = j + gdelta[(uint32_t)(key >> shift) & 255u];
         kout[pos] = key;
-        vout[pos] = lv[j];
+        if (VALS) vout[pos] = lv[j];
     }
 }
 
@@ -366,12 +368,11 @@ __global__ __launch_bounds__(SB) void k_sort_finish(const uint64_t *__restrict__
         if (e__ != hipSuccess) { *where = what; cleanup(); return (int)e__; } \
     } while (0)
 
-struct RadixScratch { uint32_t *hist = nullptr, *totals = nullptr; int64_t nblk = 0; };
-
-// sort the pairs by bits [begin_bit, end_bit) of the key, stable; cur: index of the buffer pair that holds the data,
-// updated.  Digits that are equal in all keys cost a histogram but no data movement.
-static hipError_t radix_sort_pairs(uint64_t *keys[2], uint32_t *vals[2], int &cur, int64_t n, int begin_bit, int end_bit,
-                                   const RadixScratch &sc, hipStream_t s) {
+// sort by bits [begin_bit, end_bit) of the key, stable; cur: index of the buffer pair that holds the data, updated.  Digits
+// that are equal in all keys cost a histogram but no data movement.  VALS = false: keys alone travel (vals unused).
+template <bool VALS>
+static hipError_t radix_sort(uint64_t *keys[2], uint32_t *vals[2], int &cur, int64_t n, int begin_bit, int end_bit,
+                             const RadixScratch &sc, hipStream_t s, int *moved = nullptr) {
     uint32_t totals[256];
     for (int shift = begin_bit; shift < end_bit; shift += 8) {
         hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)sc.nblk), dim3(RS_BLOCK), 0, s, keys[cur], n, shift, sc.nblk, sc.hist);
@@ -382,11 +383,33 @@ static hipError_t radix_sort_pairs(uint64_t *keys[2], uint32_t *vals[2], int &cu
         bool single = false;
         for (int b = 0; b < 256; ++b) single = single || (int64_t)totals[b] == n;
         if (single) continue;
-        hipLaunchKernelGGL(k_rs_scatter, dim3((unsigned)sc.nblk), dim3(RS_BLOCK), 0, s, keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1],
-                           n, shift, sc.nblk, sc.hist, sc.totals);
+        hipLaunchKernelGGL(k_rs_scatter<VALS>, dim3((unsigned)sc.nblk), dim3(RS_BLOCK), 0, s, keys[cur], VALS ? vals[cur] : nullptr, keys[cur ^ 1],
+                           VALS ? vals[cur ^ 1] : nullptr, n, shift, sc.nblk, sc.hist, sc.totals);
         cur ^= 1;
+        if (moved) ++*moved;
     }
     return hipGetLastError();
+}
+static hipError_t radix_sort_pairs(uint64_t *keys[2], uint32_t *vals[2], int &cur, int64_t n, int begin_bit, int end_bit,
+                                   const RadixScratch &sc, hipStream_t s) {
+    return radix_sort<true>(keys, vals, cur, n, begin_bit, end_bit, sc, s);
+}
+int64_t radix_tiles(int64_t n) { return (n + RS_TILE - 1) / RS_TILE; }
+// (the grid is the tiles of THIS n, whatever the scratch was sized for: a workgroup of k_rs_scatter behind the last key would
+// take its negative rest for a count)
+static RadixScratch radix_scratch_for(const RadixScratch &sc, int64_t n) {
+    RadixScratch t = sc;
+    t.nblk = radix_tiles(n);
+    return t;
+}
+hipError_t radix_sort_keys(uint64_t *keys[2], int &cur, int64_t n, int end_bit, const RadixScratch &sc, hipStream_t s, int *moved) {
+    uint32_t *none[2] = {nullptr, nullptr};
+    if (n <= 0 || radix_tiles(n) > sc.nblk) return hipErrorInvalidValue;
+    return radix_sort<false>(keys, none, cur, n, 0, end_bit, radix_scratch_for(sc, n), s, moved);
+}
+hipError_t radix_sort_rows(uint64_t *keys[2], uint32_t *vals[2], int &cur, int64_t n, int end_bit, const RadixScratch &sc, hipStream_t s, int *moved) {
+    if (n <= 0 || radix_tiles(n) > sc.nblk) return hipErrorInvalidValue;
+    return radix_sort<true>(keys, vals, cur, n, 0, end_bit, radix_scratch_for(sc, n), s, moved);
 }
 
 int sort_names(const uint8_t *data, int64_t gbase, const int64_t *name_off, const int32_t *name_len, int64_t n,

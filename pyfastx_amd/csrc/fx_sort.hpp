@@ -11,6 +11,16 @@ hipError_t pool_malloc(void **p, size_t bytes);
 void *scratch_get(int device, size_t bytes, size_t *cap);
 void scratch_put(int device, void *p, size_t cap);
 
+// The stable 8-bit LSD passes of fx_sort.hip on their own (fx_kmer_table.hpp): n <= 2^31 keys in keys[cur], sorted by bits
+// [0, end_bit); the sorted keys end in keys[cur] (updated).  hist: 256 * nblk words with nblk >= radix_tiles(n) (the scratch
+// may be sized for more keys than a call sorts), totals: 256 words, both on the device.  radix_sort_keys moves the keys alone, radix_sort_rows carries a 32-bit value with each.  Every pass waits for the
+// stream (a digit that is equal in all keys moves nothing); *moved += the passes that moved data.
+struct RadixScratch { uint32_t *hist = nullptr, *totals = nullptr; int64_t nblk = 0; };
+int64_t radix_tiles(int64_t n);
+hipError_t radix_sort_keys(uint64_t *keys[2], int &cur, int64_t n, int end_bit, const RadixScratch &sc, hipStream_t s, int *moved = nullptr);
+hipError_t radix_sort_rows(uint64_t *keys[2], uint32_t *vals[2], int &cur, int64_t n, int end_bit, const RadixScratch &sc, hipStream_t s,
+                           int *moved = nullptr);
+
 // Sorted order of n names that live in the resident stream (name i = name_len[i] bytes at data + name_off[i] - gbase)
 // in SQLite's BINARY collation: memcmp over the common length, the shorter name first on a tie.  d_order[i] (device,
 // int64) = 0-based index of the i-th smallest name, equal names in index order; *d_ndup (device) = number of

@@ -46,6 +46,7 @@
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
 #include "fx_kmer.hpp"
+#include "fx_kmer_table.hpp"
 
 using namespace fx;
 
@@ -322,10 +323,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold"};
 
 struct Prof {
     bool on = false;
@@ -4196,6 +4197,320 @@ extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t 
     } else if ((rc = out.prepare(h, k, 1, false))) return rc;
     out.pin.release(counts);
     return FX_OK;
+}
+
+// ------------------------------------------------------------------ sparse k-mer tables (fx_kmer_table.hpp)
+// Device working memory of a call, per key of capacity: two key buffers, the counts, the heads' positions (28 bytes) and the
+// sort's histograms (half a byte); in fold mode also the two (key, row) buffers of the fold, its counts and the running list
+// (48 bytes more).  KT_FIXED_BYTES: the bins, the cursor, the digit totals, the chunk sums of the scans.
+constexpr int64_t KT_DEFAULT_BYTES = (int64_t)8 << 30, KT_MIN_BYTES = 1 << 20, KT_FIXED_BYTES = 1 << 16;
+constexpr int64_t KT_KEY_BYTES = 29, KT_FOLD_KEY_BYTES = 77;
+constexpr int64_t KT_MAX_KEYS = (int64_t)1 << 31;            // the sort's offsets are 32-bit
+
+// What is walked: `units` position units (runs, queries) of at most per_unit windows each; walk(emit, A, u0, u1) launches the
+// histogram (the whole selection) or the emit pass over the units [u0, u1).
+struct KtSource {
+    std::function<void(bool, const KtArgs &, int64_t, int64_t)> walk;
+    int64_t units = 0, per_unit = 1;
+};
+
+// The table as it grows in pinned memory: the partitions' results are final as they come and are laid back to back.
+struct KtOut {
+    PinnedOut<2> pin;
+    int64_t rows = 0, cap = 0;
+    explicit KtOut(fx_handle *h) : pin(h) {}
+    bool reserve(int64_t need) {
+        if (need <= cap && pin.p[0]) return true;
+        const int64_t ncap = std::max<int64_t>({need, 2 * cap, 1});
+        void *a = fx_pinned_alloc(ncap * 8), *b = fx_pinned_alloc(ncap * 8);
+        if (!a || !b) { fx_pinned_free(a); fx_pinned_free(b); return false; }
+        if (rows) { memcpy(a, pin.p[0], (size_t)rows * 8); memcpy(b, pin.p[1], (size_t)rows * 8); }
+        fx_pinned_free(pin.p[0]); fx_pinned_free(pin.p[1]);
+        pin.p[0] = a; pin.p[1] = b; cap = ncap;
+        return true;
+    }
+    int append(fx_handle *h, const uint64_t *d_codes, const int64_t *d_counts, int64_t n) {
+        if (n <= 0) return FX_OK;
+        if (!reserve(rows + n)) return fail(FX_ENOMEM, "pinned blocks for %lld table entries", (long long)(rows + n));
+        int rc = home(h, "k-mer table", {{pin.as<int64_t>(0) + rows, d_codes, n * 8}, {pin.as<int64_t>(1) + rows, d_counts, n * 8}});
+        if (!rc) rows += n;
+        return rc;
+    }
+};
+
+struct KtWork {
+    fx_handle *h;
+    int bits;                                                // 2k
+    int64_t cap = 0;                                         // keys per buffer
+    ScratchBuf<uint64_t> key[2], fkey[2], rk;
+    ScratchBuf<int64_t> cnt, W, rc, sums;
+    ScratchBuf<uint32_t> S, row[2], hist, totals;
+    RadixScratch rs;
+    unsigned long long *cursor = nullptr;                    // (in the block of the bins)
+    int64_t *d_tot = nullptr;
+    int64_t n_run = 0;                                       // rows of the running list
+    KtWork(fx_handle *hh, int k) : h(hh), bits(2 * k) {}
+    int alloc(int64_t keys, bool fold) {
+        cap = keys;
+        int rc_ = 0;
+        const int dev = h->device;
+        hipStream_t s = h->stream;
+        rs.nblk = radix_tiles(cap);
+        if ((rc_ = key[0].alloc(dev, cap, s)) || (rc_ = key[1].alloc(dev, cap, s)) || (rc_ = cnt.alloc(dev, cap, s)) || (rc_ = S.alloc(dev, cap, s)) ||
+            (rc_ = hist.alloc(dev, rs.nblk * 256, s)) || (rc_ = totals.alloc(dev, 256, s)) || (rc_ = sums.alloc(dev, cap / SRCH_CHUNK + 2, s)))
+            return rc_;
+        rs.hist = hist.p; rs.totals = totals.p;
+        if (fold && ((rc_ = fkey[0].alloc(dev, cap, s)) || (rc_ = fkey[1].alloc(dev, cap, s)) || (rc_ = row[0].alloc(dev, cap, s)) ||
+                     (rc_ = row[1].alloc(dev, cap, s)) || (rc_ = W.alloc(dev, cap, s)) || (rc_ = rk.alloc(dev, cap, s)) || (rc_ = rc.alloc(dev, cap, s))))
+            return rc_;
+        return FX_OK;
+    }
+    // flagged elements among n > 0 -> *total (waits); the chunk offsets stay in `sums` for the compaction that follows
+    template <class Ld> int count(int id, Ld ld, int64_t n, int64_t *total) {
+        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
+        FX_LAUNCH(h, id, (k_sscan_sums<1, Ld>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums.p);
+        FX_LAUNCH(h, id, (k_sscan_top<1>), dim3(1), dim3(BLOCK), sums.p, nch, d_tot);
+        HIPCHK(hipGetLastError());
+        return read_home(h, total, d_tot, 8);
+    }
+    template <class Ld, class Put> void compact(int id, Ld ld, int64_t n, Put put) {
+        FX_LAUNCH(h, id, (k_kt_compact<Ld, Put>), dim3((unsigned)((n + SRCH_CHUNK - 1) / SRCH_CHUNK)), dim3(BLOCK), ld, n, (const int64_t *)sums.p, put);
+    }
+    // n > 0 keys in key[0] -> *nd entries whose count reaches m, ascending: codes in *codes, counts in cnt
+    int sort_reduce(int64_t n, int64_t m, int64_t *nd, const uint64_t **codes) {
+        uint64_t *kp[2] = {key[0].p, key[1].p};
+        int cur = 0;
+        h->prof.begin(K_KT_SORT, h->stream);
+        hipError_t e = radix_sort_keys(kp, cur, n, bits, rs, h->stream);
+        h->prof.end(h->stream);
+        if (e != hipSuccess) return fail(FX_EDEVICE, "k-mer table sort: %s", hipGetErrorString(e));
+        int64_t heads = 0;
+        int r = count(K_KT_REDUCE, KtLdHead{kp[cur]}, n, &heads);
+        if (r) return r;
+        compact(K_KT_REDUCE, KtLdHead{kp[cur]}, n, KtPutStart{S.p});
+        const KtLdKeep keep{S.p, heads, n, m};
+        if ((r = count(K_KT_REDUCE, keep, heads, nd))) return r;
+        if (*nd > 0) compact(K_KT_REDUCE, keep, heads, KtPutEntry{kp[cur], S.p, heads, n, kp[cur ^ 1], cnt.p});
+        *codes = kp[cur ^ 1];
+        return FX_OK;
+    }
+    // the running list and ns > 0 rows (codes, cnt) -> the running list
+    int fold(const uint64_t *codes, int64_t ns) {
+        const int64_t m = n_run + ns;
+        if (m > cap)
+            return fail(FX_ENOMEM, "the k-mer table of one code range has more than %lld distinct codes: max_bytes of %lld bytes or more needed",
+                        (long long)cap, (long long)(KT_FIXED_BYTES + m * KT_FOLD_KEY_BYTES));
+        FX_LAUNCH(h, K_KT_FOLD, k_kt_concat, dim3(nblocks(m, BLOCK)), dim3(BLOCK), (const uint64_t *)rk.p, (const int64_t *)rc.p, n_run, codes,
+                  (const int64_t *)cnt.p, ns, fkey[0].p, W.p, row[0].p);
+        uint64_t *kp[2] = {fkey[0].p, fkey[1].p};
+        uint32_t *vp[2] = {row[0].p, row[1].p};
+        int cur = 0;
+        h->prof.begin(K_KT_FOLD, h->stream);
+        hipError_t e = radix_sort_rows(kp, vp, cur, m, bits, rs, h->stream);
+        h->prof.end(h->stream);
+        if (e != hipSuccess) return fail(FX_EDEVICE, "k-mer table fold: %s", hipGetErrorString(e));
+        int r = count(K_KT_FOLD, KtLdHead{kp[cur]}, m, &n_run);
+        if (r) return r;
+        compact(K_KT_FOLD, KtLdHead{kp[cur]}, m, KtPutFold{kp[cur], vp[cur], W.p, m, rk.p, rc.p});
+        return FX_OK;
+    }
+};
+
+static int kmer_table_run(fx_handle *h, int k, int64_t min_count, int64_t max_bytes, const KtSource &src, KtOut &out, int64_t *n_windows,
+                          int64_t *n_parts) {
+    int rc;
+    const int bin_bits = std::min(2 * k, KT_BIN_BITS), shift = 2 * k - bin_bits, n_bins = 1 << bin_bits;
+    // 1. the histogram of the top bits
+    ScratchBuf<unsigned long long> ctl;
+    if ((rc = ctl.alloc(h->device, KT_BINS + 8, h->stream))) return rc;
+    HIPCHK(hipMemsetAsync(ctl.p, 0, (KT_BINS + 8) * 8, h->stream));
+    KtArgs A{};
+    A.shift = shift; A.bins = ctl.p; A.cursor = ctl.p + KT_BINS;
+    src.walk(false, A, 0, src.units);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> bins((size_t)KT_BINS);
+    if ((rc = read_home(h, bins.data(), ctl.p, KT_BINS * 8))) return rc;
+    int64_t total = 0, largest = 0;
+    for (int b = 0; b < n_bins; ++b) { total += bins[(size_t)b]; largest = std::max(largest, bins[(size_t)b]); }
+    *n_windows = total;
+    if (!total) return FX_OK;
+    // 2. the capacity of the key buffers; a bin above it is taken in position sub-chunks and folded
+    int64_t cap = std::min((max_bytes - KT_FIXED_BYTES) / KT_KEY_BYTES, KT_MAX_KEYS);
+    const bool fold = largest > cap;
+    if (fold) cap = std::min((max_bytes - KT_FIXED_BYTES) / KT_FOLD_KEY_BYTES, KT_MAX_KEYS);
+    if (fold && src.per_unit > cap)
+        return fail(FX_ENOMEM, "one read of %lld windows does not fit a key buffer: max_bytes of %lld bytes or more needed", (long long)src.per_unit,
+                    (long long)(KT_FIXED_BYTES + src.per_unit * KT_FOLD_KEY_BYTES));
+    // 3. consecutive bins -> partitions of at most cap windows
+    struct Part { int b0, b1; int64_t n; };
+    std::vector<Part> parts;
+    Part cur{0, 0, 0};
+    int64_t room = 0;                                        // keys of the largest partition that is not folded
+    for (int b = 0; b < n_bins; ++b) {
+        const int64_t c = bins[(size_t)b];
+        if (cur.n + c > cap) {
+            if (cur.n) parts.push_back(cur);
+            cur = Part{b, b, 0};
+        }
+        cur.b1 = b + 1;
+        cur.n += c;
+        if (cur.n > cap) { parts.push_back(cur); cur = Part{b + 1, b + 1, 0}; }       // one bin above the capacity, alone
+    }
+    if (cur.n) parts.push_back(cur);
+    for (const Part &p : parts) room = std::max(room, std::min(p.n, cap));
+    KtWork w(h, k);
+    if ((rc = w.alloc(fold ? cap : room, fold))) return rc;
+    w.cursor = ctl.p + KT_BINS;
+    w.d_tot = (int64_t *)(ctl.p + KT_BINS + 1);
+    A.out = w.key[0].p; A.cap = (uint64_t)w.cap;
+    const int64_t sub = std::max<int64_t>(cap / src.per_unit, 1);       // position units per sub-chunk of a folded partition
+    for (const Part &p : parts) {
+        A.lo = (uint64_t)p.b0 << shift; A.hi = (uint64_t)p.b1 << shift;
+        const bool folded = p.n > cap;
+        w.n_run = 0;
+        for (int64_t u0 = 0; u0 < src.units; u0 += folded ? sub : src.units) {
+            const int64_t u1 = folded ? std::min(u0 + sub, src.units) : src.units;
+            HIPCHK(hipMemsetAsync(w.cursor, 0, 8, h->stream));
+            src.walk(true, A, u0, u1);
+            HIPCHK(hipGetLastError());
+            int64_t n = 0;
+            if ((rc = read_home(h, &n, w.cursor, 8))) return rc;
+            if (n > w.cap || (!folded && n != p.n)) return fail(FX_EDEVICE, "k-mer table: %lld codes where the histogram counted %lld", (long long)n, (long long)p.n);
+            if (!n) continue;
+            int64_t nd = 0;
+            const uint64_t *codes = nullptr;
+            if ((rc = w.sort_reduce(n, folded ? 1 : min_count, &nd, &codes))) return rc;
+            ++*n_parts;
+            if (folded) rc = w.fold(codes, nd);
+            else rc = out.append(h, codes, w.cnt.p, nd);
+            if (rc) return rc;
+        }
+        if (folded && w.n_run > 0) {                         // min_count only now that every sub-chunk has been added
+            int64_t nk = 0;
+            const KtLdGe ge{w.rc.p, min_count};
+            if ((rc = w.count(K_KT_FOLD, ge, w.n_run, &nk))) return rc;
+            if (nk > 0) w.compact(K_KT_FOLD, ge, w.n_run, KtPutCopy{w.rk.p, w.rc.p, w.key[0].p, w.cnt.p});
+            if ((rc = out.append(h, w.key[0].p, w.cnt.p, nk))) return rc;
+        }
+    }
+    return FX_OK;
+}
+
+// what both entries check first, in the order of the dense ones; -> max_bytes with the default put in
+static int kmer_table_args(int32_t k, int flags, int64_t min_count, int64_t *max_bytes) {
+    if (flags & ~FX_KMER_CANONICAL) return fail(FX_EINVAL, "unknown flag bits %d", flags);
+    if (k < 1 || k > KT_MAX_K) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, KT_MAX_K);
+    if (min_count < 1) return fail(FX_EINVAL, "min_count %lld below 1", (long long)min_count);
+    if (*max_bytes == 0) *max_bytes = KT_DEFAULT_BYTES;
+    if (*max_bytes < KT_MIN_BYTES) return fail(FX_EINVAL, "max_bytes %lld below %lld", (long long)*max_bytes, (long long)KT_MIN_BYTES);
+    return FX_OK;
+}
+static int kmer_table_done(KtOut &out, int64_t **codes, int64_t **counts, int64_t *n_distinct) {
+    if (!out.reserve(1)) return fail(FX_ENOMEM, "pinned blocks for the k-mer table");
+    *n_distinct = out.rows;
+    out.pin.release(codes, counts);
+    return FX_OK;
+}
+
+extern "C" int fx_fasta_kmer_table(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, int64_t min_count, int64_t max_bytes,
+                                   int64_t **codes, int64_t **counts, int64_t *n_distinct, int64_t *n_windows, int64_t *n_parts, int64_t *first_bad) {
+    if (!h || !codes || !counts || !n_distinct || !n_windows || !n_parts || !first_bad) return fail(FX_EINVAL, "null argument");
+    *codes = *counts = nullptr; *n_distinct = *n_windows = *n_parts = 0; *first_bad = -1;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
+    int rc = kmer_table_args(k, flags, min_count, &max_bytes);
+    if (rc) return rc;
+    rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, first_bad, kBadRecord);
+    if (rc) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    KtOut out(h);
+    if (n_sel > 0) {
+        Staged st(h);
+        st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+        SearchPlan P;
+        P.masks = nullptr;
+        int64_t *d_tot = nullptr, n_runs = 0;
+        if ((rc = fasta_run_plan(h, st, K_KMER_SCAN, ids, n_ids, k, &P, &d_tot, &n_runs))) return rc;
+        if (n_runs > 0) {
+            // the kept bytes of every run and their scan: the cut at slen is known before the first window is produced
+            ScratchBuf<uint32_t> packed;
+            ScratchBuf<int64_t> K;
+            if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
+            FX_LAUNCH(h, K_KT_KEPT, k_kt_kept, dim3(nblocks(n_runs, BLOCK)), dim3(BLOCK), P, packed.p);
+            if ((rc = sscan<1>(h, st, K_KMER_SCAN, SrchLdKept{packed.p}, n_runs, K.p, d_tot))) return rc;
+            packed.release();
+            const bool canon = flags & FX_KMER_CANONICAL;
+            KtSource src;
+            src.units = n_runs; src.per_unit = SRCH_RUN;
+            src.walk = [&](bool emit, const KtArgs &A, int64_t u0, int64_t u1) {
+                with_bool(canon, [&](auto C) {
+                    with_bool(emit, [&](auto E) {
+                        static const int64_t resident = resident_blocks(h, k_kt_fasta<C(), E()>);
+                        const int64_t per = KMER_MAX_WINDOWS / SRCH_RUN;          // runs per launch: no 32-bit counter of a workgroup can wrap
+                        for (int64_t g0 = u0; g0 < u1; g0 += per) {
+                            const int64_t g1 = std::min(g0 + per, u1);
+                            FX_LAUNCH(h, E() ? K_KT_EMIT : K_KT_HIST, (k_kt_fasta<C(), E()>), dim3((unsigned)std::min<int64_t>(nblocks(g1 - g0, BLOCK), resident)), dim3(BLOCK),
+                                      P, (int)k, g0, g1, (const int64_t *)K.p, A);
+                        }
+                    });
+                });
+            };
+            if ((rc = kmer_table_run(h, k, min_count, max_bytes, src, out, n_windows, n_parts))) return rc;
+        }
+    }
+    return kmer_table_done(out, codes, counts, n_distinct);
+}
+
+extern "C" int fx_fastq_kmer_table(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                                   int64_t min_count, int64_t max_bytes, int64_t **codes, int64_t **counts, int64_t *n_distinct, int64_t *n_windows,
+                                   int64_t *n_parts, int64_t *first_bad) {
+    if (!h || !codes || !counts || !n_distinct || !n_windows || !n_parts || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    *codes = *counts = nullptr; *n_distinct = *n_windows = *n_parts = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    FqLaunch q;
+    int rc = fq_prepare(h, 0, 0, &q);                          // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+    if (rc) return rc;
+    if ((rc = kmer_table_args(k, flags, min_count, &max_bytes))) return rc;
+    const int64_t n = ids ? n_ids : h->n_reads;
+    if ((rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead))) return rc;
+    KtOut out(h);
+    if (n > 0) {
+        Staged st(h);
+        st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
+        const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
+        if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+        const FqView v = fq_view(h);
+        if (start) {
+            BadFlag bad;
+            if ((rc = bad.arm(h, st))) return rc;
+            FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, d_ids, n, d_start, d_end, bad.d);
+            HIPCHK(hipGetLastError());
+            if ((rc = bad.read(h, first_bad))) return rc;
+            if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
+        }
+        const bool canon = flags & FX_KMER_CANONICAL;
+        KtSource src;
+        src.units = n; src.per_unit = std::max<int64_t>((int64_t)h->fq_maxlen, 1);
+        src.walk = [&](bool emit, const KtArgs &A, int64_t u0, int64_t u1) {
+            // queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
+            const int64_t per = std::max<int64_t>(KMER_MAX_WINDOWS / src.per_unit, 1);
+            with_bool(canon, [&](auto C) {
+                with_bool(emit, [&](auto E) {
+                    for (int64_t q0 = u0; q0 < u1; q0 += per) {
+                        const int64_t q1 = std::min(q0 + per, u1);
+                        FX_LAUNCH(h, E() ? K_KT_EMIT : K_KT_HIST, (k_kt_fastq<C(), E()>), dim3(lane_group_grid<k_kt_fastq<C(), E()>>(h, q1 - q0, q.lpr)), dim3(BLOCK),
+                                  v.data, v.base, v.n, v.rlen, v.soff, d_ids, q0, q1, d_start, d_end, q.lpr, (int)k, A);
+                    }
+                });
+            });
+        };
+        if ((rc = kmer_table_run(h, k, min_count, max_bytes, src, out, n_windows, n_parts))) return rc;
+    }
+    return kmer_table_done(out, codes, counts, n_distinct);
 }
 
 // ------------------------------------------------------------- names

@@ -1,7 +1,8 @@
 """k-mer spectra of the resident FASTA and FASTQ streams (extension; the reference counts single letters only).
 
 Fasta.kmer_counts / kmer_profile and Fastq.kmer_counts check their arguments here and hand them to fx_fasta_kmers and
-fx_fastq_kmers (csrc/fx_kmer.hpp).  The definition -- alphabet, code of a window, canonical form -- is written down in
+fx_fastq_kmers (csrc/fx_kmer.hpp); Fasta.kmer_table and Fastq.kmer_table (1 <= k <= 31, the codes that occur with their
+counts: a KmerTable) go to fx_fasta_kmer_table and fx_fastq_kmer_table (csrc/fx_kmer_table.hpp).  The definition -- alphabet, code of a window, canonical form -- is written down in
 include/fxgpu.h and, as plain Python, in tests/kmer_truth.py."""
 import numpy as np
 
@@ -9,6 +10,7 @@ from . import _lib, trim
 
 MAX_K = 13                # the dense table is 8 * 4**k bytes: 512 MiB at k = 13
 MAX_PROFILE_K = 6         # one row per record
+MAX_TABLE_K = 31          # the sparse table: a code has 2k <= 62 bits, an exact non-negative int64
 
 
 def check_k(k, hi=MAX_K):
@@ -71,3 +73,107 @@ def fastq_counts_blob(blob, n_reads, k, canonical=False, ids=None, start=None, e
         if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
             raise ValueError("the interval of query %d lies outside its read" % e.first_bad)
         raise
+
+
+# ------------------------------------------------------------------ sparse tables (1 <= k <= 31)
+def _check_int(v, name, lo):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError("%s must be an int" % name)
+    if int(v) < lo:
+        raise ValueError("%s %d below %d" % (name, int(v), lo))
+    return int(v)
+
+
+def check_table(k, min_count=1, max_bytes=None):
+    """The arguments of kmer_table -> (k, min_count, max_bytes as the library takes it: 0 for the default)."""
+    k = check_k(k, MAX_TABLE_K)
+    min_count = _check_int(min_count, "min_count", 1)
+    max_bytes = 0 if max_bytes is None else _check_int(max_bytes, "max_bytes", 1 << 20)
+    return k, min_count, max_bytes
+
+
+_LETTER = np.full(256, -1, dtype=np.int64)
+for _j, _c in enumerate("ACGT"):
+    _LETTER[ord(_c)] = _LETTER[ord(_c.lower())] = _j
+
+
+def kmer_code(s, k):
+    """The code of a k-letter string; ValueError for another length or a letter outside ACGTacgt."""
+    if isinstance(s, str):
+        s = s.encode("latin-1", "replace")
+    d = _LETTER[np.frombuffer(bytes(s), dtype=np.uint8)]
+    if d.size != k:
+        raise ValueError("a k-mer of %d letters where k is %d" % (d.size, k))
+    if (d < 0).any():
+        raise ValueError("a k-mer holds letters of ACGTacgt only")
+    code = 0
+    for x in d.tolist():
+        code = code * 4 + x
+    return code
+
+
+class KmerTable:
+    """The k-mers that occur in a selection: codes (int64, ascending, canonical ones only where canonical) and their counts
+    (int64); n_windows = valid windows of the selection before min_count, n_parts = sort-and-reduce rounds the call took."""
+
+    def __init__(self, k, canonical, codes, counts, n_windows=None, n_parts=0):
+        self.k = int(k)
+        self.canonical = bool(canonical)
+        self.codes = np.asarray(codes, dtype=np.int64)
+        self.counts = np.asarray(counts, dtype=np.int64)
+        self.n_windows = int(self.counts.sum()) if n_windows is None else int(n_windows)
+        self.n_parts = int(n_parts)
+
+    def __len__(self):
+        return int(self.codes.size)
+
+    def __repr__(self):
+        return "<KmerTable k=%d%s: %d distinct of %d windows>" % (self.k, " canonical" if self.canonical else "", len(self), self.n_windows)
+
+    def count(self, x):
+        """How often a k-mer occurs: x a k-letter string or a code -> int; an array of codes -> int64 array.  0 where it is
+        absent.  On a canonical table the query is folded to its canonical code first."""
+        scalar = isinstance(x, (str, bytes, bytearray, int, np.integer)) and not isinstance(x, bool)
+        q = kmer_code(x, self.k) if isinstance(x, (str, bytes, bytearray)) else x
+        q = np.atleast_1d(np.asarray(q, dtype=np.int64))
+        if self.canonical:
+            q = np.minimum(q, revcomp_code(q, self.k))
+        at = np.searchsorted(self.codes, q)
+        inside = at < self.codes.size
+        at = np.where(inside, at, 0)
+        out = np.zeros(q.shape, dtype=np.int64)
+        if self.codes.size:
+            hit = inside & (self.codes[at] == q)
+            out[hit] = self.counts[at[hit]]
+        return int(out[0]) if scalar else out
+
+    def spectrum(self):
+        """int64 array whose entry c is the number of distinct k-mers that occur c times (entry 0 is 0)."""
+        if not self.counts.size:
+            return np.zeros(1, dtype=np.int64)
+        return np.bincount(self.counts).astype(np.int64)
+
+    def strings(self, lo=0, hi=None):
+        """The letters of the entries [lo, hi) of the table."""
+        return [kmer_string(c, self.k) for c in self.codes[lo:hi].tolist()]
+
+
+def fasta_table_blob(blob, k, canonical=False, ids=None, min_count=1, max_bytes=None):
+    """The table of the records `ids` (int64 ids or None) of a Blob whose FASTA table is resident -> KmerTable."""
+    k, min_count, max_bytes = check_table(k, min_count, max_bytes)
+    codes, counts, nw, parts = blob.fasta_kmer_table(k, bool(canonical), ids, min_count, max_bytes)
+    return KmerTable(k, canonical, codes, counts, nw, parts)
+
+
+def fastq_table_blob(blob, n_reads, k, canonical=False, ids=None, start=None, end=None, min_count=1, max_bytes=None):
+    """The table of seq[start:end] of the reads `ids`; ids, start and end by the rules of Fastq.records -> KmerTable."""
+    k, min_count, max_bytes = check_table(k, min_count, max_bytes)
+    ids = trim.check_ids(ids, n_reads)
+    start, end = trim.check_intervals(start, end, n_reads if ids is None else ids.size)
+    try:
+        codes, counts, nw, parts = blob.fastq_kmer_table(k, bool(canonical), ids, start, end, min_count, max_bytes)
+    except _lib.FxError as e:
+        if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
+            raise ValueError("the interval of query %d lies outside its read" % e.first_bad)
+        raise
+    return KmerTable(k, canonical, codes, counts, nw, parts)
