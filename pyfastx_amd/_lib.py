@@ -50,7 +50,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -236,6 +236,12 @@ def lib():
     L.fx_fastq_kmers.argtypes = [vp, i32, i32, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(i64)]
     L.fx_fasta_kmer_table.argtypes = [vp, i32, i32, vp, i64, i64, i64] + [C.POINTER(vp)] * 2 + [C.POINTER(i64)] * 4
     L.fx_fastq_kmer_table.argtypes = [vp, i32, i32, vp, i64, vp, vp, i64, i64] + [C.POINTER(vp)] * 2 + [C.POINTER(i64)] * 4
+    L.fx_kmer_set_create.argtypes = [vp, i32, i32, vp, i64, C.POINTER(vp)]
+    L.fx_kmer_set_free.argtypes = [vp]
+    L.fx_kmer_set_contains.argtypes = [vp, vp, i64, vp]
+    L.fx_fastq_kmer_hits.argtypes = [vp, vp, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_kmer_screen.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fasta_kmer_hits.argtypes = [vp, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_names_build.argtypes = [vp, i32]
     L.fx_names_lookup.argtypes = [vp, i32, i64, vp, vp, vp]
     L.fx_revcomp.argtypes = [i32, i32, vp, i64, i32]
@@ -474,6 +480,38 @@ class Comm:
 
 KSEQ_REC = np.dtype([("hdr_off", "<i8"), ("hdr_line", "<i8"), ("seq_len", "<i8"), ("seq_cum", "<i8"),
                      ("hdr_len", "<u4"), ("s_n", "<u4"), ("q_n", "<u4"), ("flags", "<u4")])
+
+
+class KmerSet:
+    """Owning wrapper of an fx_kmer_set: a hash set of k-mer codes in device memory, created through a blob of its device and
+    independent of it afterwards."""
+
+    def __init__(self, blob, k, canonical, codes):
+        codes = np.ascontiguousarray(codes, dtype=np.int64)
+        s = C.c_void_p()
+        check(lib().fx_kmer_set_create(blob._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(codes) if codes.size else None, codes.size, C.byref(s)))
+        self._s, self.k, self.canonical, self.n = s, int(k), bool(canonical), int(codes.size)
+
+    def contains(self, codes):
+        """uint8 array: 1 where the code is in the set as given (fx_kmer_set_contains)."""
+        codes = np.ascontiguousarray(codes, dtype=np.int64)
+        out = np.zeros(codes.size, dtype=np.uint8)
+        if self._s is None:
+            raise FxError(FX_ESTATE, "the k-mer set has been freed")
+        if codes.size:
+            check(lib().fx_kmer_set_contains(self._s, _ptr(codes), codes.size, _ptr(out)))
+        return out.reshape(codes.shape)
+
+    def close(self):
+        if self._s:
+            lib().fx_kmer_set_free(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Blob:
@@ -1189,6 +1227,49 @@ class Blob:
             start = end = None                                 # no query, no interval
         head = (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, _ptr(start), _ptr(end))
         return self._kmer_table(lib().fx_fastq_kmer_table, head, min_count, max_bytes)
+
+    def kmer_set(self, k, canonical, codes):
+        """A device k-mer set of `codes` on this blob's device (fx_kmer_set_create) -> KmerSet; any blob of the device may use it."""
+        return KmerSet(self, k, canonical, codes)
+
+    def _kmer_hits(self, call, head, dtype):
+        pw, ph, n, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(-1)
+        rc = call(*head, C.byref(pw), C.byref(ph), C.byref(n), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(n.value)
+        return pinned_array(pw.value, max(m, 1), dtype)[:m], pinned_array(ph.value, max(m, 1), dtype)[:m]
+
+    def _fastq_queries(self, ids, start, end):
+        buf, n_ids, _ = self._kmer_ids(ids)
+        start = None if start is None else self._i64(start)
+        end = None if end is None else self._i64(end)
+        if start is not None and start.size == 0:
+            start = end = None                                 # no query, no interval
+        return (_ptr(buf), n_ids, _ptr(start), _ptr(end)), (buf, start, end)
+
+    def fastq_kmer_hits(self, kset, ids=None, start=None, end=None):
+        """Per query the valid windows of seq[start:end] and how many of them are in `kset` (fx_fastq_kmer_hits) ->
+        (n_windows, n_hits), int32 in pinned memory.  A bad id or interval raises FxError(FX_ERANGE) with .first_bad."""
+        q, keep = self._fastq_queries(ids, start, end)
+        return self._kmer_hits(lib().fx_fastq_kmer_hits, (self._h, kset._s) + q, np.int32)
+
+    def fastq_kmer_screen(self, kset, ids=None, start=None, end=None, min_hits=1, frac=(0, 0), invert=False):
+        """The ascending positions of the queries whose hits pass min_hits and the ratio frac = (num, den) (fx_fastq_kmer_screen;
+        den 0: not asked) -> int64 in pinned memory."""
+        q, keep = self._fastq_queries(ids, start, end)
+        p, n, bad = C.c_void_p(), C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_kmer_screen(self._h, kset._s, *q, int(min_hits), int(frac[0]), int(frac[1]), 1 if invert else 0,
+                                        C.byref(p), C.byref(n), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(n.value)
+        return pinned_array(p.value, max(m, 1), np.int64)[:m]
+
+    def fasta_kmer_hits(self, kset, ids=None):
+        """Per selected record the valid windows and the hits in `kset` (fx_fasta_kmer_hits) -> (n_windows, n_hits), int64."""
+        buf, n_ids, _ = self._kmer_ids(ids)
+        return self._kmer_hits(lib().fx_fasta_kmer_hits, (self._h, kset._s, _ptr(buf), n_ids), np.int64)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)

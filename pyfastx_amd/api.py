@@ -865,6 +865,18 @@ class Fasta(_fxobj.FastaCore):
         sel = None if ids is None else self._ids_of(ids)
         return kmer.fasta_table_blob(self._search_blob(), k, canonical, sel, min_count, max_bytes)
 
+    def kmer_hits(self, table, ids=None):
+        """Extension: per record, how many of the k-mers of its `seq` occur in `table` (a kmer.KmerTable: another assembly's
+        kmer_table, KmerTable.from_strings of a primer list, ...) -> (n_windows, n_hits), int64 arrays in pinned memory, one
+        row per id (names or 0-based ids, a record listed twice has two rows; None: every record).  k and the canonical form
+        are the table's; windows are those of kmer_table; a window that occurs twice counts twice.  n_hits / n_windows is the
+        containment index of the record in the table's source.  The table's codes become a hash set in device memory on
+        first use (csrc/fx_kmer_screen.hpp), kept on the table until it is collected or table.release()."""
+        from . import kmer
+        kmer.check_screen_table(table)
+        sel = None if ids is None else self._ids_of(ids)
+        return kmer.fasta_hits_blob(self._search_blob(), self._st.device, table, sel)
+
     def kmer_profile(self, k, canonical=False, ids=None, max_bytes=1 << 30):
         """Extension: one k-mer spectrum per record -> int64[n_sel, 4**k] in pinned memory, rows in the order of ids (all
         records in file order when None); the definition is kmer_counts'.  1 <= k <= 6; rows that would take more than
@@ -1938,6 +1950,28 @@ class Fastq(_fxobj.FastqCore):
         from . import kmer
         kmer.check_table(k, min_count, max_bytes)
         return kmer.fastq_table_blob(self._qc_blob(), self._rlen_host.size, k, canonical, ids, start, end, min_count, max_bytes)
+
+    def kmer_hits(self, table, ids=None, start=None, end=None):
+        """Extension: per query, the valid k-mer windows of seq[start:end] and how many of them occur in `table` (a
+        kmer.KmerTable of a contaminant, adapter list, rRNA set, ...: k and the canonical form are the table's) ->
+        (n_windows, n_hits), int32 arrays in pinned memory; ids / start / end follow kmer_counts.  A window that occurs twice
+        counts twice.  The table's codes become a hash set in device memory on first use (csrc/fx_kmer_screen.hpp), kept on
+        the table until it is collected or table.release()."""
+        from . import kmer
+        kmer.check_screen_table(table)
+        return kmer.fastq_hits_blob(self._qc_blob(), self._st.device, self._rlen_host.size, table, ids, start, end)
+
+    def screen(self, table, min_hits=1, min_frac=None, invert=False, ids=None, start=None, end=None):
+        """Extension: the k-mer filter -- the ascending positions (int64, pinned memory) of the queries with at least min_hits
+        windows in `table` and, where min_frac (0..1) is given, at least that share of their valid windows (taken as a
+        fraction with a denominator <= 1000 and compared in integers on the device; a query without windows passes it);
+        invert=True returns the others instead.  The columns of kmer_hits stay on the device.  With ids=None the positions
+        are read ids: fq.write(path, ids=fq.screen(phix, invert=True)) drops the contaminated reads; with trimmed intervals
+        index ids, start and end with them."""
+        from . import kmer
+        kmer.check_screen_table(table)
+        kmer.check_screen(min_hits, min_frac, invert)
+        return kmer.fastq_screen_blob(self._qc_blob(), self._st.device, self._rlen_host.size, table, min_hits, min_frac, invert, ids, start, end)
 
     def records(self, ids=None, start=None, end=None, min_len=0):
         """Extension: four-line FASTQ records of the reads `ids` (None: every read), cut to [start, end) -- what trim returned

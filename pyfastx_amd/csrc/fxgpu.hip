@@ -47,6 +47,7 @@
 #include "fx_fastq_trim.hpp"
 #include "fx_kmer.hpp"
 #include "fx_kmer_table.hpp"
+#include "fx_kmer_screen.hpp"
 
 using namespace fx;
 
@@ -323,10 +324,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen"};
 
 struct Prof {
     bool on = false;
@@ -365,6 +366,12 @@ struct Prof {
     do {                                                                          \
         (h)->prof.begin(id, (h)->stream);                                         \
         hipLaunchKernelGGL(kern, grid, block, 0, (h)->stream, __VA_ARGS__);       \
+        (h)->prof.end((h)->stream);                                               \
+    } while (0)
+#define FX_LAUNCH_LDS(h, id, kern, grid, block, lds, ...)                         \
+    do {                                                                          \
+        (h)->prof.begin(id, (h)->stream);                                         \
+        hipLaunchKernelGGL(kern, grid, block, lds, (h)->stream, __VA_ARGS__);     \
         (h)->prof.end((h)->stream);                                               \
     } while (0)
 
@@ -4511,6 +4518,252 @@ extern "C" int fx_fastq_kmer_table(fx_handle *h, int32_t k, int flags, const int
         if ((rc = kmer_table_run(h, k, min_count, max_bytes, src, out, n_windows, n_parts))) return rc;
     }
     return kmer_table_done(out, codes, counts, n_distinct);
+}
+
+// ------------------------------------------------------------------ k-mer screening (fx_kmer_screen.hpp)
+struct fx_kmer_set {
+    int device = 0, k = 0, flags = 0, log2 = KS_MIN_LOG2;
+    int64_t n = 0;                                           // codes given at creation, duplicates included
+    uint64_t *slots = nullptr;
+    hipStream_t stream = nullptr;                            // fx_kmer_set_contains runs on it: the set needs no handle after its creation
+    KsView view() const { return KsView{slots, log2}; }
+    bool in_lds() const { return log2 <= KS_LDS_LOG2; }
+    size_t lds_bytes() const { return in_lds() ? (size_t)8 << log2 : 0; }
+};
+
+extern "C" int fx_kmer_set_free(fx_kmer_set *set) {
+    if (!set) return FX_OK;
+    (void)hipSetDevice(set->device);
+    if (set->stream) { (void)hipStreamSynchronize(set->stream); (void)hipStreamDestroy(set->stream); }
+    if (set->slots) (void)hipFree(set->slots);
+    delete set;
+    return FX_OK;
+}
+
+extern "C" int fx_kmer_set_create(fx_handle *h, int32_t k, int flags, const int64_t *codes, int64_t n, fx_kmer_set **set) {
+    if (!h || !set) return fail(FX_EINVAL, "null argument");
+    *set = nullptr;
+    if (n < 0 || n > KS_MAX_KEYS || (n > 0 && !codes)) return fail(FX_EINVAL, "%lld codes: outside 0..2^31, or a null array", (long long)n);
+    if (flags & ~FX_KMER_CANONICAL) return fail(FX_EINVAL, "unknown flag bits %d", flags);
+    if (k < 1 || k > KT_MAX_K) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, KT_MAX_K);
+    int rc = use_device(h);
+    if (rc) return rc;
+    struct Drop { void operator()(fx_kmer_set *s) const { (void)fx_kmer_set_free(s); } };
+    std::unique_ptr<fx_kmer_set, Drop> s(new fx_kmer_set());
+    s->device = h->device; s->k = k; s->flags = flags; s->n = n;
+    while (((int64_t)1 << s->log2) < 2 * n) ++s->log2;
+    const int64_t slots = (int64_t)1 << s->log2;
+    HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    Staged st(h);
+    ScratchBuf<int64_t> d_codes;
+    if (n > 0) {                                             // every code is looked at before anything is kept
+        if ((rc = d_codes.alloc(h->device, n, h->stream))) return rc;
+        HIPCHK(hipMemcpyAsync(d_codes.p, codes, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+        BadFlag bad;
+        if ((rc = bad.arm(h, st))) return rc;
+        FX_LAUNCH(h, K_KS_INSERT, k_ks_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)d_codes.p, n, (int)k, flags & FX_KMER_CANONICAL, bad.d);
+        HIPCHK(hipGetLastError());
+        int64_t first = -1;
+        if ((rc = bad.read(h, &first))) return rc;
+        if (first >= 0)
+            return fail(FX_EINVAL, "code %lld at position %lld lies outside [0, 4^%d)%s", (long long)codes[first], (long long)first, (int)k,
+                        flags & FX_KMER_CANONICAL ? " or is not canonical" : "");
+    }
+    if (dev_malloc((void **)&s->slots, (size_t)slots * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        s->slots = nullptr;
+        return fail(FX_ENOMEM, "%lld bytes of device memory for a k-mer set of %lld codes", (long long)(slots * 8), (long long)n);
+    }
+    HIPCHK(hipMemsetAsync(s->slots, 0xFF, (size_t)slots * 8, h->stream));
+    if (n > 0)
+        FX_LAUNCH(h, K_KS_INSERT, k_ks_insert, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)d_codes.p, n, (unsigned long long *)s->slots, s->log2);
+    if ((rc = home(h, "k-mer set", {}))) return rc;
+    *set = s.release();
+    return FX_OK;
+}
+
+extern "C" int fx_kmer_set_contains(fx_kmer_set *set, const int64_t *codes, int64_t n, uint8_t *out) {
+    if (!set || n < 0 || (n > 0 && (!codes || !out))) return fail(FX_EINVAL, "null argument");
+    if (n == 0) return FX_OK;
+    HIPCHK(hipSetDevice(set->device));
+    int rc;
+    ScratchBuf<int64_t> d_codes;
+    ScratchBuf<uint8_t> d_out;
+    if ((rc = d_codes.alloc(set->device, n, set->stream)) || (rc = d_out.alloc(set->device, n, set->stream))) return rc;
+    HIPCHK(hipMemcpyAsync(d_codes.p, codes, (size_t)n * 8, hipMemcpyHostToDevice, set->stream));
+    hipLaunchKernelGGL(k_ks_contains, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, set->stream, set->view(), set->k, (const int64_t *)d_codes.p, n, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out.p, (size_t)n, hipMemcpyDeviceToHost, set->stream));
+    HIPCHK(hipStreamSynchronize(set->stream));
+    return FX_OK;
+}
+
+// The grid of a walk that strides: `want` workgroups, at most the ones resident with `lds` bytes of dynamic LDS each.
+template <class K> static unsigned ks_grid(fx_handle *h, K kern, size_t lds, int64_t want) {
+    int per_cu = 0, n_cu = 256;
+    if (lds && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BLOCK, lds) != hipSuccess || per_cu <= 0) per_cu = 2;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
+    return (unsigned)std::min<int64_t>(want, (int64_t)per_cu * std::max(n_cu, 1));
+}
+
+// What the two FASTQ entries check, in the order of fx_fastq_kmer_table.
+static int ks_fastq_args(fx_handle *h, const fx_kmer_set *set, const int64_t *ids, int64_t n_ids, int64_t *first_bad, FqLaunch *q) {
+    int rc = fq_prepare(h, 0, 0, q);                           // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+    if (rc) return rc;
+    if (set->device != h->device) return fail(FX_EINVAL, "the k-mer set lives on device %d, the handle on device %d", set->device, h->device);
+    return check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
+}
+
+// n_windows / n_hits of n > 0 queries on the device: two int32 columns of one block, each from a 256-byte boundary.
+struct KsCols {
+    ScratchBuf<int32_t> dev;
+    int32_t *nw = nullptr, *nh = nullptr;
+};
+static int ks_fastq_run(fx_handle *h, const fx_kmer_set *set, Staged &st, const FqLaunch &q, const int64_t *ids, int64_t n, const int64_t *start,
+                        const int64_t *end, int64_t *first_bad, KsCols &o) {
+    int rc;
+    st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
+    const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
+    if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+    const FqView v = fq_view(h);
+    if (start) {
+        BadFlag bad;
+        if ((rc = bad.arm(h, st))) return rc;
+        FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, d_ids, n, d_start, d_end, bad.d);
+        HIPCHK(hipGetLastError());
+        if ((rc = bad.read(h, first_bad))) return rc;
+        if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
+    }
+    const int64_t stride = (n + 63) & ~(int64_t)63;
+    if ((rc = o.dev.alloc(h->device, 2 * stride, h->stream))) return rc;
+    o.nw = o.dev.p; o.nh = o.dev.p + stride;
+    const KsView S = set->view();
+    const size_t lds = set->lds_bytes();
+    const int k = set->k, lpr = q.lpr;
+    with_bool(set->flags & FX_KMER_CANONICAL, [&](auto C) {
+        with_bool(set->in_lds(), [&](auto L) {
+            auto kern = k_ks_fastq<C(), L()>;
+            FX_LAUNCH_LDS(h, K_KS_FASTQ, kern, dim3(ks_grid(h, kern, lds, nblocks(n, lane_groups(lpr)))), dim3(BLOCK), lds, v.data, v.base, v.n, v.rlen,
+                          v.soff, d_ids, n, d_start, d_end, lpr, k, S, o.nw, o.nh);
+        });
+    });
+    HIPCHK(hipGetLastError());
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_kmer_hits(fx_handle *h, const fx_kmer_set *set, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                                  int32_t **n_windows, int32_t **n_hits, int64_t *n_rows, int64_t *first_bad) {
+    if (!h || !set || !n_windows || !n_hits || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    *n_windows = *n_hits = nullptr; *n_rows = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    FqLaunch q;
+    int rc = ks_fastq_args(h, set, ids, n_ids, first_bad, &q);
+    if (rc) return rc;
+    const int64_t n = ids ? n_ids : h->n_reads;
+    PinnedOut<2> out(h);
+    auto pinned = [&] { return out.alloc(0, std::max<int64_t>(n, 1) * 4) && out.alloc(1, std::max<int64_t>(n, 1) * 4); };
+    if (n > 0) {
+        Staged st(h);
+        KsCols o;
+        if ((rc = ks_fastq_run(h, set, st, q, ids, n, start, end, first_bad, o))) return rc;
+        if (!pinned()) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n);
+        if ((rc = home(h, "k-mer hits", {{out.p[0], o.nw, n * 4}, {out.p[1], o.nh, n * 4}}))) return rc;
+    } else if (!pinned()) return fail(FX_ENOMEM, "pinned blocks");
+    out.release(n_windows, n_hits);
+    *n_rows = n;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_kmer_screen(fx_handle *h, const fx_kmer_set *set, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                                    int64_t min_hits, int64_t frac_num, int64_t frac_den, int invert, int64_t **pos, int64_t *n_pos, int64_t *first_bad) {
+    if (!h || !set || !pos || !n_pos || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    *pos = nullptr; *n_pos = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    const int64_t lim = 1000000000ll;
+    if (min_hits < 0) return fail(FX_EINVAL, "min_hits %lld below 0", (long long)min_hits);
+    if (frac_num < 0 || frac_num > lim || frac_den < 0 || frac_den > lim) return fail(FX_EINVAL, "a ratio outside 0..10^9");
+    FqLaunch q;
+    int rc = ks_fastq_args(h, set, ids, n_ids, first_bad, &q);
+    if (rc) return rc;
+    const int64_t n = ids ? n_ids : h->n_reads;
+    int64_t total = 0;
+    PinnedOut<1> out(h);
+    if (n > 0) {
+        Staged st(h);
+        KsCols o;
+        ScratchBuf<uint8_t> pass;
+        int64_t *sums = nullptr, *d_tot = nullptr;
+        if ((rc = ks_fastq_run(h, set, st, q, ids, n, start, end, first_bad, o))) return rc;
+        if ((rc = pass.alloc(h->device, n, h->stream)) || (rc = st.scratch<int64_t>(1, &d_tot))) return rc;
+        FX_LAUNCH(h, K_KS_SCREEN, k_ks_pass, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int32_t *)o.nw, (const int32_t *)o.nh, n, min_hits, frac_num, frac_den,
+                  invert, pass.p);
+        // the chunk offsets and the total; k_fq_select_emit applies the offsets itself
+        if ((rc = sscan<1>(h, st, K_KS_SCREEN, QcLdPass{pass.p}, n, nullptr, d_tot, &sums)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
+        if (!out.alloc(0, std::max<int64_t>(total, 1) * 8)) return fail(FX_ENOMEM, "pinned block for %lld positions", (long long)total);
+        if (total == 0) h->prof.drain();
+        else {
+            ScratchBuf<int64_t> dev;
+            if ((rc = dev.alloc(h->device, total, h->stream))) return rc;
+            FX_LAUNCH(h, K_KS_SCREEN, k_fq_select_emit, dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, dev.p);
+            if ((rc = home(h, "screen emit", {{out.p[0], dev.p, total * 8}}))) return rc;
+        }
+    } else if (!out.alloc(0, 8)) return fail(FX_ENOMEM, "pinned block");
+    out.release(pos);
+    *n_pos = total;
+    return FX_OK;
+}
+
+extern "C" int fx_fasta_kmer_hits(fx_handle *h, const fx_kmer_set *set, const int64_t *ids, int64_t n_ids, int64_t **n_windows, int64_t **n_hits,
+                                  int64_t *n_rows, int64_t *first_bad) {
+    if (!h || !set || !n_windows || !n_hits || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
+    *n_windows = *n_hits = nullptr; *n_rows = 0; *first_bad = -1;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
+    if (set->device != h->device) return fail(FX_EINVAL, "the k-mer set lives on device %d, the handle on device %d", set->device, h->device);
+    int rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, first_bad, kBadRecord);
+    if (rc) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    PinnedOut<2> out(h);
+    if (!out.alloc(0, std::max<int64_t>(n_sel, 1) * 8) || !out.alloc(1, std::max<int64_t>(n_sel, 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n_sel);
+    if (n_sel > 0) {
+        Staged st(h);
+        st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+        const int k = set->k;
+        SearchPlan P;
+        P.masks = nullptr;
+        int64_t *d_tot = nullptr, n_runs = 0;
+        if ((rc = fasta_run_plan(h, st, K_KMER_SCAN, ids, n_ids, k, &P, &d_tot, &n_runs))) return rc;
+        ScratchBuf<unsigned long long> acc;                  // a (windows, hits) pair per row
+        ScratchBuf<int64_t> cols, K;
+        ScratchBuf<uint32_t> packed;
+        if ((rc = acc.alloc(h->device, 2 * n_sel, h->stream)) || (rc = cols.alloc(h->device, 2 * n_sel, h->stream))) return rc;
+        HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_sel * 16, h->stream));
+        if (n_runs > 0) {
+            // the kept bytes of every run and their scan: the cut at slen is known before the first window is looked up
+            if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
+            FX_LAUNCH(h, K_KT_KEPT, k_kt_kept, dim3(nblocks(n_runs, BLOCK)), dim3(BLOCK), P, packed.p);
+            if ((rc = sscan<1>(h, st, K_KMER_SCAN, SrchLdKept{packed.p}, n_runs, K.p, d_tot))) return rc;
+            const KsView S = set->view();
+            const size_t lds = set->lds_bytes();
+            with_bool(set->flags & FX_KMER_CANONICAL, [&](auto C) {
+                with_bool(set->in_lds(), [&](auto L) {
+                    auto kern = k_ks_fasta<C(), L()>;
+                    FX_LAUNCH_LDS(h, K_KS_FASTA, kern, dim3(ks_grid(h, kern, lds, nblocks(n_runs, BLOCK))), dim3(BLOCK), lds, P, k, (const int64_t *)K.p, S, acc.p);
+                });
+            });
+        }
+        FX_LAUNCH(h, K_KS_FASTA, k_ks_split, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), (const unsigned long long *)acc.p, n_sel, cols.p, cols.p + n_sel);
+        if ((rc = home(h, "k-mer hits", {{out.p[0], cols.p, n_sel * 8}, {out.p[1], cols.p + n_sel, n_sel * 8}}))) return rc;
+    }
+    out.release(n_windows, n_hits);
+    *n_rows = n_sel;
+    return FX_OK;
 }
 
 // ------------------------------------------------------------- names

@@ -123,6 +123,40 @@ class KmerTable:
         self.counts = np.asarray(counts, dtype=np.int64)
         self.n_windows = int(self.counts.sum()) if n_windows is None else int(n_windows)
         self.n_parts = int(n_parts)
+        self._sets = {}                                        # device -> _lib.KmerSet of the codes, made by the first screen there
+
+    @classmethod
+    def from_strings(cls, seqs, k, canonical=False):
+        """The table of the windows of the strings `seqs` (str or bytes; one alone counts as a list of one), computed on the
+        host by the definition of this module: letters outside ACGTacgt break windows, a string shorter than k has none.  An
+        adapter or primer list becomes a table without a file."""
+        k = check_k(k, MAX_TABLE_K)
+        if isinstance(seqs, (str, bytes, bytearray)):
+            seqs = [seqs]
+        found = [np.zeros(0, dtype=np.int64)]
+        for s in seqs:
+            if isinstance(s, str):
+                s = s.encode("latin-1", "replace")
+            d = _LETTER[np.frombuffer(bytes(s), dtype=np.uint8)]
+            n = d.size - k + 1
+            if n <= 0:
+                continue
+            code = np.zeros(n, dtype=np.int64)
+            bad = np.zeros(n, dtype=bool)
+            for j in range(k):
+                w = d[j:j + n]
+                bad |= w < 0
+                code = code * 4 + (w & 3)
+            code = code[~bad]
+            found.append(np.minimum(code, revcomp_code(code, k)) if canonical else code)
+        codes, counts = np.unique(np.concatenate(found), return_counts=True)
+        return cls(k, canonical, codes, counts.astype(np.int64), n_parts=0)
+
+    def release(self):
+        """Free the device sets the screens of this table have made (they are freed with the table otherwise)."""
+        for s in self._sets.values():
+            s.close()
+        self._sets = {}
 
     def __len__(self):
         return int(self.codes.size)
@@ -177,3 +211,75 @@ def fastq_table_blob(blob, n_reads, k, canonical=False, ids=None, start=None, en
             raise ValueError("the interval of query %d lies outside its read" % e.first_bad)
         raise
     return KmerTable(k, canonical, codes, counts, nw, parts)
+
+
+# ------------------------------------------------------------------ screening against a table (csrc/fx_kmer_screen.hpp)
+SCREEN_LDS_KEYS = 4096    # a set of at most this many codes is probed in LDS (an image of at most 64 KiB), a larger one in global memory
+
+
+def check_screen_table(table):
+    """The table a screen runs against; anything that is no KmerTable: TypeError."""
+    if not isinstance(table, KmerTable):
+        raise TypeError("a kmer.KmerTable is needed (Fasta.kmer_table, Fastq.kmer_table, KmerTable.from_strings), not %s" % type(table).__name__)
+    return table
+
+
+def check_screen(min_hits=1, min_frac=None, invert=False):
+    """The criteria of Fastq.screen as fx_fastq_kmer_screen takes them -> (min_hits, (numerator, denominator), invert);
+    min_frac None: (0, 0), the ratio is not asked; else a fraction in 0..1 by the rule of qc.as_ratio."""
+    from . import qc
+    if isinstance(min_hits, bool) or not isinstance(min_hits, (int, np.integer)):
+        raise ValueError("min_hits must be an int")
+    if int(min_hits) < 0:
+        raise ValueError("min_hits %d is negative" % int(min_hits))
+    frac = (0, 0)
+    if min_frac is not None:
+        frac = qc.as_ratio(min_frac, "min_frac")
+        if frac[0] > frac[1]:
+            raise ValueError("min_frac %r outside 0..1" % (min_frac,))
+    return int(min_hits), frac, bool(invert)
+
+
+def device_set(table, blob, device):
+    """The device k-mer set of a table on `device`: created through `blob` on first use, kept on the table."""
+    check_screen_table(table)
+    s = table._sets.get(int(device))
+    if s is None:
+        s = table._sets[int(device)] = blob.kmer_set(table.k, table.canonical, table.codes)
+    return s
+
+
+def _range_error(e, what):
+    if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
+        return ValueError("the interval of query %d lies outside its %s" % (e.first_bad, what))
+    return e
+
+
+def fastq_hits_blob(blob, device, n_reads, table, ids=None, start=None, end=None):
+    """(n_windows, n_hits), int32, of seq[start:end] of the reads `ids` against the table; ids, start and end by the rules of
+    Fastq.records."""
+    check_screen_table(table)
+    ids = trim.check_ids(ids, n_reads)
+    start, end = trim.check_intervals(start, end, n_reads if ids is None else ids.size)
+    try:
+        return blob.fastq_kmer_hits(device_set(table, blob, device), ids, start, end)
+    except _lib.FxError as e:
+        raise _range_error(e, "read")
+
+
+def fastq_screen_blob(blob, device, n_reads, table, min_hits=1, min_frac=None, invert=False, ids=None, start=None, end=None):
+    """The ascending positions (int64) of the queries that pass the screen."""
+    check_screen_table(table)
+    min_hits, frac, invert = check_screen(min_hits, min_frac, invert)
+    ids = trim.check_ids(ids, n_reads)
+    start, end = trim.check_intervals(start, end, n_reads if ids is None else ids.size)
+    try:
+        return blob.fastq_kmer_screen(device_set(table, blob, device), ids, start, end, min_hits, frac, invert)
+    except _lib.FxError as e:
+        raise _range_error(e, "read")
+
+
+def fasta_hits_blob(blob, device, table, ids=None):
+    """(n_windows, n_hits), int64, one row per record of `ids` (int64 ids or None) of a Blob whose FASTA table is resident."""
+    check_screen_table(table)
+    return blob.fasta_kmer_hits(device_set(table, blob, device), ids)
