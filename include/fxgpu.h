@@ -509,6 +509,46 @@ int fx_fastq_kmer_screen(fx_handle *h, const fx_kmer_set *set, const int64_t *id
 int fx_fasta_kmer_hits(fx_handle *h, const fx_kmer_set *set, const int64_t *ids, int64_t n_ids,
                        int64_t **n_windows, int64_t **n_hits, int64_t *n_rows, int64_t *first_bad);
 
+/* ------------------------------------------------------------------ duplicate reads (extension)
+ * Exact duplicate detection on the resident FASTQ stream (pyfastx_amd/csrc/fx_fastq_dedup.hpp): what FastQC's duplication
+ * levels, `seqkit rmdup -s` or `fastp --dedup` answer, without a base leaving the device.  The reference has no counterpart.
+ * Queries.  ids, n_ids, start, end are those of fx_fastq_kmers, word for word: ids 0-based, in any order, repeats allowed;
+ * ids = NULL: every read (a non-NULL ids with n_ids = 0: no query); start and end both given or both NULL; row q of both
+ * belongs to query q; 0 <= start <= end <= rlen.
+ * The key of query q is the byte string s[a:b], s = the rlen bytes at soff (what fx_fastq_fetch returns), a = 0 and b = rlen
+ * unless start / end are given.  The bytes are taken as they are: case-sensitive, N and IUPAC codes are ordinary bytes.  The
+ * name and the quality line play no part.
+ * Duplicates.  Two queries are duplicates when their keys are equal as byte strings, lengths included; all empty keys are
+ * equal to one another, and a read listed twice in ids is a duplicate of its first listing.  FX_DUP_REVCOMP: two queries are
+ * duplicates when the key of one equals the key of the other or its reverse complement -- the key reversed, A<->T, C<->G,
+ * a<->t, c<->g, every other byte mapped to itself; that is: when min(key, rc(key)), compared as byte strings, is the same.
+ * first[q] is the smallest query position p whose key is a duplicate of q's: first[q] <= q, and first[q] == q exactly for the
+ * first occurrence of each group.  *n_groups = the number of groups.
+ * The answer is exact, not probabilistic: queries are grouped by a 64-bit fingerprint, and every member of a group of equal
+ * fingerprints is then compared with the group's first member byte by byte; the ones that differ (two keys, one fingerprint)
+ * go through another round under another seed.  *n_rounds = the rounds that ran (0 without a query, 1 in practice).
+ *   hash_bits    0: all 64 bits of the fingerprint; 1..64: only that many.  It exists so that tests can reach the collision
+ *                path.  No result depends on it, only *n_rounds does.
+ * fx_fastq_dup_first: *first, *n_rows = the number of queries.
+ * fx_fastq_dedup: the ascending positions among the queries of the first occurrences whose group has at least min_copies
+ *   (>= 1) and, unless max_copies < 0, at most max_copies members -- the read ids themselves when ids is NULL; *copies (the
+ *   pointer may be NULL: not wanted) = the members of the group of each.  first stays on the device; only the positions and
+ *   the copies come home.  *n_groups counts all groups, whatever min_copies / max_copies select.
+ * Outputs are pinned blocks of fx_pinned_alloc that belong to the caller (fx_pinned_free), never NULL after FX_OK.
+ * Errors: a null handle or output pointer (copies apart), start without end: FX_EINVAL, nothing touched; before
+ * fx_fastq_build: FX_ESTATE; a byte-range shard, unknown flag bits, hash_bits outside 0..64, min_copies < 1, more than 2^31
+ * queries (the sort carries 32-bit positions): FX_EINVAL; an id outside the table, or an interval outside 0 <= start <= end
+ * <= rlen: *first_bad = its position among the queries, FX_ERANGE, nothing allocated; device working memory (about 45 bytes
+ * per query, out of the library's scratch pool) not to be had: FX_ENOMEM; no device: FX_EDEVICE (there is no CPU path). */
+enum { FX_DUP_REVCOMP = 1 };
+int fx_fastq_dup_first(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                       int flags, int hash_bits, int64_t **first, int64_t *n_rows, int64_t *n_groups,
+                       int64_t *n_rounds, int64_t *first_bad);
+int fx_fastq_dedup(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                   int flags, int hash_bits, int64_t min_copies, int64_t max_copies,
+                   int64_t **pos, int64_t **copies, int64_t *n_pos, int64_t *n_groups, int64_t *n_rounds,
+                   int64_t *first_bad);
+
 /* ------------------------------------------------------------------ Fastx
  * Replaces kseq_read (kseq.c:138-179) as pyfastx_fastx_next drives it (fastx.c:124-130): index-free iteration over a
  * file with kseq's own record rules -- FASTA and FASTQ records mixed, sequence / quality over any number of lines,

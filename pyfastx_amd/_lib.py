@@ -14,6 +14,7 @@ FX_HOST, FX_DEVICE = 0, 1
 FX_UPPER, FX_REVERSE, FX_COMPLEMENT, FX_RAW = 1, 2, 4, 8
 FX_SEARCH_DEGENERATE, FX_SEARCH_UPPER, FX_SEARCH_PLUS, FX_SEARCH_MINUS = 1, 2, 4, 8
 FX_KMER_CANONICAL = 1
+FX_DUP_REVCOMP = 1
 FX_OK, FX_ENOENT, FX_EFORMAT, FX_EIO, FX_EDEVICE, FX_ENOMEM, FX_ERANGE, FX_EINVAL, FX_ESTATE = \
     0, -1, -2, -3, -4, -5, -6, -7, -8
 
@@ -50,7 +51,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -242,6 +243,9 @@ def lib():
     L.fx_fastq_kmer_hits.argtypes = [vp, vp, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_kmer_screen.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fasta_kmer_hits.argtypes = [vp, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_dup_first.argtypes = [vp, vp, i64, vp, vp, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_dedup.argtypes = [vp, vp, i64, vp, vp, i32, i32, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                 C.POINTER(i64)]
     L.fx_names_build.argtypes = [vp, i32]
     L.fx_names_lookup.argtypes = [vp, i32, i64, vp, vp, vp]
     L.fx_revcomp.argtypes = [i32, i32, vp, i64, i32]
@@ -1270,6 +1274,32 @@ class Blob:
         """Per selected record the valid windows and the hits in `kset` (fx_fasta_kmer_hits) -> (n_windows, n_hits), int64."""
         buf, n_ids, _ = self._kmer_ids(ids)
         return self._kmer_hits(lib().fx_fasta_kmer_hits, (self._h, kset._s, _ptr(buf), n_ids), np.int64)
+
+    def fastq_dup_first(self, ids=None, start=None, end=None, revcomp=False, hash_bits=0):
+        """first[q] = the smallest query position whose key seq[start:end] is a duplicate of query q's (fx_fastq_dup_first) ->
+        (first int64[n] in pinned memory, n_groups, n_rounds).  hash_bits: the fingerprint bits kept (0: 64); no result but
+        n_rounds depends on it.  A bad id or interval raises FxError(FX_ERANGE) with .first_bad."""
+        q, keep = self._fastq_queries(ids, start, end)
+        p, n, groups, rounds, bad = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_dup_first(self._h, *q, FX_DUP_REVCOMP if revcomp else 0, int(hash_bits), C.byref(p), C.byref(n), C.byref(groups),
+                                      C.byref(rounds), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(n.value)
+        return pinned_array(p.value, max(m, 1), np.int64)[:m], int(groups.value), int(rounds.value)
+
+    def fastq_dedup(self, ids=None, start=None, end=None, revcomp=False, hash_bits=0, min_copies=1, max_copies=-1, want_copies=False):
+        """The ascending positions of the first occurrences whose group has min_copies..max_copies members (fx_fastq_dedup;
+        max_copies < 0: not asked) -> (pos int64 in pinned memory, copies int64 or None, n_groups, n_rounds)."""
+        q, keep = self._fastq_queries(ids, start, end)
+        p, pc, n, groups, rounds, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_dedup(self._h, *q, FX_DUP_REVCOMP if revcomp else 0, int(hash_bits), int(min_copies), int(max_copies), C.byref(p),
+                                  C.byref(pc) if want_copies else None, C.byref(n), C.byref(groups), C.byref(rounds), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(n.value)
+        copies = pinned_array(pc.value, max(m, 1), np.int64)[:m] if want_copies else None
+        return pinned_array(p.value, max(m, 1), np.int64)[:m], copies, int(groups.value), int(rounds.value)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)

@@ -1973,6 +1973,31 @@ class Fastq(_fxobj.FastqCore):
         kmer.check_screen(min_hits, min_frac, invert)
         return kmer.fastq_screen_blob(self._qc_blob(), self._st.device, self._rlen_host.size, table, min_hits, min_frac, invert, ids, start, end)
 
+    def duplicates(self, ids=None, start=None, end=None, revcomp=False):
+        """Extension: exact duplicate detection on the GPU (csrc/fx_fastq_dedup.hpp) -> first, int64 in pinned memory, one row
+        per query: first[q] is the smallest query position whose key is a duplicate of query q's, so first[q] == q exactly for
+        the first occurrence of each group.  The key of a query is seq[start:end] as bytes -- case-sensitive, N an ordinary
+        byte, name and quality play no part --; two queries are duplicates when their keys are equal, with revcomp=True also
+        when one is the reverse complement of the other.  ids / start / end follow kmer_counts; a read listed twice in ids is
+        a duplicate of its first listing.  A bad id: IndexError; a bad argument: ValueError."""
+        from . import dedup
+        dedup.check_flag(revcomp, "revcomp")
+        return dedup.duplicates_blob(self._qc_blob(), self._rlen_host.size, ids, start, end, revcomp)[0]
+
+    def dedup(self, ids=None, start=None, end=None, revcomp=False, min_copies=1, max_copies=None, return_counts=False):
+        """Extension: duplicate removal -- the ascending positions (int64, pinned memory) of the first occurrence of every
+        group of duplicates (see duplicates) that has at least min_copies and, where given, at most max_copies members; with
+        return_counts=True -> (positions, copies), copies[k] = the members of the group of positions[k] (what
+        dedup.duplication_levels takes).  first stays on the device.  With ids=None the positions are read ids:
+        fq.write(path, ids=fq.dedup()) writes every distinct sequence once; with trimmed intervals index ids, start and end
+        with them, as for screen."""
+        from . import dedup
+        dedup.check_flag(revcomp, "revcomp")
+        dedup.check_flag(return_counts, "return_counts")
+        dedup.check_copies(min_copies, max_copies)
+        pos, copies, _, _ = dedup.dedup_blob(self._qc_blob(), self._rlen_host.size, ids, start, end, revcomp, min_copies, max_copies, return_counts)
+        return (pos, copies) if return_counts else pos
+
     def records(self, ids=None, start=None, end=None, min_len=0):
         """Extension: four-line FASTQ records of the reads `ids` (None: every read), cut to [start, end) -- what trim returned
         for the same ids; both None: whole reads -- formatted and laid out back to back on the GPU -> (uint8 buffer, int64

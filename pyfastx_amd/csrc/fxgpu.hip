@@ -48,6 +48,7 @@
 #include "fx_kmer.hpp"
 #include "fx_kmer_table.hpp"
 #include "fx_kmer_screen.hpp"
+#include "fx_fastq_dedup.hpp"
 
 using namespace fx;
 
@@ -324,10 +325,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select"};
 
 struct Prof {
     bool on = false;
@@ -4763,6 +4764,194 @@ extern "C" int fx_fasta_kmer_hits(fx_handle *h, const fx_kmer_set *set, const in
     }
     out.release(n_windows, n_hits);
     *n_rows = n_sel;
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ duplicate reads (fx_fastq_dedup.hpp)
+// The device working memory of a call, per query: two (fingerprint, index) buffers of the sort, the run rank and the heads'
+// indices, the unresolved flag, first, and -- where the group sizes are asked for -- copies and the per-run counter of
+// unresolved elements; the lists of the refinement rounds come when a round leaves something unresolved.
+struct DdWork {
+    ScratchBuf<uint64_t> key[2];
+    ScratchBuf<uint32_t> val[2], G, S, hist, totals, list[2], copies, unres;
+    ScratchBuf<uint8_t> flag;
+    ScratchBuf<int64_t> first, sums;
+    RadixScratch rs;
+    int64_t *d_tot = nullptr;
+    int alloc(fx_handle *h, Staged &st, int64_t n, bool want_copies) {
+        int rc;
+        const int dev = h->device;
+        hipStream_t s = h->stream;
+        rs.nblk = radix_tiles(n);
+        if ((rc = key[0].alloc(dev, n, s)) || (rc = key[1].alloc(dev, n, s)) || (rc = val[0].alloc(dev, n, s)) || (rc = val[1].alloc(dev, n, s)) ||
+            (rc = G.alloc(dev, n, s)) || (rc = S.alloc(dev, n, s)) || (rc = hist.alloc(dev, rs.nblk * 256, s)) || (rc = totals.alloc(dev, 256, s)) ||
+            (rc = flag.alloc(dev, n, s)) || (rc = first.alloc(dev, n, s)) || (rc = sums.alloc(dev, n / SRCH_CHUNK + 2, s)) ||
+            (rc = st.scratch<int64_t>(2, &d_tot)))
+            return rc;
+        if (want_copies && ((rc = copies.alloc(dev, n, s)) || (rc = unres.alloc(dev, n, s)))) return rc;
+        rs.hist = hist.p; rs.totals = totals.p;
+        return FX_OK;
+    }
+};
+
+// What the two entries check before anything is allocated, in the order of the screening entries; the queries on the device.
+struct DdArgs { FqLaunch q; int64_t n; const int64_t *d_ids, *d_start, *d_end; };
+static int dd_prepare(fx_handle *h, Staged &st, const int64_t *ids, const int64_t *start, const int64_t *end, int64_t *first_bad, DdArgs *a) {
+    int rc;
+    a->d_ids = a->d_start = a->d_end = nullptr;
+    const int64_t n = a->n;
+    if (n == 0) return FX_OK;
+    st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
+    if ((rc = st.up(h, ids, ids ? n : 0, &a->d_ids)) || (rc = st.up(h, start, start ? n : 0, &a->d_start)) || (rc = st.up(h, end, end ? n : 0, &a->d_end))) return rc;
+    if (start) {
+        const FqView v = fq_view(h);
+        BadFlag bad;
+        if ((rc = bad.arm(h, st))) return rc;
+        FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, a->d_ids, n, a->d_start, a->d_end, bad.d);
+        HIPCHK(hipGetLastError());
+        if ((rc = bad.read(h, first_bad))) return rc;
+        if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
+    }
+    return FX_OK;
+}
+static int dd_check(fx_handle *h, const int64_t *ids, int64_t n_ids, int flags, int hash_bits, int64_t min_copies, int64_t *first_bad, DdArgs *a) {
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    int rc = fq_prepare(h, 0, 0, &a->q);                       // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+    if (rc) return rc;
+    if (flags & ~FX_DUP_REVCOMP) return fail(FX_EINVAL, "unknown flag bits %d", flags);
+    if (hash_bits < 0 || hash_bits > 64) return fail(FX_EINVAL, "hash_bits %d outside 0..64", hash_bits);
+    if (min_copies < 1) return fail(FX_EINVAL, "min_copies %lld below 1", (long long)min_copies);
+    a->n = ids ? n_ids : h->n_reads;
+    if (a->n > DD_MAX_QUERIES) return fail(FX_EINVAL, "%lld queries, more than the 2^31 the sort carries positions for", (long long)a->n);
+    return check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
+}
+
+// first (and copies) of a.n > 0 queries on the device: the rounds of fx_fastq_dedup.hpp.  Nothing waits in here but the sort's
+// passes and the two totals of a round.
+static int dd_run(fx_handle *h, const DdArgs &a, int flags, int hash_bits, bool want_copies, DdWork &w, int64_t *n_groups, int64_t *n_rounds) {
+    int rc;
+    const FqView v = fq_view(h);
+    const int lpr = a.q.lpr, bits = hash_bits ? hash_bits : 64;
+    const uint64_t mask = bits == 64 ? ~0ull : (1ull << bits) - 1ull;
+    const bool revcomp = flags & FX_DUP_REVCOMP;
+    DdQueries Q{v.rlen, v.soff, a.d_ids, a.d_start, a.d_end, nullptr, v.base};
+    int64_t m = a.n, groups = 0, rounds = 0;
+    int lcur = 0;
+    while (m > 0) {
+        const uint64_t seed = dd_seed(rounds);
+        const unsigned nch = nblocks(m, SRCH_CHUNK);
+        with_bool(revcomp, [&](auto R) {
+            FX_LAUNCH(h, K_DD_HASH, k_dd_hash<R()>, dim3(lane_group_grid<k_dd_hash<R()>>(h, m, lpr)), dim3(BLOCK), v.data, v.n, Q, m, lpr, seed, mask,
+                      w.key[0].p, w.val[0].p);
+        });
+        uint64_t *kp[2] = {w.key[0].p, w.key[1].p};
+        uint32_t *vp[2] = {w.val[0].p, w.val[1].p};
+        int cur = 0;
+        h->prof.begin(K_DD_SORT, h->stream);
+        hipError_t e = radix_sort_rows(kp, vp, cur, m, bits, w.rs, h->stream);
+        h->prof.end(h->stream);
+        if (e != hipSuccess) return fail(FX_EDEVICE, "duplicate sort: %s", hipGetErrorString(e));
+        // head flags -> rank and heads; every sorted element against its head; the group sizes; the unresolved counted
+        const KtLdHead heads{kp[cur]};
+        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_sums<1, KtLdHead>), dim3(nch), dim3(BLOCK), heads, m, w.sums.p);
+        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_top<1>), dim3(1), dim3(BLOCK), w.sums.p, (int64_t)nch, w.d_tot);
+        FX_LAUNCH(h, K_DD_VERIFY, k_dd_rank, dim3(nch), dim3(BLOCK), (const uint64_t *)kp[cur], m, (const int64_t *)w.sums.p, w.G.p, w.S.p);
+        if (want_copies) HIPCHK(hipMemsetAsync(w.unres.p, 0, (size_t)m * 4, h->stream));
+        with_bool(revcomp, [&](auto R) {
+            FX_LAUNCH(h, K_DD_VERIFY, k_dd_verify<R()>, dim3(lane_group_grid<k_dd_verify<R()>>(h, m, lpr)), dim3(BLOCK), v.data, v.n, Q, m, lpr,
+                      (const uint32_t *)vp[cur], (const uint32_t *)w.G.p, (const uint32_t *)w.S.p, w.first.p, w.flag.p, want_copies ? w.unres.p : nullptr);
+        });
+        if (want_copies)
+            FX_LAUNCH(h, K_DD_VERIFY, k_dd_copies, dim3(nblocks(m, BLOCK)), dim3(BLOCK), (const uint32_t *)w.S.p, (const int64_t *)w.d_tot, m,
+                      (const uint32_t *)vp[cur], Q.list, (const uint32_t *)w.unres.p, w.copies.p);
+        const QcLdPass left{w.flag.p};
+        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_sums<1, QcLdPass>), dim3(nch), dim3(BLOCK), left, m, w.sums.p);
+        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_top<1>), dim3(1), dim3(BLOCK), w.sums.p, (int64_t)nch, w.d_tot + 1);
+        HIPCHK(hipGetLastError());
+        int64_t tot[2] = {0, 0};                              // the runs of this round, what it left unresolved
+        if ((rc = read_home(h, tot, w.d_tot, 16))) return rc;
+        groups += tot[0];
+        ++rounds;
+        if (tot[1] >= m || tot[0] <= 0) return fail(FX_EDEVICE, "duplicate round %lld resolved nothing", (long long)rounds);     // (every head resolves)
+        if (tot[1] > 0) {                                     // their queries, ascending, are the next round's elements
+            ScratchBuf<uint32_t> &next = w.list[lcur];
+            if (!next.p && (rc = next.alloc(h->device, tot[1], h->stream))) return rc;
+            FX_LAUNCH(h, K_DD_VERIFY, (k_kt_compact<QcLdPass, DdPutList>), dim3(nch), dim3(BLOCK), left, m, (const int64_t *)w.sums.p, DdPutList{Q.list, next.p});
+            Q.list = next.p;
+            lcur ^= 1;
+        }
+        m = tot[1];
+    }
+    *n_groups = groups; *n_rounds = rounds;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_dup_first(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end, int flags, int hash_bits,
+                                  int64_t **first, int64_t *n_rows, int64_t *n_groups, int64_t *n_rounds, int64_t *first_bad) {
+    if (!h || !first || !n_rows || !n_groups || !n_rounds || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    *first = nullptr; *n_rows = *n_groups = *n_rounds = 0; *first_bad = -1;
+    DdArgs a;
+    int rc = dd_check(h, ids, n_ids, flags, hash_bits, 1, first_bad, &a);
+    if (rc) return rc;
+    const int64_t n = a.n;
+    PinnedOut<1> out(h);
+    if (n > 0) {
+        Staged st(h);
+        DdWork w;
+        if ((rc = dd_prepare(h, st, ids, start, end, first_bad, &a)) || (rc = w.alloc(h, st, n, false))) return rc;
+        if (!out.alloc(0, n * 8)) return fail(FX_ENOMEM, "pinned block for %lld rows", (long long)n);
+        if ((rc = dd_run(h, a, flags, hash_bits, false, w, n_groups, n_rounds)) || (rc = home(h, "duplicates", {{out.p[0], w.first.p, n * 8}}))) {
+            *n_groups = *n_rounds = 0;
+            return rc;
+        }
+    } else if (!out.alloc(0, 8)) return fail(FX_ENOMEM, "pinned block");
+    out.release(first);
+    *n_rows = n;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_dedup(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end, int flags, int hash_bits,
+                              int64_t min_copies, int64_t max_copies, int64_t **pos, int64_t **copies, int64_t *n_pos, int64_t *n_groups,
+                              int64_t *n_rounds, int64_t *first_bad) {
+    if (!h || !pos || !n_pos || !n_groups || !n_rounds || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    *pos = nullptr; *n_pos = *n_groups = *n_rounds = 0; *first_bad = -1;
+    if (copies) *copies = nullptr;
+    DdArgs a;
+    int rc = dd_check(h, ids, n_ids, flags, hash_bits, min_copies, first_bad, &a);
+    if (rc) return rc;
+    const int64_t n = a.n;
+    int64_t total = 0;
+    PinnedOut<2> out(h);
+    auto pinned = [&](int64_t rows) { return out.alloc(0, std::max<int64_t>(rows, 1) * 8) && (!copies || out.alloc(1, std::max<int64_t>(rows, 1) * 8)); };
+    if (n > 0) {
+        Staged st(h);
+        DdWork w;
+        ScratchBuf<uint8_t> pass;
+        int64_t *sums = nullptr, groups = 0, rounds = 0;
+        if ((rc = dd_prepare(h, st, ids, start, end, first_bad, &a)) || (rc = w.alloc(h, st, n, true)) ||
+            (rc = pass.alloc(h->device, n, h->stream)) || (rc = dd_run(h, a, flags, hash_bits, true, w, &groups, &rounds)))
+            return rc;
+        FX_LAUNCH(h, K_DD_SELECT, k_dd_pass, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)w.first.p, (const uint32_t *)w.copies.p, n, min_copies,
+                  max_copies, pass.p);
+        // the chunk offsets and the total; k_fq_select_emit applies the offsets itself
+        if ((rc = sscan<1>(h, st, K_DD_SELECT, QcLdPass{pass.p}, n, nullptr, w.d_tot, &sums)) || (rc = read_home(h, &total, w.d_tot, 8))) return rc;
+        if (!pinned(total)) return fail(FX_ENOMEM, "pinned blocks for %lld positions", (long long)total);
+        if (total == 0) h->prof.drain();
+        else {
+            ScratchBuf<int64_t> dev;                           // the positions, then their copies
+            if ((rc = dev.alloc(h->device, 2 * total, h->stream))) return rc;
+            FX_LAUNCH(h, K_DD_SELECT, k_fq_select_emit, dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, dev.p);
+            if (copies)
+                FX_LAUNCH(h, K_DD_SELECT, k_dd_gather, dim3(nblocks(total, BLOCK)), dim3(BLOCK), (const int64_t *)dev.p, total, (const uint32_t *)w.copies.p,
+                          dev.p + total);
+            if ((rc = home(h, "dedup emit", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, copies ? total * 8 : 0}}))) return rc;
+        }
+        *n_groups = groups; *n_rounds = rounds;
+    } else if (!pinned(0)) return fail(FX_ENOMEM, "pinned blocks");
+    out.release(pos, copies);
+    *n_pos = total;
     return FX_OK;
 }
 
