@@ -334,6 +334,25 @@ enum { FX_SEARCH_DEGENERATE = 1, FX_SEARCH_UPPER = 2, FX_SEARCH_PLUS = 4, FX_SEA
 int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, const int64_t *ids, int64_t n_ids,
                     int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int64_t *n_hits, int64_t *counts);
 
+/* ------------------------------------------------------------------ search with mismatches
+ * Extension.  Every window of plen letters of the `seq` of the records -- the text fx_fasta_search walks, with its rules:
+ * bytes 10/13/32 dropped, windows across line ends and never across records, cut at slen -- that MISMATCHES the pattern at
+ * no more than max_mismatch positions (Hamming distance: substitutions only, no insertion or deletion), with its distance
+ * (pyfastx_amd/csrc/fx_search_approx.hpp: Shift-And with max_mismatch + 1 state words).  A position mismatches exactly
+ * when fx_fasta_search would not match there under the same mode, so max_mismatch = 0 gives fx_fasta_search's hits, row
+ * for row.
+ *   pat, rpat, plen, mode, ids, n_ids, cap, rec, start, strand, n_hits, counts: as for fx_fasta_search.
+ *   max_mismatch 0..min(8, plen - 1).
+ *   anchor       bit j set: letter j of pat must not mismatch (a PAM, a primer's 3' end); given for pat, the library mirrors
+ *                it for rpat (letter j of pat is letter plen - 1 - j of rpat).  0: no anchor.
+ *   mismatch     a fourth array beside rec / start / strand: the distance of every hit, 0..max_mismatch.
+ * FX_EINVAL: plen outside 1..64, max_mismatch outside its range, an anchor bit at or above plen (these three are refused
+ * before the handle is looked at), no strand, a null pattern of a strand asked for, a byte-range shard.  FX_ESTATE: no
+ * table built.  FX_ERANGE: more than cap hits, *n_hits = their number, nothing allocated. */
+int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int32_t max_mismatch,
+                           uint64_t anchor, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
+                           uint8_t **strand, uint8_t **mismatch, int64_t *n_hits, int64_t *counts);
+
 /* FASTQ reads by 0-based id (read.c:37-45, 152-167, 237-278): seq and qual
  * are rlen bytes each at dst_off[i]; quali = qual - phred as int8
  * (phred 0 -> 33, read.c:268).  Any of seq/qual/quali may be NULL. */

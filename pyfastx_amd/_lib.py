@@ -51,7 +51,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -225,6 +225,8 @@ def lib():
     L.fx_pinned_holds.argtypes = [vp, i64]
     L.fx_fasta_fetch_alloc.argtypes = [vp, i64, vp, vp, vp, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     L.fx_fasta_search.argtypes = [vp, vp, vp, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
+    L.fx_fasta_search_approx.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                         C.POINTER(vp), C.POINTER(i64), vp]
     L.fx_fastq_fetch_alloc.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     L.fx_fetch_phases.argtypes = [C.POINTER(C.c_double), i32]
     L.fx_fastq_read_stats.argtypes = [vp, vp, i64, i32, i32] + [C.POINTER(vp)] * 7 + [C.POINTER(i64), C.POINTER(i64)]
@@ -1055,11 +1057,11 @@ class Blob:
         o = pinned_array(offs.value, n + 2, np.int64)[:n + 1]
         return pinned_array(dst.value, max(int(o[n]), 1))[:int(o[n])], o
 
-    def fasta_search(self, pattern, rpattern, mode, ids=None, cap=0, counts=False):
+    def fasta_search(self, pattern, rpattern, mode, ids=None, cap=0, counts=False, max_mismatch=None, anchor=0):
         """Every overlapping hit of one pattern on the resident table (fx_fasta_search): pattern / rpattern are the bytes
         searched on + / - (None for a strand that is not in `mode`).  -> (n_hits, (rec, start, strand) pinned arrays or None,
         counts int64[n_sel, 2] or None); more than `cap` hits raise FxError(FX_ERANGE) whose .n_hits is the true count.
-        cap = 0 with counts: counts only."""
+        cap = 0 with counts: counts only.  (max_mismatch, anchor: how fasta_search_approx comes through here.)"""
         plen = len(pattern if pattern is not None else rpattern)
         ids = None if ids is None else self._i64(ids)
         if ids is not None:
@@ -1071,9 +1073,14 @@ class Blob:
         cnt = np.zeros((n_sel, 2), dtype=np.int64) if counts else None
         pat = None if pattern is None else np.frombuffer(bytes(pattern), dtype=np.uint8)
         rpat = None if rpattern is None else np.frombuffer(bytes(rpattern), dtype=np.uint8)
-        rec, st, sd, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
-        rc = lib().fx_fasta_search(self._h, _ptr(pat), _ptr(rpat), plen, int(mode), _ptr(ids), 0 if ids is None else ids.size,
-                                   int(cap), C.byref(rec), C.byref(st), C.byref(sd), C.byref(n), _ptr(cnt))
+        rec, st, sd, mm, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        if max_mismatch is None:
+            rc = lib().fx_fasta_search(self._h, _ptr(pat), _ptr(rpat), plen, int(mode), _ptr(ids), 0 if ids is None else ids.size,
+                                       int(cap), C.byref(rec), C.byref(st), C.byref(sd), C.byref(n), _ptr(cnt))
+        else:
+            rc = lib().fx_fasta_search_approx(self._h, _ptr(pat), _ptr(rpat), plen, int(mode), int(max_mismatch), int(anchor), _ptr(ids),
+                                              0 if ids is None else ids.size, int(cap), C.byref(rec), C.byref(st), C.byref(sd),
+                                              C.byref(mm), C.byref(n), _ptr(cnt))
         if rc:
             _raise(rc, n_hits=int(n.value))
         total = int(n.value)
@@ -1081,7 +1088,15 @@ class Blob:
         if rec.value:
             hits = (pinned_array(rec.value, max(total, 1), np.int64)[:total], pinned_array(st.value, max(total, 1), np.int64)[:total],
                     pinned_array(sd.value, max(total, 1), np.uint8)[:total])
+            if max_mismatch is not None:
+                hits += (pinned_array(mm.value, max(total, 1), np.uint8)[:total],)
         return total, hits, cnt
+
+    def fasta_search_approx(self, pattern, rpattern, mode, max_mismatch, anchor=0, ids=None, cap=0, counts=False):
+        """fasta_search with up to max_mismatch mismatching letters per hit, none of them at a position whose bit is set in
+        `anchor` (bit j = letter j of `pattern`) (fx_fasta_search_approx) -> (n_hits, (rec, start, strand, mismatch) pinned
+        arrays or None, counts or None)."""
+        return self.fasta_search(pattern, rpattern, mode, ids, cap, counts, int(max_mismatch), anchor)
 
     def fastq_fetch_alloc(self, read_id, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         """Reads by id with the layout left to the library (fx_fastq_fetch_alloc) -> (seq, qual, quali, offsets), pinned."""

@@ -841,6 +841,27 @@ class Fasta(_fxobj.FastaCore):
         blob = self._search_blob()
         return search.count_blob(blob, pattern, strand, degenerate, self._uppercase, self._st.device)
 
+    def search_approx(self, pattern, mismatches, anchor=None, strand="both", degenerate=False, ids=None, max_hits=10**8):
+        """Extension: search_all with up to `mismatches` (0..8, below the pattern's length) substituted letters per hit --
+        every window of len(pattern) letters of a record's `seq` whose Hamming distance to the pattern is at most
+        `mismatches`; no insertions or deletions.  A letter mismatches exactly where search_all would not match it (byte
+        inequality, or the IUPAC subset rule under degenerate=True), so mismatches=0 gives search_all's rows.  anchor: the
+        positions of the pattern, as written (forward strand), where no mismatch may fall -- None, a slice or an iterable of
+        0-based positions, e.g. slice(20, 23) for the NGG of a 20 nt guide + PAM; on '-' the same letters are held.
+        -> ApproxHits(ids, starts, stops, strands, mismatches): SearchHits' columns and order plus the distance of every
+        hit (uint8).  ids, max_hits: as for search_all.  On the GPU from the resident stream (csrc/fx_search_approx.hpp)."""
+        from . import search
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        blob = self._search_blob()
+        return search.approx_blob(blob, pattern, mismatches, anchor, strand, degenerate, self._uppercase, sel, max_hits, self._st.device)
+
+    def search_approx_counts(self, pattern, mismatches, anchor=None, strand="both", degenerate=False):
+        """Extension: hits of search_approx per record -> int64[len(fa), 2] (column 0 '+', column 1 '-'); the hits themselves
+        are never materialised."""
+        from . import search
+        blob = self._search_blob()
+        return search.approx_count_blob(blob, pattern, mismatches, anchor, strand, degenerate, self._uppercase, self._st.device)
+
     def kmer_counts(self, k, canonical=False, ids=None):
         """Extension: the k-mer spectrum of the `seq` of every record -> int64[4**k] in pinned memory, counted on the GPU
         from the resident stream (csrc/fx_kmer.hpp).  Letters A C G T in either case (A = 0, C = 1, G = 2, T = 3; uppercase=

@@ -43,6 +43,7 @@
 #include "fx_sort.hpp"
 #include "fx_kseq.hpp"
 #include "fx_search.hpp"
+#include "fx_search_approx.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
 #include "fx_kmer.hpp"
@@ -325,10 +326,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit"};
 
 struct Prof {
     bool on = false;
@@ -3753,17 +3754,30 @@ static bool search_masks(const uint8_t *pat, int plen, int mode, uint64_t *fwd) 
     return true;
 }
 
-extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, const int64_t *ids,
-                               int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int64_t *n_hits,
-                               int64_t *counts) {
+// The level count the approximate kernels run d mismatches with: the smallest instantiated one that holds d + 1 levels.
+template <class F> static void with_levels(int d, F &&f) {
+    if (d == 0) f(std::integral_constant<int, 1>{});
+    else if (d == 1) f(std::integral_constant<int, 2>{});
+    else if (d == 2) f(std::integral_constant<int, 3>{});
+    else if (d <= 4) f(std::integral_constant<int, 5>{});
+    else f(std::integral_constant<int, 9>{});
+}
+
+// Both search entries.  max_mismatch < 0: the exact automaton (fx_search.hpp); otherwise the approximate one
+// (fx_search_approx.hpp) with its anchor and the mismatch column -- the plan, the scans, the cut, the list and the way home
+// are the same.
+static int fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int max_mismatch, uint64_t anchor,
+                        const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand,
+                        uint8_t **mismatch, int64_t *n_hits, int64_t *counts) {
+    const bool approx = max_mismatch >= 0;
     if (!h || !n_hits) return fail(FX_EINVAL, "null argument");
     *n_hits = 0;
-    if (rec) *rec = nullptr; if (start) *start = nullptr; if (strand) *strand = nullptr;
+    if (rec) *rec = nullptr; if (start) *start = nullptr; if (strand) *strand = nullptr; if (mismatch) *mismatch = nullptr;
     if (plen < 1 || plen > 64) return fail(FX_EINVAL, "pattern length %d outside 1..64", (int)plen);
     if (!(mode & (FX_SEARCH_PLUS | FX_SEARCH_MINUS))) return fail(FX_EINVAL, "no strand selected");
     if (((mode & FX_SEARCH_PLUS) && !pat) || ((mode & FX_SEARCH_MINUS) && !rpat)) return fail(FX_EINVAL, "null pattern");
     const bool counts_only = cap == 0 && counts;
-    if (cap < 0 || (!counts_only && (!rec || !start || !strand))) return fail(FX_EINVAL, "null output");
+    if (cap < 0 || (!counts_only && (!rec || !start || !strand || (approx && !mismatch)))) return fail(FX_EINVAL, "null output");
     if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
     if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
     if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for hits across its cuts");
@@ -3787,6 +3801,14 @@ extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *
     if ((rc = st.up(h, masks.data(), 256, &d_masks))) return rc;
     P.masks = d_masks;
     const bool wide = plen > 32;
+    ApproxArg A{0, 0, 0};
+    if (approx) {                              // where a mismatch may fall: the pattern's positions minus the anchor, mirrored for '-'
+        const uint64_t valid = plen == 64 ? ~0ull : (1ull << plen) - 1;
+        uint64_t mirror = 0;
+        for (int j = 0; j < plen; ++j) mirror |= ((anchor >> j) & 1ull) << (plen - 1 - j);
+        const uint64_t nf = (mode & FX_SEARCH_PLUS) ? valid & ~anchor : 0, nr = (mode & FX_SEARCH_MINUS) ? valid & ~mirror : 0;
+        A = wide ? ApproxArg{nf, nr, max_mismatch} : ApproxArg{nf | (nr << 32), 0, max_mismatch};
+    }
     int64_t *tot = (int64_t *)fx_pinned_alloc(64), *d_tot = nullptr;        // tot: where the totals of the scans land
     if (!tot) return FX_ENOMEM;
     std::unique_ptr<int64_t, void (*)(int64_t *)> tot_guard(tot, [](int64_t *p) { fx_pinned_free(p); });
@@ -3805,9 +3827,22 @@ extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *
     if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, 4 * nr1, h->stream))) return rc;
     int64_t *K = pref.p, *Pp = pref.p + nr1, *Pm = pref.p + 2 * nr1, *NZ = pref.p + 3 * nr1;
     const unsigned grid_runs = nblocks(P.n_runs, BLOCK), grid_sel = nblocks(n_sel, BLOCK);
-    with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<W()>, dim3(grid_runs), dim3(BLOCK), P, packed.p); });
+    // the approximate kernels of this call: f(WIDE, NLEV)
+    auto with_form = [&](auto &&f) { with_bool(wide, [&](auto W) { with_levels(A.d, [&](auto N) { f(W, N); }); }); };
+    if (approx)
+        with_form([&](auto W, auto N) {
+            FX_LAUNCH(h, K_ASEARCH_COUNT, (k_asearch_count<decltype(W)::value, decltype(N)::value>), dim3(grid_runs), dim3(BLOCK), P, A, packed.p);
+        });
+    else
+        with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<W()>, dim3(grid_runs), dim3(BLOCK), P, packed.p); });
     if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{packed.p}, P.n_runs, K, d_tot))) return rc;
-    with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<W()>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p); });
+    if (approx)
+        with_form([&](auto W, auto N) {
+            FX_LAUNCH(h, K_SEARCH_SCAN, (k_asearch_fix<decltype(W)::value, decltype(N)::value>), dim3(grid_sel), dim3(BLOCK), P, A, (const int64_t *)K,
+                      packed.p);
+        });
+    else
+        with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<W()>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p); });
     if ((rc = sscan<3>(h, st, K_SEARCH_SCAN, SrchLdHits{packed.p}, P.n_runs, Pp, d_tot))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
     if (counts) {
         if ((rc = st.scratch<int64_t>(2 * n_sel, &cnt_dev))) return rc;
@@ -3821,25 +3856,52 @@ extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *
     if (counts_only) { h->prof.drain(); return FX_OK; }
     if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
     // 3. emit: the runs with hits, at their offsets; the answers home by DMA into pinned blocks
-    PinnedOut<3> out(h);
+    PinnedOut<4> out(h);                       // rec, start, strand, mismatch (the approximate search alone)
     const int64_t m = std::max<int64_t>(total, 1);
-    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m)) return fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m) || (approx && !out.alloc(3, m)))
+        return fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total);
     if (total == 0) h->prof.drain();
     else {
         ScratchBuf<int64_t> out64, list;
-        ScratchBuf<uint8_t> out8;
-        if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out8.alloc(h->device, total, h->stream)) ||
+        ScratchBuf<uint8_t> out8;              // strand, then mismatch
+        if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out8.alloc(h->device, (approx ? 2 : 1) * total, h->stream)) ||
             (rc = list.alloc(h->device, n_list, h->stream)))
             return rc;
         hipLaunchKernelGGL(k_search_list, dim3(grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
-        with_bool(wide, [&](auto W) {
-            FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<W()>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
-                      (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
-        });
-        if ((rc = home(h, "search emit", {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], out8.p, total}}))) return rc;
+        if (approx)
+            with_form([&](auto W, auto N) {
+                FX_LAUNCH(h, K_ASEARCH_EMIT, (k_asearch_emit<decltype(W)::value, decltype(N)::value>), dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, A,
+                          (const int64_t *)list.p, n_list, (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total,
+                          out8.p, out8.p + total);
+            });
+        else
+            with_bool(wide, [&](auto W) {
+                FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<W()>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
+                          (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
+            });
+        if ((rc = home(h, "search emit", {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], out8.p, total},
+                                          {out.p[3], out8.p + total, approx ? total : 0}})))
+            return rc;
     }
-    out.release(rec, start, strand);
+    out.release(rec, start, strand, mismatch);
     return FX_OK;
+}
+
+extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, const int64_t *ids,
+                               int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int64_t *n_hits,
+                               int64_t *counts) {
+    return fasta_search(h, pat, rpat, plen, mode, -1, 0, ids, n_ids, cap, rec, start, strand, nullptr, n_hits, counts);
+}
+
+// (fx_search_approx.hpp)  What the numbers alone decide is refused first, before the handle is looked at.
+extern "C" int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int32_t max_mismatch,
+                                      uint64_t anchor, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
+                                      uint8_t **strand, uint8_t **mismatch, int64_t *n_hits, int64_t *counts) {
+    if (plen < 1 || plen > 64) return fail(FX_EINVAL, "pattern length %d outside 1..64", (int)plen);
+    if (max_mismatch < 0 || max_mismatch > std::min(8, plen - 1))
+        return fail(FX_EINVAL, "max_mismatch %d outside 0..%d", (int)max_mismatch, std::min(8, plen - 1));
+    if (plen < 64 && (anchor >> plen)) return fail(FX_EINVAL, "anchor position at or above the pattern length %d", (int)plen);
+    return fasta_search(h, pat, rpat, plen, mode, max_mismatch, anchor, ids, n_ids, cap, rec, start, strand, mismatch, n_hits, counts);
 }
 
 // ------------------------------------------------------------------ FASTQ quality control (fx_fastq_qc.hpp)

@@ -1,7 +1,9 @@
 """Genome-wide motif search on the resident stream (extension; the reference only has Sequence.search, sequence.c:519-558).
 
 Fasta.search_all / search_counts check the pattern here and hand it to fx_fasta_search (csrc/fx_search.hpp): every
-overlapping hit in the `seq` of the records, on one or both strands, exact or with IUPAC codes."""
+overlapping hit in the `seq` of the records, on one or both strands, exact or with IUPAC codes.  Fasta.search_approx /
+search_approx_counts allow up to `mismatches` substituted letters per hit, none of them inside an anchor
+(fx_fasta_search_approx, csrc/fx_search_approx.hpp)."""
 from collections import namedtuple
 
 import numpy as np
@@ -9,8 +11,10 @@ import numpy as np
 from . import _lib
 
 SearchHits = namedtuple("SearchHits", ["ids", "starts", "stops", "strands"])
+ApproxHits = namedtuple("ApproxHits", ["ids", "starts", "stops", "strands", "mismatches"])
 
 MAX_PATTERN = 64
+MAX_MISMATCH = 8
 
 # the base set of every IUPAC letter (U is T)
 IUPAC = {k: frozenset(v) for k, v in {
@@ -92,4 +96,65 @@ def count_blob(blob, pattern, strand="both", degenerate=False, uppercase=False, 
     if uppercase:
         mode |= _lib.FX_SEARCH_UPPER
     _, _, counts = blob.fasta_search(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, cap=0, counts=True)
+    return counts
+
+
+def compile_approx(pattern, mismatches, anchor=None, strand="both", degenerate=False, device=0):
+    """compile_pattern plus the mismatch budget -> (mode bits, bytes on +, bytes on -, mismatches, anchor bit mask).
+    anchor: the positions of the FORWARD pattern where no mismatch may fall -- None, a slice, or an iterable of 0-based
+    positions; bit j of the mask is letter j (the library mirrors it for '-').  ValueError for what compile_pattern
+    refuses, mismatches outside 0..min(8, len(pattern) - 1) or no integer, a position outside the pattern or no integer."""
+    mode, fwd, rev = compile_pattern(pattern, strand, degenerate, device)
+    L = len(fwd)
+    if isinstance(mismatches, bool) or not isinstance(mismatches, (int, np.integer)):
+        raise ValueError("mismatches must be an integer, not %r" % (mismatches,))
+    if not 0 <= mismatches <= min(MAX_MISMATCH, L - 1):
+        raise ValueError("mismatches=%d outside 0..%d for a pattern of %d letters" % (mismatches, min(MAX_MISMATCH, L - 1), L))
+    mask = 0
+    if isinstance(anchor, slice):
+        anchor = range(*anchor.indices(L))
+    elif anchor is None:
+        anchor = ()
+    elif isinstance(anchor, (str, bytes, bytearray)) or not hasattr(anchor, "__iter__"):
+        raise ValueError("anchor must be None, a slice or an iterable of positions, not %r" % (anchor,))
+    for j in anchor:
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)):
+            raise ValueError("anchor position %r is not an integer" % (j,))
+        if not 0 <= j < L:
+            raise ValueError("anchor position %d outside the pattern (0..%d)" % (j, L - 1))
+        mask |= 1 << int(j)
+    return mode, fwd, rev, int(mismatches), mask
+
+
+def approx_blob(blob, pattern, mismatches, anchor=None, strand="both", degenerate=False, uppercase=False, ids=None, max_hits=10**8,
+                device=0):
+    """search_blob with mismatches -> ApproxHits (arrays in pinned memory; mismatches: uint8, the Hamming distance of every
+    hit)."""
+    mode, fwd, rev, d, mask = compile_approx(pattern, mismatches, anchor, strand, degenerate, device)
+    if uppercase:
+        mode |= _lib.FX_SEARCH_UPPER
+    if max_hits < 0:
+        raise ValueError("max_hits must not be negative")
+    try:
+        total, hits, _ = blob.fasta_search_approx(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, d, mask, ids=ids,
+                                                  cap=int(max_hits))
+    except _lib.FxError as e:
+        if e.code == _lib.FX_ERANGE and getattr(e, "n_hits", 0) > max_hits:
+            raise ValueError("%d hits, more than max_hits=%d" % (e.n_hits, max_hits))
+        raise
+    if hits is None:
+        z = np.zeros(0, dtype=np.int64)
+        return ApproxHits(z, z.copy(), z.copy(), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
+    rec, starts, strands, mis = hits
+    stops = _lib.pinned_empty(total, np.int64)
+    np.add(starts, len(fwd), out=stops)
+    return ApproxHits(rec, starts, stops, strands, mis)
+
+
+def approx_count_blob(blob, pattern, mismatches, anchor=None, strand="both", degenerate=False, uppercase=False, device=0):
+    """Hits of approx_blob per record on + and on - -> int64[n_records, 2]; the hits themselves never leave the device."""
+    mode, fwd, rev, d, mask = compile_approx(pattern, mismatches, anchor, strand, degenerate, device)
+    if uppercase:
+        mode |= _lib.FX_SEARCH_UPPER
+    _, _, counts = blob.fasta_search_approx(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, d, mask, cap=0, counts=True)
     return counts
