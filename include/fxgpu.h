@@ -429,6 +429,45 @@ int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const
                           int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept,
                           int64_t *first_bad);
 
+/* ------------------------------------------------------------------ paired-end FASTQ: mate overlap, merged records (extension)
+ * The reference has no counterpart: it reads one file at a time.  h1 and h2 hold the two files of a paired run; pair i is read i
+ * of h1 and read i of h2, with s1, q1, L1 and s2, q2, L2 the bytes fx_fastq_fetch returns for them (a byte past the end of a
+ * stream reads as 0).  Integer and exact (pyfastx_amd/csrc/fx_fastq_pair.hpp).
+ *
+ * Position j of read 1 MATCHES position k of the reverse-complemented read 2 when s1[j] and s2[L2-1-k] are both upper-case
+ * A C G T and s1[j] is the Watson-Crick complement of s2[L2-1-k]; lower case, N and IUPAC codes mismatch, as in fx_fastq_trim.
+ * DIAGONAL d, in -(L2-1) .. L1-1, places letter k of the reverse complement under s1[k+d]: lo = max(0, d), hi = min(L1, d + L2),
+ * m = hi - lo, mm = the j in [lo, hi) that do not match k = j - d.  d is ACCEPTED when m >= min_overlap, mm <= max_diff and
+ * mm * err_den <= err_num * m.  The diagonals are tried in the order 0, 1, ..., L1-1, -1, -2, ..., -(L2-1) -- the longest
+ * overlap first in each direction -- and the first accepted one is the pair's result; there is no shortcut.
+ *
+ * fx_fastq_pair_overlap: per pair (in the order of ids; ids = NULL: every pair), five columns of *n_rows rows:
+ *   diag        d, or FX_PAIR_NONE when no diagonal is accepted
+ *   overlap     m (0 when none);  mismatches  mm (0 when none)
+ *   end1, end2  what survives adapter read-through: for d < 0 end1 = min(L1, L2 + d) and end2 = L2 + d, otherwise L1 and L2
+ *   (the insert follows: none: -1; d >= 0: max(L1, d + L2); d < 0: L2 + d).
+ *   min_overlap >= 1, max_diff >= 0, err_num within 0..10^9, err_den within 1..10^9, else FX_EINVAL.
+ * fx_fastq_pair_merge_alloc: the merged records of the queries, back to back.  diag: row k belongs to query k (what
+ *   fx_fastq_pair_overlap returned for the same ids); a row that is neither FX_PAIR_NONE nor inside -(L2-1) .. L1-1 of its pair
+ *   gives *first_bad = the first such query, FX_ERANGE, nothing allocated.  With F = the insert, fragment position f in [0, F)
+ *   has has1 = f < L1, k = f - d, has2 = 0 <= k < L2, y = comp(s2[L2-1-k]) (comp: the complement table of fx_fastq_fetch's
+ *   reverse-complement flag), b = q2[L2-1-k]; only one mate present: that mate's byte and quality; both, with x = s1[f] and a =
+ *   q1[f]: x == y as bytes: x with quality max(a, b); else a >= b: x, a; else y, b (qualities compared as raw bytes).  The
+ *   record is H1 "\n" seq "\n+\n" qual "\n", H1 = the header of read 1 as fx_fastq_format_alloc cuts it.  A query with diag =
+ *   FX_PAIR_NONE or F < min_len (>= 0) produces no bytes.  Record k is dst[dst_off[k] .. dst_off[k + 1]); dst_off has *n_rows
+ *   + 1 entries, *n_merged = the records that produced bytes.
+ * ids, the pinned outputs (fx_pinned_alloc blocks that belong to the caller, never NULL after FX_OK), *first_bad and the errors
+ * are those of fx_fastq_trim / fx_fastq_format_alloc (a null handle or output pointer: FX_EINVAL, nothing touched; an id
+ * outside the table: *first_bad = its position, FX_ERANGE, nothing allocated), and: handles on different devices: FX_EINVAL;
+ * different numbers of reads: FX_EINVAL; either handle a byte-range shard: FX_EINVAL; either handle before fx_fastq_build:
+ * FX_ESTATE.  The work runs on h1's stream, which is made to wait for what h2's stream holds (an event, no device-wide wait). */
+#define FX_PAIR_NONE INT32_MIN
+int fx_fastq_pair_overlap(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, int32_t min_overlap, int32_t max_diff,
+                          int64_t err_num, int64_t err_den, int32_t **diag, int32_t **overlap, int32_t **mismatches,
+                          int64_t **end1, int64_t **end2, int64_t *n_rows, int64_t *first_bad);
+int fx_fastq_pair_merge_alloc(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, const int32_t *diag, int64_t min_len,
+                              uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_merged, int64_t *first_bad);
+
 /* ------------------------------------------------------------------ k-mer spectra (extension)
  * The reference counts single letters only (composition); these count every window of k bases, 1 <= k <= 13, into a dense
  * table of 4^k exact int64 counters on the device (pyfastx_amd/csrc/fx_kmer.hpp).  Larger k, up to 31, has a sparse form:

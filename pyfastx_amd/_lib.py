@@ -51,7 +51,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -235,6 +235,9 @@ def lib():
     L.fx_fastq_trim.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i64, i64, i32, i32, i64, i64, i32,
                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_format_alloc.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_pair_overlap.argtypes = [vp, vp, vp, i64, i32, i32, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                        C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_pair_merge_alloc.argtypes = [vp, vp, vp, i64, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fasta_kmers.argtypes = [vp, i32, i32, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_kmers.argtypes = [vp, i32, i32, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(i64)]
     L.fx_fasta_kmer_table.argtypes = [vp, i32, i32, vp, i64, i64, i64] + [C.POINTER(vp)] * 2 + [C.POINTER(i64)] * 4
@@ -1181,6 +1184,37 @@ class Blob:
         o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
         tot = int(o[m])
         return pinned_array(pd.value, max(tot, 1))[:tot], o, int(kept.value)
+
+    def fastq_pair_overlap(self, mate, ids=None, min_overlap=30, max_diff=5, err=(1, 5)):
+        """The overlap of every pair (this blob: read 1, `mate`: read 2; fx_fastq_pair_overlap) -> dict of pinned columns diag,
+        overlap, mismatches (int32), end1, end2 (int64) in the order of ids (None: every pair); diag is FX_PAIR_NONE where no
+        diagonal is accepted.  err = (num, den).  An id outside the table raises FxError(FX_ERANGE) with .first_bad."""
+        ids = None if ids is None else self._i64(ids)
+        cols = [C.c_void_p() for _ in range(5)]
+        n, bad = C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_pair_overlap(self._h, mate._h, _ptr(ids), 0 if ids is None else ids.size, int(min_overlap), int(max_diff),
+                                         int(err[0]), int(err[1]), *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(n.value)
+        names = (("diag", np.int32), ("overlap", np.int32), ("mismatches", np.int32), ("end1", np.int64), ("end2", np.int64))
+        return {k: pinned_array(c.value, max(m, 1), dt)[:m] for (k, dt), c in zip(names, cols)}
+
+    def fastq_pair_merge_alloc(self, mate, diag, ids=None, min_len=0):
+        """The merged records of the pairs (fx_fastq_pair_merge_alloc; diag: what fastq_pair_overlap returned for the same
+        ids) -> (uint8 buffer, int64 offsets[n + 1], records merged), pinned.  A bad id or diagonal raises
+        FxError(FX_ERANGE) with .first_bad."""
+        ids = None if ids is None else self._i64(ids)
+        diag = np.ascontiguousarray(diag, dtype=np.int32)
+        pd, po, n, merged, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_pair_merge_alloc(self._h, mate._h, _ptr(ids), 0 if ids is None else ids.size, _ptr(diag) if diag.size else None,
+                                             int(min_len), C.byref(pd), C.byref(po), C.byref(n), C.byref(merged), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(n.value)
+        o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
+        tot = int(o[m])
+        return pinned_array(pd.value, max(tot, 1))[:tot], o, int(merged.value)
 
     @staticmethod
     def _kmer_ids(ids):

@@ -46,6 +46,7 @@
 #include "fx_search_approx.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
+#include "fx_fastq_pair.hpp"
 #include "fx_kmer.hpp"
 #include "fx_kmer_table.hpp"
 #include "fx_kmer_screen.hpp"
@@ -326,10 +327,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit"};
 
 struct Prof {
     bool on = false;
@@ -4141,6 +4142,123 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
     }
     out.release(dst, dst_off);
     *n_rows = n; *n_kept = kept;
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ paired-end FASTQ (fx_fastq_pair.hpp)
+// Extension: the reference has no counterpart (it reads one file at a time).
+// What the two entries share: both handles whole streams with their tables built, on one device, with as many reads; the ids
+// inside the table; and the order of the two streams -- everything of the call runs on h1's stream, which waits for an event
+// recorded on h2's (what h2 has enqueued so far: its build, its staging), not for the device.
+static PairSrc pair_src(const fx_handle *h) { const FqView v = fq_view(h); return {v.data, v.base, v.n, v.rlen, v.soff, v.qoff, v.dlen}; }
+static int pair_prepare(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, int64_t *first_bad, FqLaunch *q1, FqLaunch *q2) {
+    if (h1->device != h2->device) return fail(FX_EINVAL, "the mates lie on different devices (%d, %d)", h1->device, h2->device);
+    int rc;
+    if ((rc = fq_prepare(h1, 0, 0, q1)) || (rc = fq_prepare(h2, 0, 0, q2))) return rc;
+    if (h1->n_reads != h2->n_reads)
+        return fail(FX_EINVAL, "the mates have different numbers of reads (%lld, %lld)", (long long)h1->n_reads, (long long)h2->n_reads);
+    if ((rc = check_ids(ids, n_ids, h1->n_reads, first_bad, kBadRead))) return rc;
+    if (h1 != h2) {
+        hipEvent_t ev = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        hipError_t e = hipEventRecord(ev, h2->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(h1->stream, ev, 0);
+        (void)hipEventDestroy(ev);                         // (released once it has completed)
+        if (e != hipSuccess) return fail(FX_EDEVICE, "ordering the two streams: %s", hipGetErrorString(e));
+    }
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_pair_overlap(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, int32_t min_overlap, int32_t max_diff,
+                                     int64_t err_num, int64_t err_den, int32_t **diag, int32_t **overlap, int32_t **mismatches,
+                                     int64_t **end1, int64_t **end2, int64_t *n_rows, int64_t *first_bad) {
+    if (!h1 || !h2 || !diag || !overlap || !mismatches || !end1 || !end2 || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
+    *diag = *overlap = *mismatches = nullptr; *end1 = *end2 = nullptr; *n_rows = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    const int64_t lim = 1000000000ll;
+    if (min_overlap < 1) return fail(FX_EINVAL, "min_overlap %d below 1", (int)min_overlap);
+    if (max_diff < 0) return fail(FX_EINVAL, "negative max_diff");
+    if (err_num < 0 || err_num > lim || err_den < 1 || err_den > lim) return fail(FX_EINVAL, "error ratio outside 0..10^9");
+    FqLaunch q1, q2;
+    int rc = pair_prepare(h1, h2, ids, n_ids, first_bad, &q1, &q2);
+    if (rc) return rc;
+    const int64_t n = ids ? n_ids : h1->n_reads;
+    const int64_t m = std::max<int64_t>(n, 1);
+    static const int width[5] = {4, 4, 4, 8, 8};
+    PinnedOut<5> out(h1);
+    for (int c = 0; c < 5; ++c)
+        if (!out.alloc(c, m * width[c])) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n);
+    if (n > 0) {
+        Staged st(h1);
+        st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+        const int64_t *d_ids = nullptr;
+        if ((rc = st.up(h1, ids, ids ? n_ids : 0, &d_ids))) return rc;
+        ScratchBuf<uint8_t> dev;                           // the five columns, each from a 256-byte boundary
+        int64_t at[6] = {0};
+        for (int c = 0; c < 5; ++c) at[c + 1] = at[c] + ((n * width[c] + 255) & ~255ll);
+        if ((rc = dev.alloc(h1->device, at[5], h1->stream))) return rc;
+        const PairCols cols{(int32_t *)(dev.p + at[0]), (int32_t *)(dev.p + at[1]), (int32_t *)(dev.p + at[2]), (int64_t *)(dev.p + at[3]),
+                            (int64_t *)(dev.p + at[4])};
+        // a lane group holds the longest read of either stream at once (up to 1024 bytes; a longer one is walked by one lane)
+        const int lpr = (int)std::clamp<int64_t>((std::max<int64_t>(h1->fq_maxlen, h2->fq_maxlen) + 15) / 16, 1, 64);
+        FX_LAUNCH(h1, K_FP_OVERLAP, k_fp_overlap, dim3(lane_group_grid<k_fp_overlap>(h1, n, lpr)), dim3(BLOCK), pair_src(h1), pair_src(h2), d_ids, n, lpr,
+                  PairPar{min_overlap, max_diff, err_num, err_den}, cols);
+        D2H col[5];
+        for (int c = 0; c < 5; ++c) col[c] = {out.p[c], dev.p + at[c], n * width[c]};
+        if ((rc = home(h1, "pair overlap", col, 5))) return rc;
+    }
+    out.release(diag, overlap, mismatches, end1, end2);
+    *n_rows = n;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_pair_merge_alloc(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, const int32_t *diag, int64_t min_len,
+                                         uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_merged, int64_t *first_bad) {
+    if (!h1 || !h2 || !dst || !dst_off || !n_rows || !n_merged || !first_bad) return fail(FX_EINVAL, "null argument");
+    *dst = nullptr; *dst_off = nullptr; *n_rows = 0; *n_merged = 0; *first_bad = -1;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    if (min_len < 0) return fail(FX_EINVAL, "negative min_len");
+    FqLaunch q1, q2;
+    int rc = pair_prepare(h1, h2, ids, n_ids, first_bad, &q1, &q2);
+    if (rc) return rc;
+    const int64_t n = ids ? n_ids : h1->n_reads;
+    if (n > 0 && !diag) return fail(FX_EINVAL, "null argument");
+    PinnedOut<2> out(h1);                                  // the records, their offsets
+    int64_t merged = 0;
+    if (n == 0) {
+        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
+        out.as<int64_t>(1)[0] = 0;
+    } else {
+        Staged st(h1);
+        st.reserve_pin((ids ? n : 0) * 8 + n * 4 + 1024);
+        const int64_t *d_ids = nullptr;
+        const int32_t *d_diag = nullptr;
+        if ((rc = st.up(h1, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h1, diag, n, &d_diag))) return rc;
+        ScratchBuf<int64_t> cnt, offs;                     // record sizes; exclusive offsets (n + 1), then the merged counts (n + 1)
+        int64_t *d_tot = nullptr, tot[2] = {0, 0};
+        BadFlag bad;
+        if ((rc = cnt.alloc(h1->device, n, h1->stream)) || (rc = offs.alloc(h1->device, 2 * (n + 1), h1->stream)) || (rc = st.scratch<int64_t>(2, &d_tot)) ||
+            (rc = bad.arm(h1, st)))
+            return rc;
+        const PairSrc A = pair_src(h1), B = pair_src(h2);
+        FX_LAUNCH(h1, K_FP_MERGE_COUNT, k_fp_merge_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), A, B, d_ids, n, d_diag, min_len, cnt.p, bad.d);
+        if ((rc = sscan<2>(h1, st, K_FP_MERGE_SCAN, FmtLdCnt{cnt.p}, n, offs.p, d_tot))) return rc;
+        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h1->stream));            // (lands before the flag does)
+        if ((rc = bad.read(h1, first_bad))) return rc;
+        if (*first_bad >= 0) return fail(FX_ERANGE, "the diagonal of query %lld lies outside its pair", (long long)*first_bad);
+        const int64_t total = tot[0];
+        merged = tot[1];
+        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
+        ScratchBuf<uint8_t> dev;
+        if ((rc = dev.alloc(h1->device, std::max<int64_t>(total, 1), h1->stream))) return rc;
+        const int lpr = std::max(q1.lpr, q2.lpr);
+        if (total > 0)                                     // (every record at once: the grid is not capped at the resident workgroups)
+            FX_LAUNCH(h1, K_FP_MERGE_EMIT, k_fp_merge_emit, dim3(nblocks(n, lane_groups(lpr))), dim3(BLOCK), A, B, d_ids, n, d_diag, (const int64_t *)offs.p, lpr,
+                      dev.p);
+        if ((rc = home(h1, "pair merge", {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}}))) return rc;
+    }
+    out.release(dst, dst_off);
+    *n_rows = n; *n_merged = merged;
     return FX_OK;
 }
 

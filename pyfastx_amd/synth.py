@@ -194,6 +194,77 @@ def fastq_generate(n_reads, device, rlen=150, seed=7):
     return blob, cols
 
 
+def fastq_pair_generate(n_pairs, device, rlen=150, insert_mean=200.0, insert_sd=60.0, adapter1="AGATCGGAAGAGCACACGTCTGAACTCCAGTCA",
+                        adapter2="AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT", error_rate=0.005, seed=11, min_insert=20):
+    """The two files of a paired-end run in HBM, in the frame of fastq_generate (headers `... 1:N:0:ACGT` / `... 2:N:0:ACGT`,
+    the same name for both mates, qualities uniform 35..70, LF): pair i is a fragment of i.i.d. A C G T whose length is
+    normal(insert_mean, insert_sd), rounded and clipped to min_insert .. 2 * rlen + 100; read 1 is its first rlen letters,
+    read 2 the first rlen letters of its reverse complement; where the fragment is shorter than the read the adapter follows
+    (adapter1 in read 1, adapter2 in read 2 -- read-through), then random letters; every letter of either read is then
+    replaced by another one with probability error_rate.
+    -> (blob1, cols1, blob2, cols2, insert int64[n_pairs]): the columns as fastq_generate's, the true fragment lengths."""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    max_insert = 2 * rlen + 100
+    ins = torch.empty(n_pairs, device=device, dtype=torch.float32).normal_(float(insert_mean), float(insert_sd), generator=g)
+    ins = ins.round().clamp_(min_insert, max_insert).to(torch.int64)
+    heads = [b"@SYN:1:FC:1:0000:00000:000000000 %d:N:0:ACGT\n" % m for m in (1, 2)]
+    hl = len(heads[0])
+    rec = hl + rlen + 1 + 2 + rlen + 1
+    idx = torch.arange(n_pairs, device=device, dtype=torch.int64)
+    tile, x = (idx // 50_000) % 10_000, (idx * 7919) % 100_000
+    ts = []
+    for head in heads:
+        t = torch.empty((n_pairs, rec), dtype=torch.uint8, device=device)
+        t[:, :hl] = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(device)
+        for k in range(9):
+            t[:, 31 - k] = (48 + (idx // (10 ** k)) % 10).to(torch.uint8)
+        for k in range(4):
+            t[:, 15 - k] = (48 + (tile // (10 ** k)) % 10).to(torch.uint8)
+        for k in range(5):
+            t[:, 21 - k] = (48 + (x // (10 ** k)) % 10).to(torch.uint8)
+        t[:, hl + rlen] = 10
+        t[:, hl + rlen + 1] = ord("+")
+        t[:, hl + rlen + 2] = 10
+        t[:, rec - 1] = 10
+        ts.append(t)
+    lut = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device=device)           # code c, complement 3 - c
+    code = {65: 0, 67: 1, 71: 2, 84: 3}
+    ads = [torch.tensor([code[c] for c in a.upper().encode()][:rlen], dtype=torch.uint8, device=device) for a in (adapter1, adapter2)]
+    j = torch.arange(rlen, device=device, dtype=torch.int64)[None, :]
+    step = 1 << 19
+    for a in range(0, n_pairs, step):
+        b = min(n_pairs, a + step)
+        m = b - a
+        F = ins[a:b, None]
+        frag = torch.randint(0, 4, (m, max_insert), device=device, generator=g, dtype=torch.uint8)
+        inside = j < F
+        for mate in (0, 1):
+            tail = torch.randint(0, 4, (m, rlen), device=device, generator=g, dtype=torch.uint8)       # the adapter, then random letters
+            tail[:, :ads[mate].numel()] = ads[mate]
+            src = j if mate == 0 else (F - 1 - j)
+            own = frag.gather(1, src.clamp(0, max_insert - 1).expand(m, rlen))
+            if mate == 1:
+                own = 3 - own
+            r = torch.where(inside, own, tail.gather(1, (j - F).clamp(0, rlen - 1)))
+            hit = torch.rand((m, rlen), device=device, generator=g) < error_rate
+            r = torch.where(hit, (r + torch.randint(1, 4, (m, rlen), device=device, generator=g, dtype=torch.uint8)) & 3, r)
+            ts[mate][a:b, hl:hl + rlen] = lut[r.long()]
+            ts[mate][a:b, hl + rlen + 3:hl + 2 * rlen + 3] = torch.randint(35, 71, (m, rlen), device=device, generator=g, dtype=torch.uint8)
+    n_bytes = n_pairs * rec
+    i = np.arange(n_pairs, dtype=np.int64)
+    out = []
+    for t in ts:
+        blob = torch.zeros(n_bytes + 131072, dtype=torch.uint8, device=device)
+        blob[:n_bytes] = t.view(-1)
+        cols = {"name_off": i * rec + 1, "name_len": np.full(n_pairs, 31, np.int64), "dlen": np.full(n_pairs, hl - 1, np.int64),
+                "rlen": np.full(n_pairs, rlen, np.int64), "soff": i * rec + hl, "qoff": i * rec + hl + rlen + 3,
+                "n_bytes": n_bytes, "rec": rec}
+        out += [blob, cols]
+    return out[0], out[1], out[2], out[3], ins.cpu().numpy()
+
+
 # --------------------------------------------------------------------------- C4: BGZF framing
 def bgzf_compress(raw, block=65280, level=6):
     """bgzip-compatible framing of `raw` (SAM spec 4.1): independent raw-deflate members of
