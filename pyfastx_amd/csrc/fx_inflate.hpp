@@ -92,7 +92,8 @@ __device__ __forceinline__ uint32_t getbits(BitIn &b, int n) {
 //   pool   POOL entries per work-item shared by the sub-tables of both codes of a block
 //   sym, cnt (GLOBAL scratch, 320 + 32 words per member): symbols in canonical order and codes per length, read by the
 //          slow path only -- the canonical walk of zlib's contrib/puff (a public algorithm, not part of the reference
-//          tree) -- which no stream of a well-behaved compressor ever reaches.
+//          tree).  Genome text and FASTQ never reach it; zlib's default strategy on bytes with a long-tailed distribution
+//          does (literal trees of 14 bits need 240-270 sub-table entries at 8 root bits: tests/deflate_truth.py).
 // What the stream of a genome looks like decides the sizes: ~13 k symbols per 64 KiB member, three quarters of them
 // matches (zlib takes any match it finds in four-letter text; mean length 6.5), length codes of 2-10 bits, distance
 // codes of 3-12 bits + up to 13 extra bits; one dynamic block per member.  With 832 B per member every member of the
