@@ -353,6 +353,53 @@ int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const uint8_t *rpat
                            uint64_t anchor, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
                            uint8_t **strand, uint8_t **mismatch, int64_t *n_hits, int64_t *counts);
 
+/* ------------------------------------------------------------------ regions, windows, class runs
+ * Composition of intervals of the records, and the maximal runs of a letter class (pyfastx_amd/csrc/fx_annot.hpp).  The text
+ * of a record is the one fx_fasta_search walks: the bytes of [boff, boff + blen) with 10 / 13 / 32 dropped, cut at slen; the
+ * file's own bytes are classified (no upper-casing).  Coordinates are 0-based half-open positions in that text.
+ * Seven int64 columns, in this order: A C G T N other masked.  A counts 'A' and 'a', and so for C G T N; other is every other
+ * kept byte (IUPAC codes, 'U' and 'u' -- U is not T here, as Sequence.gc_content counts A C G T only --, '*', '-', bytes
+ * >= 128); the first six sum to the interval's length; masked counts the kept bytes in 'a'..'z' and overlaps the first six.
+ * All of them rest on the RANK INDEX of the handle: per 256-byte run of the fx_fasta_search layout over all records, the
+ * exclusive prefixes of the kept bytes and of the seven columns (eight int64: a quarter of the stream's size in device
+ * memory, blocks of the scratch pool).
+ *   fx_fasta_rank_build   builds it (one pass over the stream and a scan); a second call does nothing.  Every entry below
+ *                builds it when it is not there.  A new table (fx_fasta_build*, fx_fasta_set_table, fx_fasta_set_row) or
+ *                shard context makes it invalid; fx_close gives its memory back.
+ *   fx_fasta_rank_free    gives its memory back now; the next entry builds it again.
+ * Whole streams only: a byte-range shard gives FX_EINVAL.  FX_ESTATE: no table built.  Without a device every entry returns
+ * FX_EDEVICE before it looks at an argument.
+ *
+ * fx_fasta_region_counts replaces slicing and counting on the host, one interval at a time (Sequence.composition,
+ * gc_content, gc_skew of fa[name][a:b]: sequence.c:562-749): counts[i * 7 + c] = column c of [start[i], stop[i]) of record
+ * seq_id[i].  Per query two binary searches over the index and at most two runs (512 bytes) of the stream are read,
+ * whatever the interval's length.  where = FX_HOST: the four arrays are host memory; FX_DEVICE: device memory, and the
+ * call returns when the kernel has run.  Ids and intervals are checked on the device, as fx_fasta_fetch_alloc checks them:
+ * an id outside the table, start < 0, stop < start or stop > slen: FX_ERANGE and *first_bad = the first such query (counts
+ * then hold nothing of use).  An empty interval is valid and gives zeros.
+ *
+ * fx_fasta_window_counts (extension; the reference has no windows): for every selected record (ids: 0-based, any order,
+ * NULL: all) the windows [j * step, min(j * step + window, slen)) for every j >= 0 with j * step < slen -- with partial = 0
+ * only those with j * step + window <= slen --, laid out by record (in the order of ids), then by j; made on the device from
+ * a scan of the per-record window counts and answered as regions.  *n = their number; above max_windows: FX_ERANGE and
+ * nothing is allocated.  rec, start, stop (n each) and counts (n * 7): pinned blocks of fx_pinned_alloc that belong to the
+ * caller (fx_pinned_free each).  window < 1, step < 1, max_windows < 0: FX_EINVAL.
+ *
+ * fx_fasta_class_runs (extension): every MAXIMAL interval of the text of the selected records whose letters all lie in a set
+ * of byte values and whose length is at least min_len (>= 1), as (record, start, stop) rows ordered by the position of the
+ * record in ids (NULL: all), then by start -- no sort, no atomic.  set32: 256 bits, bit (c & 7) of byte (c >> 3) = byte value
+ * c is in the set.  An interval may span any number of runs, begin at 0 or end at slen; it never joins across two records.
+ * Kept bytes behind slen are not looked at: an interval that reaches the cut ends at slen.  *n_total = the number of such
+ * intervals; above max_runs: FX_ERANGE, *n = 0 and nothing is allocated; else *n = *n_total rows in pinned blocks as above. */
+int fx_fasta_rank_build(fx_handle *h);
+int fx_fasta_rank_free(fx_handle *h);
+int fx_fasta_region_counts(fx_handle *h, int where, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
+                           int64_t *counts, int64_t *first_bad);
+int fx_fasta_window_counts(fx_handle *h, const int64_t *ids, int64_t n_ids, int64_t window, int64_t step, int partial,
+                           int64_t max_windows, int64_t **rec, int64_t **start, int64_t **stop, int64_t **counts, int64_t *n);
+int fx_fasta_class_runs(fx_handle *h, const uint8_t *set32, int64_t min_len, const int64_t *ids, int64_t n_ids, int64_t max_runs,
+                        int64_t **rec, int64_t **start, int64_t **stop, int64_t *n, int64_t *n_total);
+
 /* FASTQ reads by 0-based id (read.c:37-45, 152-167, 237-278): seq and qual
  * are rlen bytes each at dst_off[i]; quali = qual - phred as int8
  * (phred 0 -> 33, read.c:268).  Any of seq/qual/quali may be NULL. */

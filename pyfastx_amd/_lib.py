@@ -51,7 +51,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -227,6 +227,11 @@ def lib():
     L.fx_fasta_search.argtypes = [vp, vp, vp, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
     L.fx_fasta_search_approx.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                          C.POINTER(vp), C.POINTER(i64), vp]
+    L.fx_fasta_rank_build.argtypes = [vp]
+    L.fx_fasta_rank_free.argtypes = [vp]
+    L.fx_fasta_region_counts.argtypes = [vp, i32, i64, vp, vp, vp, vp, C.POINTER(i64)]
+    L.fx_fasta_window_counts.argtypes = [vp, vp, i64, i64, i64, i32, i64] + [C.POINTER(vp)] * 4 + [C.POINTER(i64)]
+    L.fx_fasta_class_runs.argtypes = [vp, vp, i64, vp, i64, i64] + [C.POINTER(vp)] * 3 + [C.POINTER(i64)] * 2
     L.fx_fastq_fetch_alloc.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     L.fx_fetch_phases.argtypes = [C.POINTER(C.c_double), i32]
     L.fx_fastq_read_stats.argtypes = [vp, vp, i64, i32, i32] + [C.POINTER(vp)] * 7 + [C.POINTER(i64), C.POINTER(i64)]
@@ -1100,6 +1105,59 @@ class Blob:
         `anchor` (bit j = letter j of `pattern`) (fx_fasta_search_approx) -> (n_hits, (rec, start, strand, mismatch) pinned
         arrays or None, counts or None)."""
         return self.fasta_search(pattern, rpattern, mode, ids, cap, counts, int(max_mismatch), anchor)
+
+    def fasta_rank_build(self):
+        """The rank index of the resident table (fx_fasta_rank_build); a second call does nothing."""
+        check(lib().fx_fasta_rank_build(self._h))
+
+    def fasta_rank_free(self):
+        """The rank index's device memory back to the pool (fx_fasta_rank_free); the next region / window / run call rebuilds it."""
+        check(lib().fx_fasta_rank_free(self._h))
+
+    def fasta_region_counts(self, seq_id, start, stop):
+        """The seven class counts A C G T N other masked of every (record id, start, stop) (fx_fasta_region_counts) ->
+        int64[n, 7]; an invalid query raises FxError(FX_ERANGE) whose .first_bad is its index."""
+        seq_id, start, stop = self._i64(seq_id), self._i64(start), self._i64(stop)
+        n = seq_id.size
+        if start.size != n or stop.size != n:
+            raise ValueError("ids, starts and stops differ in length")
+        counts = pinned_empty(n * 7, np.int64).reshape(n, 7)
+        bad = C.c_int64(-1)
+        rc = lib().fx_fasta_region_counts(self._h, FX_HOST, n, _ptr(seq_id), _ptr(start), _ptr(stop), _ptr(counts), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        return counts
+
+    def fasta_window_counts(self, window, step, partial=True, ids=None, cap=10**8):
+        """The windows of the selected records and their class counts (fx_fasta_window_counts) -> (rec, start, stop, counts
+        int64[n, 7]) pinned arrays; more than `cap` windows raise FxError(FX_ERANGE) whose .n_rows is the true count."""
+        ids = None if ids is None else self._i64(ids)
+        out = [C.c_void_p() for _ in range(4)]
+        n = C.c_int64(0)
+        rc = lib().fx_fasta_window_counts(self._h, _ptr(ids), 0 if ids is None else ids.size, int(window), int(step), int(bool(partial)),
+                                          int(cap), *[C.byref(p) for p in out], C.byref(n))
+        if rc:
+            _raise(rc, n_rows=int(n.value))
+        t = int(n.value)
+        rec, a, b = (pinned_array(p.value, max(t, 1), np.int64)[:t] for p in out[:3])
+        return rec, a, b, pinned_array(out[3].value, max(t, 1) * 7, np.int64)[:t * 7].reshape(t, 7)
+
+    def fasta_class_runs(self, set32, min_len=1, ids=None, cap=10**8):
+        """Every maximal interval of letters of the 256-bit set `set32` (32 bytes) of at least min_len letters
+        (fx_fasta_class_runs) -> (rec, start, stop) pinned arrays; more than `cap` raise FxError(FX_ERANGE) whose .n_rows is
+        the true count."""
+        ids = None if ids is None else self._i64(ids)
+        bits = np.frombuffer(bytes(set32), dtype=np.uint8)
+        if bits.size != 32:
+            raise ValueError("a byte set is 32 bytes")
+        out = [C.c_void_p() for _ in range(3)]
+        n, tot = C.c_int64(0), C.c_int64(0)
+        rc = lib().fx_fasta_class_runs(self._h, _ptr(bits), int(min_len), _ptr(ids), 0 if ids is None else ids.size, int(cap),
+                                       *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
+        if rc:
+            _raise(rc, n_rows=int(tot.value))
+        t = int(n.value)
+        return tuple(pinned_array(p.value, max(t, 1), np.int64)[:t] for p in out)
 
     def fastq_fetch_alloc(self, read_id, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         """Reads by id with the layout left to the library (fx_fastq_fetch_alloc) -> (seq, qual, quali, offsets), pinned."""

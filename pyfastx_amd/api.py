@@ -907,6 +907,57 @@ class Fasta(_fxobj.FastaCore):
         kmer.check_profile(k, self._seq_counts if sel is None else len(sel), max_bytes)
         return kmer.fasta_profile_blob(self._search_blob(), k, canonical, sel, self._seq_counts, max_bytes)
 
+    def region_stats(self, names_or_ids, starts, stops):
+        """Batched composition of intervals -- what fa[name][a:b].composition, .gc_content and .gc_skew answer one slice at a
+        time on the host (sequence.c:562-749): 0-based half-open (start, stop) on many sequences in one kernel launch ->
+        annot.RegionStats with ids, starts, stops, counts (int64[n, 7]; columns A C G T N other masked: either case, U in
+        other, masked = letters in a..z) and the derived length, gc_content (percent), gc_skew and masked_fraction.  The
+        file's own letters are counted (uppercase= plays no part).  names_or_ids and the errors are fetch_many's: an unknown
+        name KeyError, an id outside the table IndexError, an interval outside its sequence ValueError; an empty interval
+        gives zeros.  Counted on the GPU from the rank index of the table (csrc/fx_annot.hpp), built on first use: two runs
+        of the stream are read per interval, whatever its length."""
+        from . import annot
+        n = len(names_or_ids)
+        ids = self._ids_of(names_or_ids)
+        starts, stops = np.asarray(starts, dtype=np.int64), np.asarray(stops, dtype=np.int64)
+        if starts.shape != (n,) or stops.shape != (n,):
+            raise ValueError("ids, starts and stops differ in length")
+        blob = self._search_blob()
+        try:
+            return annot.region_blob(blob, ids, starts, stops)
+        except _lib.FxError as e:
+            if e.code != _lib.FX_ERANGE or getattr(e, "first_bad", -1) < 0:
+                raise _fx_to_py(e)
+            raise ValueError("interval outside the sequence")
+
+    def window_stats(self, window, step=None, ids=None, partial=True, max_windows=10**8):
+        """Extension: composition of every window [j * step, min(j * step + window, len)) with j * step < len of every record
+        (ids: restrict to these names or 0-based ids) -> annot.RegionStats, rows by record, then by j.  step=None tiles (step =
+        window); partial=False keeps only whole windows.  More than max_windows windows: ValueError with the count, nothing
+        allocated.  The windows are made and counted on the GPU (csrc/fx_annot.hpp); no array of windows crosses the link."""
+        from . import annot
+        annot.check_windows(window, step, max_windows)
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        blob = self._search_blob()
+        return annot.window_blob(blob, self._table()["slen"], window, step, sel, partial, max_windows)
+
+    def class_runs(self, kind=None, min_len=1, ids=None, max_runs=10**8, letters=None):
+        """Extension: every maximal stretch of the `seq` of the records whose letters all belong to one class and that is at
+        least min_len letters long -> annot.ClassRuns(ids, starts, stops) ordered by (record, start), with .lengths and
+        .write_bed(path).  kind: 'N' (N, n: assembly gaps), 'masked' (a..z: soft-masked repeats), 'unmasked' (A..Z), or an
+        explicit set of letters used exactly as written -- a str / bytes of more than one distinct letter, or any given as
+        letters=...  A stretch never joins across two records.  ids: restrict to these records.  More than max_runs:
+        ValueError with the count, nothing allocated.  On the GPU from the resident stream (csrc/fx_annot.hpp)."""
+        from . import annot
+        annot.class_set(kind, letters)
+        annot.check_runs(min_len, max_runs)
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        blob = self._search_blob()
+
+        def name_of(r):
+            return self._db.execute("SELECT chrom FROM seq WHERE ID=?", (int(r) + 1,)).fetchone()[0]
+        return annot.runs_blob(blob, kind, min_len, sel, max_runs, letters, name_of)
+
     def _search_blob(self):
         """The blob with the record table resident (installed once from the .fxi, as fetch_many does); a sharded or windowed
         stream has no halo for hits that straddle its cuts."""

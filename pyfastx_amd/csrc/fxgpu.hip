@@ -44,6 +44,7 @@
 #include "fx_kseq.hpp"
 #include "fx_search.hpp"
 #include "fx_search_approx.hpp"
+#include "fx_annot.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
 #include "fx_fastq_pair.hpp"
@@ -327,10 +328,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit"};
 
 struct Prof {
     bool on = false;
@@ -466,7 +467,11 @@ struct fx_handle {
     ScratchBuf<int64_t> fxi_part_first;
     int64_t fxi_part_nleaf = 0, fxi_part_row_base = 0;
     int fxi_part_kind = -1;
-    DevBuf<uint8_t> arena;     // scratch for host-array calls (Staged)
+    // the rank index of the FASTA table (fx_annot.hpp), built on first use: first run of every record, 8 exclusive prefixes per run
+    ScratchBuf<int64_t> rk_run0, rk_pref;    // (blocks of the scratch pool: a quarter of the stream's size)
+    int64_t rk_runs = 0;
+    bool rk_valid = false;                   // false again whenever the table or the shard context changes
+    DevBuf<uint8_t> arena;    // scratch for host-array calls (Staged)
     int64_t arena_used = 0;
     uint8_t *pin_in = nullptr; // pinned staging for the query arrays of host-array calls: pageable source -> here (threads) -> one DMA each
     int64_t pin_in_cap = 0, pin_in_used = 0;
@@ -549,6 +554,7 @@ extern "C" int fx_close(fx_handle *h) {
     h->fxi_order.release();                                  // (back to the pool while the stream it names still exists)
     h->fxi_soff.release(); h->fxi_slen.release();
     h->fxi_part_first.release();
+    h->rk_run0.release(); h->rk_pref.release();
     free_blob(h);
     if (h->pin_tot) (void)hipHostFree(h->pin_tot);
     if (h->one_box) (void)hipHostFree(h->one_box);
@@ -582,7 +588,7 @@ extern "C" int fx_set_shard(fx_handle *h, int64_t base, int prev_byte, int is_la
     h->base = base;
     h->prev_byte = base == 0 ? '\n' : (prev_byte & 0xFF);
     h->is_last = is_last != 0;
-    h->scanned = h->fasta_built = h->fastq_built = h->comp_runs_valid = false;
+    h->scanned = h->fasta_built = h->fastq_built = h->comp_runs_valid = h->rk_valid = false;
     h->nm_kind = -1;
     return FX_OK;
 }
@@ -2252,7 +2258,7 @@ extern "C" int fx_fasta_build_begin(fx_handle *h, int full_name) {
     h->nm_kind = -1;
     const bool with_comp = (full_name & 2) != 0;   // bit 1: the composition counters ride on the scan (fx_fasta_comp* then reads nothing twice)
     full_name &= 1;
-    h->comp_runs_valid = false;
+    h->comp_runs_valid = h->rk_valid = false;
     if ((rc = granule_pass<0>(h, false, with_comp))) return rc;      // the one pass over the stream: granule summaries + prefixes
     if (h->hdr.cap < 4096 && (rc = alloc_fasta_table(h, 4096))) return rc;
     if ((rc = enqueue_records(h, full_name))) return rc;
@@ -2309,6 +2315,7 @@ extern "C" int fx_fasta_set_table(fx_handle *h, int64_t n, const int64_t *boff, 
     if (!h || n < 0 || (n > 0 && (!boff || !blen || !slen || !llen || !elen || !norm))) return fail(FX_EINVAL, "bad argument");
     int rc = use_device(h);
     if (rc) return rc;
+    h->rk_valid = false;
     if ((rc = alloc_fasta_table(h, std::max<int64_t>(n, 1)))) return rc;
     auto up = [&](void *d, const void *s_, size_t bytes) { return hipMemcpyAsync(d, s_, bytes, hipMemcpyHostToDevice, h->stream); };
     if (n) {
@@ -2461,7 +2468,7 @@ static int fastq_count(fx_handle *h, int64_t *n_nl_core, int64_t *last_nl_core, 
     int rc = use_device(h);
     if (rc) return rc;
     if (h->n <= 0) return fail(FX_EFORMAT, "empty input");
-    h->fasta_built = h->fastq_built = h->comp_runs_valid = false;
+    h->fasta_built = h->fastq_built = h->comp_runs_valid = h->rk_valid = false;
     h->fq_comp_valid = false;
     // One read or two?  Line records pay when most granules fit their slot: ask three windows of the stream.
     static const int force = [] { const char *e = getenv("FX_FQ_LINES"); return e ? atoi(e) : -1; }();   // 0 / 1: experiments
@@ -2637,7 +2644,7 @@ static int fastq_records(fx_handle *h, int64_t loff, int64_t prev_nl, fx_fastq_s
 extern "C" int fx_set_halo(fx_handle *h, int64_t halo_bytes) {
     if (!h || halo_bytes < 0 || halo_bytes > h->n) return fail(FX_EINVAL, "bad halo");
     h->halo = halo_bytes;
-    h->scanned = h->fasta_built = h->fastq_built = h->comp_runs_valid = false;
+    h->scanned = h->fasta_built = h->fastq_built = h->comp_runs_valid = h->rk_valid = false;
     return FX_OK;
 }
 
@@ -3903,6 +3910,229 @@ extern "C" int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const ui
         return fail(FX_EINVAL, "max_mismatch %d outside 0..%d", (int)max_mismatch, std::min(8, plen - 1));
     if (plen < 64 && (anchor >> plen)) return fail(FX_EINVAL, "anchor position at or above the pattern length %d", (int)plen);
     return fasta_search(h, pat, rpat, plen, mode, max_mismatch, anchor, ids, n_ids, cap, rec, start, strand, mismatch, n_hits, counts);
+}
+
+// ------------------------------------------------------------------ regions, windows, class runs (fx_annot.hpp)
+static int an_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(FX_EDEVICE, "no HIP device available; libfxgpu has no CPU fallback");
+    return FX_OK;
+}
+// the plan over ALL records and the index, as the kernels take them
+static void rank_view(const fx_handle *h, SearchPlan *P, RankIndex *X) {
+    P->mis = (int64_t)((uintptr_t)h->d_data & 15);
+    P->base = h->d_data - P->mis;
+    P->n = h->n;
+    P->boff = h->fa_boff.p; P->blen = h->fa_blen.p; P->slen = h->fa_slen.p;
+    P->sel = nullptr; P->n_sel = h->n_hdr; P->run0 = h->rk_run0.p; P->n_runs = h->rk_runs;
+    P->plen = 1; P->masks = nullptr;
+    *X = RankIndex{h->rk_run0.p, h->rk_pref.p, h->rk_runs};
+}
+// The index on the handle, built when it is not there: the run plan over all records, one pass over the stream, one scan of
+// eight components.  Uses the handle's arena (Staged): entries call it before they make their own.
+static int rank_build(fx_handle *h) {
+    if (h->rk_valid) return FX_OK;
+    if (h->n_hdr <= 0) return fail(FX_ESTATE, "the table has no records");
+    int rc;
+    Staged st(h);
+    SearchPlan P;
+    int64_t *d_tot = nullptr, n_runs = 0;
+    if ((rc = fasta_run_plan(h, st, K_AN_SCAN, nullptr, 0, 1, &P, &d_tot, &n_runs))) return rc;
+    P.masks = nullptr;
+    if (n_runs >= ((int64_t)1 << 31) * AN_GROUPS) return fail(FX_ERANGE, "stream too large for one grid");
+    if ((rc = h->rk_run0.alloc(h->device, h->n_hdr + 1, h->stream)) || (rc = h->rk_pref.alloc(h->device, AN_NPREF * (n_runs + 1), h->stream))) return rc;
+    HIPCHK(hipMemcpyAsync(h->rk_run0.p, P.run0, (size_t)(h->n_hdr + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
+    ScratchBuf<uint64_t> words;
+    if (n_runs == 0) HIPCHK(hipMemsetAsync(h->rk_pref.p, 0, AN_NPREF * 8, h->stream));
+    else {
+        if ((rc = words.alloc(h->device, n_runs, h->stream))) return rc;
+        FX_LAUNCH(h, K_AN_RANK, k_an_rank, dim3(nblocks(n_runs, AN_GROUPS)), dim3(BLOCK), P, words.p);
+        if ((rc = sscan<AN_NPREF>(h, st, K_AN_SCAN, AnLdRank{words.p}, n_runs, h->rk_pref.p, d_tot))) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->prof.drain();
+    h->rk_runs = n_runs;
+    h->rk_valid = true;
+    return FX_OK;
+}
+// what every entry checks first; the index is there afterwards
+static int an_enter(fx_handle *h) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h) return fail(FX_EINVAL, "null handle");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for intervals across its cuts");
+    if ((rc = use_device(h)) || (rc = finish_build(h))) return rc;
+    return rank_build(h);
+}
+
+extern "C" int fx_fasta_rank_build(fx_handle *h) { return an_enter(h); }
+extern "C" int fx_fasta_rank_free(fx_handle *h) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h) return fail(FX_EINVAL, "null handle");
+    if ((rc = use_device(h))) return rc;
+    h->rk_valid = false;
+    h->rk_runs = 0;
+    h->rk_run0.release(); h->rk_pref.release();            // (each waits for the stream before the block changes hands)
+    return FX_OK;
+}
+
+// k_an_region over n queries whose arrays are on the device; *first = the first query it refused, or -1 (one wait)
+static int an_regions(fx_handle *h, Staged &st, const int64_t *d_id, const int64_t *d_a, const int64_t *d_b, int64_t n, int64_t *d_counts,
+                      int64_t *first) {
+    int rc;
+    SearchPlan P;
+    RankIndex X;
+    rank_view(h, &P, &X);
+    BadFlag bad;
+    if ((rc = bad.arm(h, st))) return rc;
+    FX_LAUNCH(h, K_AN_REGION, k_an_region, dim3(nblocks(n, AN_GROUPS)), dim3(BLOCK), P, X, h->n_hdr, d_id, d_a, d_b, n, d_counts, bad.d);
+    HIPCHK(hipGetLastError());
+    return bad.read(h, first);
+}
+static const char kBadRegion[] = "query %lld: record id or interval outside the sequence";
+
+extern "C" int fx_fasta_region_counts(fx_handle *h, int where, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
+                                      int64_t *counts, int64_t *first_bad) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !first_bad) return fail(FX_EINVAL, "null argument");
+    *first_bad = -1;
+    if (where != FX_HOST && where != FX_DEVICE) return fail(FX_EINVAL, "where is neither FX_HOST nor FX_DEVICE");
+    if (n < 0 || (n > 0 && (!seq_id || !start || !stop || !counts))) return fail(FX_EINVAL, "null query array");
+    if (n >= ((int64_t)1 << 31) * AN_GROUPS) return fail(FX_ERANGE, "too many queries in one batch");
+    if ((rc = an_enter(h))) return rc;
+    if (n == 0) return FX_OK;
+    Staged st(h);
+    ScratchBuf<int64_t> dev;                               // the counts of a host call
+    const int64_t *d_id = seq_id, *d_a = start, *d_b = stop;
+    int64_t *d_counts = counts;
+    if (where == FX_HOST) {
+        st.reserve_pin(n * 8 * 3 + 3 * 256);
+        if ((rc = st.up(h, seq_id, n, &d_id)) || (rc = st.up(h, start, n, &d_a)) || (rc = st.up(h, stop, n, &d_b)) ||
+            (rc = dev.alloc(h->device, n * AN_NCOL, h->stream)))
+            return rc;
+        d_counts = dev.p;
+    }
+    if ((rc = an_regions(h, st, d_id, d_a, d_b, n, d_counts, first_bad))) return rc;
+    if (*first_bad >= 0) return fail(FX_ERANGE, kBadRegion, (long long)*first_bad);
+    if (where == FX_HOST) return home(h, "region counts", {{counts, d_counts, n * AN_NCOL * 8}});
+    h->prof.drain();
+    return FX_OK;
+}
+
+extern "C" int fx_fasta_window_counts(fx_handle *h, const int64_t *ids, int64_t n_ids, int64_t window, int64_t step, int partial,
+                                      int64_t max_windows, int64_t **rec, int64_t **start, int64_t **stop, int64_t **counts, int64_t *n) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !rec || !start || !stop || !counts || !n) return fail(FX_EINVAL, "null argument");
+    *rec = *start = *stop = *counts = nullptr; *n = 0;
+    if (window < 1 || step < 1) return fail(FX_EINVAL, "window %lld and step %lld must be at least 1", (long long)window, (long long)step);
+    if (max_windows < 0) return fail(FX_EINVAL, "max_windows must not be negative");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    Staged st(h);
+    int64_t total = 0;
+    const int64_t *d_sel = nullptr;
+    int64_t *d_tot = nullptr, *woff = nullptr;
+    if (n_sel > 0) {                                       // the windows of every record, their offsets, their number
+        if ((rc = st.up(h, ids, n_ids, &d_sel)) || (rc = st.scratch<int64_t>(8, &d_tot)) || (rc = st.scratch<int64_t>(n_sel + 1, &woff)) ||
+            (rc = sscan<1>(h, st, K_AN_SCAN, AnLdWindows{h->fa_slen.p, d_sel, window, step, partial}, n_sel, woff, d_tot)) ||
+            (rc = read_home(h, &total, d_tot, 8)))
+            return rc;
+    }
+    *n = total;
+    if (total > max_windows) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "%lld windows, more than the %lld asked for", (long long)total, (long long)max_windows);
+    }
+    if (total >= ((int64_t)1 << 31) * AN_GROUPS) return fail(FX_ERANGE, "too many windows in one batch");
+    PinnedOut<4> out(h);                                   // rec, start, stop, counts
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8) || !out.alloc(3, m * AN_NCOL * 8))
+        return fail(FX_ENOMEM, "pinned blocks for %lld windows", (long long)total);
+    if (total == 0) h->prof.drain();
+    else {
+        ScratchBuf<int64_t> dev;                           // rec, start, stop, counts
+        if ((rc = dev.alloc(h->device, (3 + AN_NCOL) * total, h->stream))) return rc;
+        int64_t *d_rec = dev.p, *d_a = dev.p + total, *d_b = dev.p + 2 * total, *d_counts = dev.p + 3 * total, first = -1;
+        FX_LAUNCH(h, K_AN_SCAN, k_an_windows, dim3(nblocks(total, BLOCK)), dim3(BLOCK), (const int64_t *)h->fa_slen.p, d_sel, n_sel,
+                  (const int64_t *)woff, window, step, total, d_rec, d_a, d_b);
+        if ((rc = an_regions(h, st, d_rec, d_a, d_b, total, d_counts, &first))) return rc;
+        if (first >= 0) return fail(FX_ERANGE, kBadRegion, (long long)first);      // (the table contradicts itself)
+        if ((rc = home(h, "window counts", {{out.p[0], d_rec, total * 8}, {out.p[1], d_a, total * 8}, {out.p[2], d_b, total * 8},
+                                            {out.p[3], d_counts, total * AN_NCOL * 8}})))
+            return rc;
+    }
+    out.release(rec, start, stop, counts);
+    return FX_OK;
+}
+
+extern "C" int fx_fasta_class_runs(fx_handle *h, const uint8_t *set32, int64_t min_len, const int64_t *ids, int64_t n_ids, int64_t max_runs,
+                                   int64_t **rec, int64_t **start, int64_t **stop, int64_t *n, int64_t *n_total) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !set32 || !rec || !start || !stop || !n || !n_total) return fail(FX_EINVAL, "null argument");
+    *rec = *start = *stop = nullptr; *n = *n_total = 0;
+    if (min_len < 1) return fail(FX_EINVAL, "min_len %lld must be at least 1", (long long)min_len);
+    if (max_runs < 0) return fail(FX_EINVAL, "max_runs must not be negative");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    Staged st(h);
+    SearchPlan P, all;
+    RankIndex X;
+    rank_view(h, &all, &X);
+    P.n_runs = 0;
+    int64_t *d_tot = nullptr, land = 0, total = 0;
+    ScratchBuf<uint32_t> packed;
+    ScratchBuf<int64_t> pref, list;                        // pref: NZ, O (n_runs + 1 each)
+    int64_t *NZ = nullptr, *O = nullptr;
+    RunsArg A{nullptr, min_len};
+    unsigned grid = 1;
+    uint32_t words[8];
+    memcpy(words, set32, 32);                              // bit c of the set = bit c & 7 of byte c >> 3 (little-endian words)
+    if (n_sel > 0) {
+        if ((rc = fasta_run_plan(h, st, K_AN_RUNS_SCAN, ids, n_ids, 1, &P, &d_tot, &land))) return rc;
+        P.masks = nullptr;
+        if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one grid");
+    }
+    if (P.n_runs > 0) {
+        const int64_t nr1 = P.n_runs + 1;
+        if ((rc = st.up(h, words, 8, &A.set)) || (rc = packed.alloc(h->device, P.n_runs, h->stream)) ||
+            (rc = pref.alloc(h->device, 2 * nr1, h->stream)) || (rc = list.alloc(h->device, P.n_runs, h->stream)))
+            return rc;
+        NZ = pref.p; O = pref.p + nr1;
+        grid = nblocks(P.n_runs, BLOCK);
+        FX_LAUNCH(h, K_AN_RUNS_COUNT, k_an_runs_count, dim3(grid), dim3(BLOCK), P, X, A, packed.p);
+        if ((rc = sscan<1>(h, st, K_AN_RUNS_SCAN, AnLdOutside{packed.p}, P.n_runs, NZ, d_tot))) return rc;
+        FX_LAUNCH(h, K_AN_RUNS_SCAN, k_an_runs_list, dim3(grid), dim3(BLOCK), (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
+        FX_LAUNCH(h, K_AN_RUNS_SCAN, k_an_runs_close, dim3(grid), dim3(BLOCK), P, X, A, (const int64_t *)NZ, (const int64_t *)list.p, packed.p);
+        if ((rc = sscan<1>(h, st, K_AN_RUNS_SCAN, AnLdCloses{packed.p}, P.n_runs, O, d_tot)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
+    }
+    *n_total = total;
+    if (total > max_runs) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "%lld runs, more than the %lld asked for", (long long)total, (long long)max_runs);
+    }
+    PinnedOut<3> out(h);                                   // rec, start, stop
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld runs", (long long)total);
+    if (total == 0) h->prof.drain();
+    else {
+        ScratchBuf<int64_t> dev;
+        if ((rc = dev.alloc(h->device, 3 * total, h->stream))) return rc;
+        FX_LAUNCH(h, K_AN_RUNS_EMIT, k_an_runs_emit, dim3(grid), dim3(BLOCK), P, X, A, (const uint32_t *)packed.p, (const int64_t *)NZ,
+                  (const int64_t *)list.p, (const int64_t *)O, dev.p, dev.p + total, dev.p + 2 * total);
+        if ((rc = home(h, "class runs", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, total * 8}, {out.p[2], dev.p + 2 * total, total * 8}})))
+            return rc;
+    }
+    *n = total;
+    out.release(rec, start, stop);
+    return FX_OK;
 }
 
 // ------------------------------------------------------------------ FASTQ quality control (fx_fastq_qc.hpp)
@@ -5507,6 +5737,7 @@ extern "C" int fx_fasta_set_row(fx_handle *h, int64_t k, int64_t boff, int64_t b
     if (!rc) rc = finish_build(h);
     if (rc) return rc;
     if (k < 0 || k >= h->n_hdr) return fail(FX_ERANGE, "row %lld out of range", (long long)k);
+    h->rk_valid = false;
     // norm: bit 0 = index.c's norm, bit 1 = line-regular (pyfastx_amd/shard.py: stitch_tail decides both from the summaries)
     hipLaunchKernelGGL(k_set_row, dim3(1), dim3(1), 0, h->stream, fasta_cols(h), k, boff, blen, slen, llen, elen, norm, dlen, name_len,
                        (int32_t)((norm >> 1) & 1));
