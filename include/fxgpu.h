@@ -400,6 +400,36 @@ int fx_fasta_window_counts(fx_handle *h, const int64_t *ids, int64_t n_ids, int6
 int fx_fasta_class_runs(fx_handle *h, const uint8_t *set32, int64_t min_len, const int64_t *ids, int64_t n_ids, int64_t max_runs,
                         int64_t **rec, int64_t **start, int64_t **stop, int64_t *n, int64_t *n_total);
 
+/* ------------------------------------------------------------------ tandem repeats
+ * fx_fasta_tandem_repeats (extension; the reference has no repeat search): the perfect tandem repeats (microsatellites) of
+ * period 1..8 of the selected records (pyfastx_amd/csrc/fx_tandem.hpp).  The text and the coordinates are those of the section
+ * above.  Letters are folded: A a = 0, C c = 1, G g = 2, T t = 3; every other kept byte (N, IUPAC codes, U, '*', '-', bytes
+ * >= 128) is INVALID and matches nothing, itself included; soft-masked repeats are found like any other.  A repeat of period
+ * p is a maximal interval [a, b) of the text of one record for which
+ *   - every letter is valid,
+ *   - code(t[j]) == code(t[j - p]) for every j in [a + p, b), and neither a - 1 nor b can join (maximal),
+ *   - b - a >= 2 p and b - a >= max(p * min_copies[p - 1], min_len),
+ *   - the motif t[a : a + p] is primitive -- not a shorter word written several times; equivalently p is the smallest period
+ *     of [a, b): ATATAT is a repeat of period 2 only, AAAAAA of period 1 only.
+ * Repeats of different periods may overlap and all are reported: these are the maximal repetitions of stringology with a
+ * bounded period, not a greedy left-to-right scan whose answer depends on where the scan stands.
+ *   min_copies   max_period entries; min_copies[p - 1] is the threshold of period p, 0: period p is not searched.
+ *   max_period   1..8.
+ *   min_len      >= 0; a further lower bound on b - a for every period.
+ *   ids, n_ids   0-based record ids, any order (NULL: all records in file order).
+ *   rec, start, stop, period, motif   one row per repeat, ordered by the position of the record in ids, then by stop, then by
+ *                period -- the order in which one left-to-right walk closes them; no sort, no atomic.  motif is the 2-bit
+ *                code of t[a : a + p], first letter most significant.  Pinned blocks of fx_pinned_alloc that belong to the
+ *                caller (fx_pinned_free each), never NULL after FX_OK, even for 0 rows.
+ *   *n_total     the number of repeats; above max_rows: FX_ERANGE, *n = 0 and nothing is allocated; else *n = *n_total.
+ * A repeat may span any number of runs, begin at 0 or end at slen; it never joins across two records.  Builds the rank index
+ * when it is not there.  Without a device FX_EDEVICE before any argument is looked at.  FX_EINVAL: a null handle or output
+ * pointer, max_period outside 1..8, an entry of min_copies that is 1 or negative, no period searched, min_len < 0,
+ * max_rows < 0, a byte-range shard.  FX_ESTATE: no table built. */
+int fx_fasta_tandem_repeats(fx_handle *h, const int32_t *min_copies, int32_t max_period, int64_t min_len, const int64_t *ids,
+                            int64_t n_ids, int64_t max_rows, int64_t **rec, int64_t **start, int64_t **stop, uint8_t **period,
+                            uint32_t **motif, int64_t *n, int64_t *n_total);
+
 /* FASTQ reads by 0-based id (read.c:37-45, 152-167, 237-278): seq and qual
  * are rlen bytes each at dst_off[i]; quali = qual - phred as int8
  * (phred 0 -> 33, read.c:268).  Any of seq/qual/quali may be NULL. */

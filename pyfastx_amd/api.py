@@ -958,6 +958,27 @@ class Fasta(_fxobj.FastaCore):
             return self._db.execute("SELECT chrom FROM seq WHERE ID=?", (int(r) + 1,)).fetchone()[0]
         return annot.runs_blob(blob, kind, min_len, sel, max_runs, letters, name_of)
 
+    def tandem_repeats(self, min_copies=(12, 7, 5, 4, 4, 4), min_len=0, ids=None, max_repeats=10**8):
+        """Extension: the perfect tandem repeats (microsatellites) of period 1..8 of the `seq` of the records ->
+        tandem.TandemRepeats(ids, starts, stops, periods, motif_codes) ordered by record, stop, period, with .lengths, .copies,
+        .motifs, .canonical_motifs, .counts_by_motif(), .sorted_by_start() and .write_bed(path).  A repeat of period p is a
+        maximal stretch of A C G T letters (either case; N and every other letter break it) in which each letter equals the
+        one p places before it, at least max(2 p, p * min_copies[p - 1], min_len) long, whose motif is not a shorter word
+        written several times (ATATAT has period 2 only).  Repeats of different periods may overlap and all are reported:
+        maximal repetitions, not MISA's greedy scan.  min_copies: 1 to 8 integers (entry p - 1: period p) or {period: copies};
+        0 = period not searched, else at least 2; the default is Krait's.  ids: restrict to these names or 0-based ids, rows
+        in their order.  A repeat never joins across two records.  More than max_repeats: ValueError with the count, nothing
+        allocated.  On the GPU from the resident stream (csrc/fx_tandem.hpp)."""
+        from . import tandem
+        tandem.check_min_copies(min_copies)
+        tandem.check_limits(min_len, max_repeats)
+        sel = None if ids is None else self._ids_of(ids)
+        blob = self._search_blob()
+
+        def name_of(r):
+            return self._db.execute("SELECT chrom FROM seq WHERE ID=?", (int(r) + 1,)).fetchone()[0]
+        return tandem.repeats_blob(blob, min_copies, min_len, sel, max_repeats, name_of)
+
     def _search_blob(self):
         """The blob with the record table resident (installed once from the .fxi, as fetch_many does); a sharded or windowed
         stream has no halo for hits that straddle its cuts."""

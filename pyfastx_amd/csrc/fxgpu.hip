@@ -45,6 +45,7 @@
 #include "fx_search.hpp"
 #include "fx_search_approx.hpp"
 #include "fx_annot.hpp"
+#include "fx_tandem.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
 #include "fx_fastq_pair.hpp"
@@ -328,10 +329,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit"};
 
 struct Prof {
     bool on = false;
@@ -4132,6 +4133,91 @@ extern "C" int fx_fasta_class_runs(fx_handle *h, const uint8_t *set32, int64_t m
     }
     *n = total;
     out.release(rec, start, stop);
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ tandem repeats (fx_tandem.hpp)
+extern "C" int fx_fasta_tandem_repeats(fx_handle *h, const int32_t *min_copies, int32_t max_period, int64_t min_len, const int64_t *ids,
+                                       int64_t n_ids, int64_t max_rows, int64_t **rec, int64_t **start, int64_t **stop, uint8_t **period,
+                                       uint32_t **motif, int64_t *n, int64_t *n_total) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !min_copies || !rec || !start || !stop || !period || !motif || !n || !n_total) return fail(FX_EINVAL, "null argument");
+    *rec = *start = *stop = nullptr; *period = nullptr; *motif = nullptr; *n = *n_total = 0;
+    if (max_period < 1 || max_period > TD_MAXP) return fail(FX_EINVAL, "max_period %d outside 1..%d", (int)max_period, TD_MAXP);
+    TdArg A{};
+    for (int p = 1; p <= max_period; ++p) {
+        const int64_t c = min_copies[p - 1];
+        if (c == 1 || c < 0) return fail(FX_EINVAL, "min_copies of period %d is %lld: 0 (not searched) or at least 2", p, (long long)c);
+        if (c == 0) continue;
+        A.search4 |= 1u << (4 * (p - 1));
+        A.thr[p - 1] = std::max<int64_t>(p * c, min_len);  // (c >= 2: at least 2 p)
+        for (int d = 1; d <= p; ++d)                       // its divisors decide whether a stretch is primitive
+            if (p % d == 0) A.track4 |= 1u << (4 * (d - 1));
+    }
+    if (!A.search4) return fail(FX_EINVAL, "no period is searched");
+    if (min_len < 0) return fail(FX_EINVAL, "min_len must not be negative");
+    if (max_rows < 0) return fail(FX_EINVAL, "max_rows must not be negative");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    int n_track = 0;
+    for (int p = 1; p <= TD_MAXP; ++p) A.slot[p - 1] = (A.track4 >> (4 * (p - 1))) & 1u ? n_track++ : 0;
+    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    Staged st(h);
+    SearchPlan P, all;
+    RankIndex X;
+    rank_view(h, &all, &X);
+    P.n_runs = 0;
+    int64_t *d_tot = nullptr, land = 0, total = 0;
+    ScratchBuf<uint32_t> words;                            // pk (n_track rows of n_runs), closes (n_runs)
+    ScratchBuf<int64_t> pref, list;                        // pref: NZ (8 components of n_runs + 1), O (n_runs + 1)
+    int64_t *NZ = nullptr, *O = nullptr;
+    uint32_t *pk = nullptr, *closes = nullptr;
+    unsigned grid = 1;
+    if (n_sel > 0) {
+        if ((rc = fasta_run_plan(h, st, K_TD_SCAN, ids, n_ids, 1, &P, &d_tot, &land))) return rc;
+        P.masks = nullptr;
+        if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one grid");
+    }
+    if (P.n_runs > 0) {
+        const int64_t nr1 = P.n_runs + 1;
+        if ((rc = words.alloc(h->device, (n_track + 1) * P.n_runs, h->stream)) || (rc = pref.alloc(h->device, (TD_MAXP + 1) * nr1, h->stream)) ||
+            (rc = list.alloc(h->device, n_track * P.n_runs, h->stream)))
+            return rc;
+        pk = words.p; closes = words.p + n_track * P.n_runs;
+        NZ = pref.p; O = pref.p + TD_MAXP * nr1;
+        grid = nblocks(P.n_runs, BLOCK);
+        TdLdBreak brk{pk, P.n_runs, {}, A.track4};
+        memcpy(brk.slot, A.slot, sizeof brk.slot);
+        FX_LAUNCH(h, K_TD_COUNT, k_td_count, dim3(grid), dim3(BLOCK), P, X, A, pk, closes);
+        if ((rc = sscan<TD_MAXP>(h, st, K_TD_SCAN, brk, P.n_runs, NZ, d_tot))) return rc;
+        FX_LAUNCH(h, K_TD_SCAN, k_td_list, dim3(grid), dim3(BLOCK), A, (const uint32_t *)pk, (const int64_t *)NZ, P.n_runs, list.p);
+        FX_LAUNCH(h, K_TD_CLOSE, k_td_close, dim3(grid), dim3(BLOCK), P, X, A, (const uint32_t *)pk, (const int64_t *)NZ, (const int64_t *)list.p, closes);
+        if ((rc = sscan<1>(h, st, K_TD_SCAN, TdLdCloses{closes}, P.n_runs, O, d_tot)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
+    }
+    *n_total = total;
+    if (total > max_rows) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "%lld repeats, more than the %lld asked for", (long long)total, (long long)max_rows);
+    }
+    PinnedOut<5> out(h);                                   // rec, start, stop, period, motif
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8) || !out.alloc(3, m) || !out.alloc(4, m * 4))
+        return fail(FX_ENOMEM, "pinned blocks for %lld repeats", (long long)total);
+    if (total == 0) h->prof.drain();
+    else {
+        ScratchBuf<int64_t> dev;                           // rec, start, stop
+        ScratchBuf<uint32_t> dev4;                         // motif, then period (one byte a row)
+        if ((rc = dev.alloc(h->device, 3 * total, h->stream)) || (rc = dev4.alloc(h->device, total + (total + 3) / 4, h->stream))) return rc;
+        uint8_t *d_period = (uint8_t *)(dev4.p + total);
+        FX_LAUNCH(h, K_TD_EMIT, k_td_emit, dim3(grid), dim3(BLOCK), P, X, A, (const uint32_t *)pk, (const int64_t *)NZ, (const int64_t *)list.p,
+                  (const uint32_t *)closes, (const int64_t *)O, dev.p, dev.p + total, dev.p + 2 * total, d_period, dev4.p);
+        if ((rc = home(h, "tandem repeats", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, total * 8}, {out.p[2], dev.p + 2 * total, total * 8},
+                                             {out.p[3], d_period, total}, {out.p[4], dev4.p, total * 4}})))
+            return rc;
+    }
+    *n = total;
+    out.release(rec, start, stop, period, motif);
     return FX_OK;
 }
 
