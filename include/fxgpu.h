@@ -430,6 +430,57 @@ int fx_fasta_tandem_repeats(fx_handle *h, const int32_t *min_copies, int32_t max
                             int64_t n_ids, int64_t max_rows, int64_t **rec, int64_t **start, int64_t **stop, uint8_t **period,
                             uint32_t **motif, int64_t *n, int64_t *n_total);
 
+/* ------------------------------------------------------------------ open reading frames, translation
+ * fx_fasta_orfs (extension; the reference reads no codon): the open reading frames of the selected records in all six frames
+ * (pyfastx_amd/csrc/fx_orf.hpp).  The text and the coordinates (0-based, half-open) are those of the sections above; letters
+ * fold as for the tandem repeats: A a = 0, C c = 1, G g = 2, T t = 3, every other kept byte (N, IUPAC codes, U, '*', '-',
+ * bytes >= 128) is INVALID.
+ *   Genetic code.  stop_mask and start_mask have one bit per codon, indexed 16 c0 + 4 c1 + c2 in that letter code; a codon in
+ *   both masks is a stop.  On the reverse strand the codon that occupies the forward positions [j, j + 3) is read as its
+ *   reverse complement: index 16 (3 - c2) + 4 (3 - c1) + (3 - c0).
+ *   Codon classes.  A codon with an invalid letter is invalid; otherwise it is STOP, START or OTHER by the masks.  A BREAK is
+ *   a STOP or an invalid codon.
+ *   Frames and segments.  For each strand and residue class c in {0, 1, 2} the codons are those at j = c (mod 3) with 0 <= j
+ *   and j + 3 <= slen.  A segment is a maximal run of consecutive codons of one class that are no breaks: its left end is c
+ *   or the end of a break codon, its right end the start of the next break codon or the end of the last full codon of the
+ *   class.  Empty segments give nothing.  A segment never joins across two records; it may span any number of runs.
+ *   mode         0 (stop to stop): the row is the segment [a, b).  1: the row is [s, b), s the first START codon of the
+ *                segment; a segment without one gives no row.
+ *   min_len      a row is kept when it has at least max(min_len, 3) letters.  The stop codon that ends an ORF is never
+ *                inside [start, stop).
+ *   strands      1 forward, 2 reverse, 3 both.  The reverse strand follows the same rules on the reverse complement of the
+ *                text; a row [s, e) found there is reported as [slen - e, slen - s).  In a left-to-right walk of the forward
+ *                text a reverse segment opens behind a reverse-strand break on its left and closes at the break on its right,
+ *                and in mode 1 its row ends at the LAST reverse START codon in front of that break.
+ *   ids, n_ids   0-based record ids, any order (NULL: all records in file order).
+ *   rec, start, stop (int64), frame (int8), flags (uint8)   one row per ORF.  frame: forward +1 + start % 3, reverse
+ *                -(1 + (slen - stop) % 3).  flags, in the ORF's own orientation: bit 0 a STOP codon follows the 3' end (not
+ *                set when an invalid codon or the end of the text ends it), bit 1 a STOP codon precedes the segment at its 5'
+ *                end (not set for an invalid codon or the record's edge), bit 2 the first codon of the row is a START codon
+ *                (always in mode 1).  Ordered by the position of the record in ids, then by the forward coordinate at which
+ *                a left-to-right walk closes the row's segment (a forward row's stop; for a reverse row the forward right end
+ *                of its segment), then forward before reverse -- no sort, no atomic.  Pinned blocks of fx_pinned_alloc that
+ *                belong to the caller (fx_pinned_free each), never NULL after FX_OK, even for 0 rows.
+ *   *n_total     the number of rows; above max_rows: FX_ERANGE, *n = 0 and nothing is allocated; else *n = *n_total.
+ * Builds the rank index when it is not there.  Without a device FX_EDEVICE before any argument is looked at.  FX_EINVAL: a
+ * null handle or output pointer, mode or strands outside its range, stop_mask == 0, mode 1 with start_mask & ~stop_mask == 0,
+ * min_len < 0, max_rows < 0, a byte-range shard.  FX_ESTATE: no table built. */
+int fx_fasta_orfs(fx_handle *h, uint64_t stop_mask, uint64_t start_mask, int mode, int strands, int64_t min_len, const int64_t *ids,
+                  int64_t n_ids, int64_t max_rows, int64_t **rec, int64_t **start, int64_t **stop, int8_t **frame, uint8_t **flags,
+                  int64_t *n, int64_t *n_total);
+/* fx_fasta_translate_alloc (extension): table translation of a batch of intervals, shaped like fx_fasta_fetch_alloc above.
+ * Query i is the interval [start[i], stop[i]) of the text of record seq_id[i]; with strand[i] != 0 its reverse complement
+ * (strand NULL: all forward).  Amino acid k of a query is aa64[16 c0 + 4 c1 + c2] of its letters 3 k .. 3 k + 2 in the letter
+ * code above; a codon with an invalid letter gives `unknown`.  A query yields (stop - start) / 3 amino acids, one or two
+ * trailing letters are ignored; no codon is rewritten to M.  The intervals are checked on the device as fx_fasta_fetch_alloc
+ * checks them (first invalid one -> *first_bad, FX_ERANGE); *dst (the amino acids back to back) and *dst_off (n + 1 offsets)
+ * are pinned blocks that belong to the caller, never NULL after FX_OK.  Without a device FX_EDEVICE before any argument is
+ * looked at.  FX_EINVAL: a null handle, table, query array or output pointer, n < 0, a byte-range shard.  FX_ESTATE: no table
+ * built. */
+int fx_fasta_translate_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
+                             const uint8_t *strand, const uint8_t *aa64, uint8_t unknown, uint8_t **dst, int64_t **dst_off,
+                             int64_t *first_bad);
+
 /* FASTQ reads by 0-based id (read.c:37-45, 152-167, 237-278): seq and qual
  * are rlen bytes each at dst_off[i]; quali = qual - phred as int8
  * (phred 0 -> 33, read.c:268).  Any of seq/qual/quali may be NULL. */

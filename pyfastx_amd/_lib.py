@@ -51,7 +51,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -233,6 +233,8 @@ def lib():
     L.fx_fasta_window_counts.argtypes = [vp, vp, i64, i64, i64, i32, i64] + [C.POINTER(vp)] * 4 + [C.POINTER(i64)]
     L.fx_fasta_class_runs.argtypes = [vp, vp, i64, vp, i64, i64] + [C.POINTER(vp)] * 3 + [C.POINTER(i64)] * 2
     L.fx_fasta_tandem_repeats.argtypes = [vp, vp, C.c_int32, i64, vp, i64, i64] + [C.POINTER(vp)] * 5 + [C.POINTER(i64)] * 2
+    L.fx_fasta_orfs.argtypes = [vp, C.c_uint64, C.c_uint64, i32, i32, i64, vp, i64, i64] + [C.POINTER(vp)] * 5 + [C.POINTER(i64)] * 2
+    L.fx_fasta_translate_alloc.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.c_uint8, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     L.fx_fastq_fetch_alloc.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     L.fx_fetch_phases.argtypes = [C.POINTER(C.c_double), i32]
     L.fx_fastq_read_stats.argtypes = [vp, vp, i64, i32, i32] + [C.POINTER(vp)] * 7 + [C.POINTER(i64), C.POINTER(i64)]
@@ -1174,6 +1176,41 @@ class Blob:
             _raise(rc, n_rows=int(tot.value))
         t = int(n.value)
         return tuple(pinned_array(p.value, max(t, 1), dt)[:t] for p, dt in zip(out, (np.int64, np.int64, np.int64, np.uint8, np.uint32)))
+
+    def fasta_orfs(self, stop_mask, start_mask, mode=1, strands=3, min_len=0, ids=None, cap=10**8):
+        """The open reading frames of the six frames (fx_fasta_orfs): masks by codon index 16 c0 + 4 c1 + c2 in A C G T order,
+        mode 0 stop to stop / 1 START to stop, strands 1 + / 2 - / 3 both -> (rec, start, stop int64, frame int8, flags uint8)
+        pinned arrays in the order the header states; more than `cap` raise FxError(FX_ERANGE) whose .n_rows is the true
+        count."""
+        ids = None if ids is None else self._i64(ids)
+        out = [C.c_void_p() for _ in range(5)]
+        n, tot = C.c_int64(0), C.c_int64(0)
+        rc = lib().fx_fasta_orfs(self._h, int(stop_mask), int(start_mask), int(mode), int(strands), int(min_len), _ptr(ids),
+                                 0 if ids is None else ids.size, int(cap), *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
+        if rc:
+            _raise(rc, n_rows=int(tot.value))
+        t = int(n.value)
+        return tuple(pinned_array(p.value, max(t, 1), dt)[:t] for p, dt in zip(out, (np.int64, np.int64, np.int64, np.int8, np.uint8)))
+
+    def fasta_translate_alloc(self, seq_id, start, stop, aa64, strand=None, unknown=ord("X")):
+        """(record id, start, stop) batches translated by the 64-byte table aa64 (fx_fasta_translate_alloc; strand: None or one
+        0 / 1 per query) -> (uint8 amino acids, int64 offsets[n+1]) in pinned memory; an invalid query raises
+        FxError(FX_ERANGE) whose .first_bad is its index."""
+        seq_id, start, stop = self._i64(seq_id), self._i64(start), self._i64(stop)
+        n = seq_id.size
+        if start.size != n or stop.size != n or (strand is not None and len(strand) != n):
+            raise ValueError("ids, starts, stops and strands differ in length")
+        sd = None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8)
+        tab = np.frombuffer(bytes(aa64), dtype=np.uint8)
+        if tab.size != 64:
+            raise ValueError("the amino-acid table has %d entries, not 64" % tab.size)
+        dst, offs, bad = C.c_void_p(), C.c_void_p(), C.c_int64(-1)
+        rc = lib().fx_fasta_translate_alloc(self._h, n, _ptr(seq_id), _ptr(start), _ptr(stop), _ptr(sd), _ptr(tab), int(unknown),
+                                            C.byref(dst), C.byref(offs), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        o = pinned_array(offs.value, n + 2, np.int64)[:n + 1]
+        return pinned_array(dst.value, max(int(o[n]), 1))[:int(o[n])], o
 
     def fastq_fetch_alloc(self, read_id, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         """Reads by id with the layout left to the library (fx_fastq_fetch_alloc) -> (seq, qual, quali, offsets), pinned."""

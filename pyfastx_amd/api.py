@@ -979,6 +979,60 @@ class Fasta(_fxobj.FastaCore):
             return self._db.execute("SELECT chrom FROM seq WHERE ID=?", (int(r) + 1,)).fetchone()[0]
         return tandem.repeats_blob(blob, min_copies, min_len, sel, max_repeats, name_of)
 
+    def orfs(self, min_len=75, table=1, starts=("ATG",), mode="start", strand="both", ids=None, max_orfs=10**8):
+        """Extension: the open reading frames of the `seq` of the records in all six frames -> orf.Orfs(ids, starts, stops,
+        frames, flags) with .lengths, .strands, .has_stop, .has_start, .complete, .sorted_by_start(), .write_bed(path),
+        .proteins() and .write_faa(path).  Letters are A C G T of either case; every other letter makes its codons invalid.
+        Per strand and frame a segment is a maximal run of codons that are neither a stop of `table` (an NCBI id in 1, 2, 4,
+        11 or a pair of 64-letter strings in TCAG order) nor invalid.  mode "stop": the rows are the segments; mode "start":
+        a row begins at the first START codon of its segment (`starts`: codons written with T, or "table" for the table's own
+        set), a segment without one gives no row.  Rows have at least max(min_len, 3) letters and never hold the stop codon
+        that ends them.  Coordinates are 0-based, half-open, on the forward strand; frames are +1..+3 and -1..-3.  strand:
+        "+", "-" or "both".  ids: restrict to these names or 0-based ids, rows in their order; within a record rows come in
+        the order a left-to-right walk closes their segments.  An ORF never joins across two records.  More than max_orfs:
+        ValueError with the count, nothing allocated.  On the GPU from the resident stream (csrc/fx_orf.hpp)."""
+        from . import orf
+        args = orf.search_args(min_len, table, starts, mode, strand, max_orfs)      # argument errors come first
+        sel = None if ids is None else self._ids_of(ids)
+        blob = self._search_blob()
+
+        def name_of(r):
+            return self._db.execute("SELECT chrom FROM seq WHERE ID=?", (int(r) + 1,)).fetchone()[0]
+        return orf.orfs_run(blob, args, sel, name_of)
+
+    def translate_many(self, names_or_ids, starts, stops, strand=None, table=1):
+        """Extension: the 0-based half-open intervals (start, stop) of many sequences translated by a genetic code ->
+        (uint8 buffer of amino acids, int64 offsets[n+1]), shaped like fetch_many.  strand: optional per-query '+'/'-' (or
+        0/1): '-' translates the reverse complement of the interval.  table: as in orfs().  An interval yields
+        (stop - start) // 3 amino acids; a codon with a letter outside A C G T (either case) gives X; no codon is rewritten
+        to M.  Ids and intervals are checked on the device; errors are those of fetch_many (csrc/fx_orf.hpp)."""
+        from . import orf
+        aa64 = orf.genetic_code(table)[0]
+        n = len(names_or_ids)
+        sd = orf.strands_of(strand, n)
+        starts = np.asarray(starts, dtype=np.int64)
+        stops = np.asarray(stops, dtype=np.int64)
+        first = names_or_ids[0] if n else 0
+        if isinstance(first, str):                           # _ids_of without its range check of ids: the device makes that one,
+            ix = self._table()["index"]                      # and reports the first bad query as fetch_many does
+            try:
+                ids = np.fromiter((ix[k] for k in names_or_ids), dtype=np.int64, count=n)
+            except KeyError as e:
+                raise KeyError("%s does not exist in fasta file" % e.args[0])
+        else:
+            ids = np.asarray(names_or_ids, dtype=np.int64)
+        blob = self._search_blob()
+        try:
+            return blob.fasta_translate_alloc(ids, starts, stops, aa64, strand=sd)
+        except _lib.FxError as e:
+            if e.code != _lib.FX_ERANGE or getattr(e, "first_bad", -1) < 0:
+                raise _fx_to_py(e)
+            k = e.first_bad                                  # the error of fetch_many, of the first query that is not valid
+            err = IndexError("index out of range (query %d)" % k) if ids[k] < 0 or ids[k] >= self._seq_counts \
+                else ValueError("interval outside the sequence (query %d)" % k)
+            err.first_bad = k
+            raise err
+
     def _search_blob(self):
         """The blob with the record table resident (installed once from the .fxi, as fetch_many does); a sharded or windowed
         stream has no halo for hits that straddle its cuts."""

@@ -46,6 +46,7 @@
 #include "fx_search_approx.hpp"
 #include "fx_annot.hpp"
 #include "fx_tandem.hpp"
+#include "fx_orf.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
 #include "fx_fastq_pair.hpp"
@@ -329,10 +330,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate"};
 
 struct Prof {
     bool on = false;
@@ -4218,6 +4219,152 @@ extern "C" int fx_fasta_tandem_repeats(fx_handle *h, const int32_t *min_copies, 
     }
     *n = total;
     out.release(rec, start, stop, period, motif);
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ open reading frames, translation (fx_orf.hpp)
+// the mask of the reverse strand by forward codon index: bit f = bit (index of the reverse complement of codon f) of m
+static uint64_t orf_reverse_mask(uint64_t m) {
+    uint64_t r = 0;
+    for (int f = 0; f < 64; ++f) {
+        const int c0 = f >> 4, c1 = (f >> 2) & 3, c2 = f & 3;
+        r |= ((m >> (16 * (3 - c2) + 4 * (3 - c1) + (3 - c0))) & 1ull) << f;
+    }
+    return r;
+}
+
+extern "C" int fx_fasta_orfs(fx_handle *h, uint64_t stop_mask, uint64_t start_mask, int mode, int strands, int64_t min_len, const int64_t *ids,
+                             int64_t n_ids, int64_t max_rows, int64_t **rec, int64_t **start, int64_t **stop, int8_t **frame, uint8_t **flags,
+                             int64_t *n, int64_t *n_total) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !rec || !start || !stop || !frame || !flags || !n || !n_total) return fail(FX_EINVAL, "null argument");
+    *rec = *start = *stop = nullptr; *frame = nullptr; *flags = nullptr; *n = *n_total = 0;
+    if (mode != 0 && mode != 1) return fail(FX_EINVAL, "mode %d: 0 (stop to stop) or 1 (START to stop)", mode);
+    if (strands < 1 || strands > 3) return fail(FX_EINVAL, "strands %d outside 1..3", strands);
+    if (!stop_mask) return fail(FX_EINVAL, "no codon is a stop");
+    start_mask &= ~stop_mask;                              // where a codon is in both masks the stop wins
+    if (mode == 1 && !start_mask) return fail(FX_EINVAL, "no START codon that is not a stop");
+    if (min_len < 0) return fail(FX_EINVAL, "min_len must not be negative");
+    if (max_rows < 0) return fail(FX_EINVAL, "max_rows must not be negative");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    const OrfArg A{{stop_mask, orf_reverse_mask(stop_mask)}, {start_mask, orf_reverse_mask(start_mask)}, std::max<int64_t>(min_len, 3), mode, strands};
+    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    Staged st(h);
+    SearchPlan P, all;
+    RankIndex X;
+    rank_view(h, &all, &X);
+    P.n_runs = 0;
+    int64_t *d_tot = nullptr, land = 0, total = 0;
+    ScratchBuf<uint64_t> pk;                               // 6 rows of n_runs
+    ScratchBuf<uint32_t> closes;
+    ScratchBuf<int64_t> pref, list;                        // pref: NZ (12 components of n_runs + 1), O (n_runs + 1); list: 12 rows
+    int64_t *NZ = nullptr, *O = nullptr;
+    unsigned grid = 1;
+    if (n_sel > 0) {
+        if ((rc = fasta_run_plan(h, st, K_ORF_SCAN, ids, n_ids, 1, &P, &d_tot, &land))) return rc;
+        P.masks = nullptr;
+        if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one grid");
+    }
+    if (P.n_runs > 0) {
+        const int64_t nr1 = P.n_runs + 1;
+        if ((rc = pk.alloc(h->device, ORF_NC * P.n_runs, h->stream)) || (rc = closes.alloc(h->device, P.n_runs, h->stream)) ||
+            (rc = pref.alloc(h->device, (2 * ORF_NC + 1) * nr1, h->stream)) || (rc = list.alloc(h->device, 2 * ORF_NC * P.n_runs, h->stream)))
+            return rc;
+        NZ = pref.p; O = pref.p + 2 * ORF_NC * nr1;
+        grid = nblocks(P.n_runs, BLOCK);
+        FX_LAUNCH(h, K_ORF_COUNT, k_orf_count, dim3(grid), dim3(BLOCK), P, X, A, pk.p, closes.p);
+        if ((rc = sscan<2 * ORF_NC>(h, st, K_ORF_SCAN, OrfLdCarry{pk.p, P.n_runs}, P.n_runs, NZ, d_tot))) return rc;
+        FX_LAUNCH(h, K_ORF_SCAN, k_orf_list, dim3(grid), dim3(BLOCK), (const uint64_t *)pk.p, (const int64_t *)NZ, P.n_runs, list.p);
+        FX_LAUNCH(h, K_ORF_CLOSE, k_orf_close, dim3(grid), dim3(BLOCK), P, X, A, (const uint64_t *)pk.p, (const int64_t *)NZ, (const int64_t *)list.p, closes.p);
+        if ((rc = sscan<1>(h, st, K_ORF_SCAN, OrfLdCloses{closes.p}, P.n_runs, O, d_tot)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
+    }
+    *n_total = total;
+    if (total > max_rows) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "%lld open reading frames, more than the %lld asked for", (long long)total, (long long)max_rows);
+    }
+    PinnedOut<5> out(h);                                   // rec, start, stop, frame, flags
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8) || !out.alloc(3, m) || !out.alloc(4, m))
+        return fail(FX_ENOMEM, "pinned blocks for %lld open reading frames", (long long)total);
+    if (total == 0) h->prof.drain();
+    else {
+        ScratchBuf<int64_t> dev;                           // rec, start, stop
+        ScratchBuf<uint8_t> dev1;                          // frame, flags
+        if ((rc = dev.alloc(h->device, 3 * total, h->stream)) || (rc = dev1.alloc(h->device, 2 * total, h->stream))) return rc;
+        FX_LAUNCH(h, K_ORF_EMIT, k_orf_emit, dim3(grid), dim3(BLOCK), P, X, A, (const uint64_t *)pk.p, (const int64_t *)NZ, (const int64_t *)list.p,
+                  (const uint32_t *)closes.p, (const int64_t *)O, dev.p, dev.p + total, dev.p + 2 * total, (int8_t *)dev1.p, dev1.p + total);
+        if ((rc = home(h, "open reading frames", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, total * 8}, {out.p[2], dev.p + 2 * total, total * 8},
+                                                  {out.p[3], dev1.p, total}, {out.p[4], dev1.p + total, total}})))
+            return rc;
+    }
+    *n = total;
+    out.release(rec, start, stop, frame, flags);
+    return FX_OK;
+}
+
+extern "C" int fx_fasta_translate_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
+                                        const uint8_t *strand, const uint8_t *aa64, uint8_t unknown, uint8_t **dst, int64_t **dst_off,
+                                        int64_t *first_bad) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !aa64 || !dst || !dst_off || !first_bad) return fail(FX_EINVAL, "null argument");
+    *dst = nullptr; *dst_off = nullptr; *first_bad = -1;
+    if (n < 0 || (n > 0 && (!seq_id || !start || !stop))) return fail(FX_EINVAL, "null query array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for intervals across its cuts");
+    if ((rc = use_device(h)) || (rc = finish_build(h))) return rc;
+    if (n >= 0x7FFFFFFFll * (int64_t)SCAN_CHUNK) return fail(FX_ERANGE, "too many queries in one batch");
+    Staged st(h);
+    PinnedOut<2> out(h);                                   // the offsets, the amino acids
+    if (n == 0) {
+        if (!out.alloc(0, 16) || !out.alloc(1, 1)) return FX_ENOMEM;
+        out.as<int64_t>(0)[0] = 0;
+        out.release(dst_off, dst);
+        return FX_OK;
+    }
+    uint8_t tab[65];
+    memcpy(tab, aa64, 64);
+    tab[64] = unknown;
+    FetchQ q;
+    memset(&q, 0, sizeof q);
+    const uint8_t *d_strand = nullptr, *d_tab = nullptr;
+    st.reserve_pin(n * 8 * 3 + (strand ? n : 0) + 6 * 256);
+    if ((rc = st.up(h, seq_id, n, &q.seq_id)) || (rc = st.up(h, start, n, &q.start)) || (rc = st.up(h, stop, n, &q.stop)) ||
+        (rc = st.up(h, strand, n, &d_strand)) || (rc = st.up(h, (const uint8_t *)tab, (int64_t)65, &d_tab)))
+        return rc;
+    int32_t *d_cnt = nullptr, *d_cnt3 = nullptr;
+    int64_t *d_sums = nullptr, *d_noff = nullptr, *d_aoff = nullptr, *offs = nullptr;
+    BadFlag bad;
+    if ((rc = st.scratch<int32_t>(n, &d_cnt)) || (rc = st.scratch<int32_t>(n, &d_cnt3)) || (rc = st.scratch<int64_t>((n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1, &d_sums)) ||
+        (rc = st.scratch<int64_t>(n + 1, &d_noff)) || (rc = bad.arm(h, st)))
+        return rc;
+    hipLaunchKernelGGL(k_q_counts_fasta, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const int64_t *)h->fa_slen.p, h->n_hdr, q.seq_id, q.start,
+                       q.stop, n, d_cnt, bad.d);
+    hipLaunchKernelGGL(k_tr_counts, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const int32_t *)d_cnt, n, d_cnt3);
+    cnt_scan(h->stream, d_cnt, n, d_sums, d_noff);         // where the letters of a query go (device only)
+    if ((rc = offsets_of_counts(h, st, d_cnt3, bad.d, n, &d_aoff, &offs, first_bad))) return rc;
+    out.p[0] = offs;
+    if (*first_bad >= 0) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "query %lld: record id or interval outside the sequence", (long long)*first_bad);
+    }
+    int64_t letters = 0;                                   // every query is valid: what the scan of d_cnt ends in
+    for (int64_t i = 0; i < n; ++i) letters += stop[i] - start[i];
+    const int64_t total = offs[n];
+    uint8_t *d_nt = nullptr, *d_aa = nullptr;
+    if (!out.alloc(1, std::max<int64_t>(total, 1))) return FX_ENOMEM;
+    if ((rc = st.scratch<uint8_t>(std::max<int64_t>(letters, 1), &d_nt)) || (rc = st.scratch<uint8_t>(std::max<int64_t>(total, 1), &d_aa))) return rc;
+    q.dst_off = d_noff;
+    if (total > 0) {
+        if ((rc = fetch_launch(h, st, q, true, letters / n > 512, n, 0, d_nt))) return rc;
+        FX_LAUNCH(h, K_TR_TRANSLATE, k_tr_translate, dim3(nblocks(total, BLOCK)), dim3(BLOCK), (const uint8_t *)d_nt, (const int64_t *)d_noff,
+                  (const int64_t *)d_aoff, d_strand, n, d_tab, total, d_aa);
+        if ((rc = home(h, "translation", {{out.p[1], d_aa, total}}))) return rc;
+    } else h->prof.drain();
+    out.release(dst_off, dst);
     return FX_OK;
 }
 
