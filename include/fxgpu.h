@@ -557,6 +557,50 @@ int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const
                           int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept,
                           int64_t *first_bad);
 
+/* ------------------------------------------------------------------ barcode demultiplexing (extension)
+ * The reference has no counterpart.  Integer and exact (pyfastx_amd/csrc/fx_fastq_demux.hpp).  s, L and H are those of
+ * fx_fastq_trim / fx_fastq_format_alloc: s = the rlen bytes at soff, L = rlen, H = the dlen bytes at soff - dlen - 1 without one
+ * trailing '\r'; a byte past the end of the stream reads as 0.
+ *
+ * A SAMPLE has n_seg = 1 or 2 SEGMENTS.  Segment g has a source src[g], an offset off[g] >= 0, a length len[g] in 1..32, a
+ * mismatch budget mm[g] in 0..len[g] and, per sample, len[g] upper-case letters of A C G T N; `barcodes` holds n_samples
+ * (1..4096) rows of len[0] + len[1] letters, segment 0 first.  For each read, segment g gives a WINDOW of len[g] slots, each a
+ * byte or ABSENT:
+ *   FX_DEMUX_SEQ5    slot j is s[off + j] if off + j < L, else ABSENT.
+ *   FX_DEMUX_SEQ3    p = L - off - len + j; slot j is s[p] if 0 <= p < L, else ABSENT.
+ *   FX_DEMUX_HEADER  off is the part number, 0 or 1.  F = the longest suffix of H that holds no ':'.  If H holds no ':' at
+ *                    all, or F is longer than 65 bytes, every slot is ABSENT (nothing further back than 66 bytes is looked
+ *                    at).  Part 0 is F up to its first '+', or all of F if there is none; part 1 is what follows the first
+ *                    '+', empty if there is none.  Slot j is byte j of the part, ABSENT beyond its end; bytes of the part
+ *                    beyond len are ignored (a prefix compare).
+ * The distance of a sample's segment, d_g = the j whose barcode letter is not 'N' and whose slot is ABSENT or is not that exact
+ * byte (lower case, N and IUPAC codes in the read mismatch, as in fx_fastq_trim); with one segment d_1 = 0.  A sample PASSES
+ * when d_g <= mm[g] for each segment; its total is t = d_0 + d_1.  With t(1) <= t(2) the two smallest totals over the passing
+ * samples:
+ *   none passes                       sample = FX_DEMUX_NONE       dist = -1    second = -1
+ *   exactly one passes                sample = its index           dist = t(1)  second = -1
+ *   t(2) - t(1) >= margin (1..64)     sample = the one with t(1)   dist = t(1)  second = t(2)
+ *   otherwise (ties included)         sample = FX_DEMUX_AMBIGUOUS  dist = t(1)  second = t(2)
+ *
+ * fx_fastq_demux: one row of sample / dist / second per query, in the order of ids (ids = NULL: every read; repeats allowed);
+ *   counts[n_samples + 2] = the queries per sample, then NONE, then AMBIGUOUS; *n_rows = the rows.  want_order != 0: also
+ *   order[n] = the query positions sorted by (bin, position) -- the bin is the sample index, n_samples for NONE, n_samples + 1
+ *   for AMBIGUOUS -- and bin_off[n_samples + 3]: bin k is order[bin_off[k] .. bin_off[k + 1]); both are made on the device (a
+ *   stable radix sort on the bin, a scan of the counters) and take at most 2^31 queries.  want_order = 0: order and bin_off
+ *   may be NULL and are not made.  Outputs are pinned blocks of fx_pinned_alloc that belong to the caller, never NULL after
+ *   FX_OK.  States and errors are those of fx_fastq_trim (a null handle or output pointer: FX_EINVAL, nothing touched; before
+ *   fx_fastq_build: FX_ESTATE; a byte-range shard: FX_EINVAL; an id outside the table: *first_bad = its position, FX_ERANGE,
+ *   nothing allocated); an argument outside the ranges above or a barcode byte outside A C G T N: FX_EINVAL. */
+#define FX_DEMUX_SEQ5 0
+#define FX_DEMUX_SEQ3 1
+#define FX_DEMUX_HEADER 2
+#define FX_DEMUX_NONE (-1)
+#define FX_DEMUX_AMBIGUOUS (-2)
+int fx_fastq_demux(fx_handle *h, const int64_t *ids, int64_t n_ids, int32_t n_seg, const int32_t *src, const int32_t *off,
+                   const int32_t *len, const int32_t *mm, const uint8_t *barcodes, int32_t n_samples, int32_t margin,
+                   int32_t want_order, int32_t **sample, int32_t **dist, int32_t **second, int64_t **counts, int64_t **order,
+                   int64_t **bin_off, int64_t *n_rows, int64_t *first_bad);
+
 /* ------------------------------------------------------------------ paired-end FASTQ: mate overlap, merged records (extension)
  * The reference has no counterpart: it reads one file at a time.  h1 and h2 hold the two files of a paired run; pair i is read i
  * of h1 and read i of h2, with s1, q1, L1 and s2, q2, L2 the bytes fx_fastq_fetch returns for them (a byte past the end of a

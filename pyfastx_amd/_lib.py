@@ -51,7 +51,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_demux", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -243,6 +243,7 @@ def lib():
     L.fx_fastq_trim.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i64, i64, i32, i32, i64, i64, i32,
                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_format_alloc.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_fastq_demux.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, i32] + [C.POINTER(vp)] * 6 + [C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_pair_overlap.argtypes = [vp, vp, vp, i64, i32, i32, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_pair_merge_alloc.argtypes = [vp, vp, vp, i64, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
@@ -1295,6 +1296,32 @@ class Blob:
         o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
         tot = int(o[m])
         return pinned_array(pd.value, max(tot, 1))[:tot], o, int(kept.value)
+
+    def fastq_demux(self, barcodes, src, off, length, mm, margin=1, ids=None, want_order=True):
+        """Barcode demultiplexing (fx_fastq_demux) -> dict of pinned columns sample, dist, second (int32, one row per query in
+        the order of ids; None: every read), counts (int64[n_samples + 2]) and, with want_order, order (int64[n]) and
+        bin_off (int64[n_samples + 3]).  barcodes: uint8[n_samples, sum(length)], upper-case A C G T N; src / off / length /
+        mm: one entry per segment (1 or 2).  An id outside the table raises FxError(FX_ERANGE) with .first_bad."""
+        ids = None if ids is None else self._i64(ids)
+        bc = np.ascontiguousarray(barcodes, dtype=np.uint8)
+        seg = [np.ascontiguousarray(a, dtype=np.int32) for a in (src, off, length, mm)]
+        n_seg = int(seg[0].size)
+        if bc.ndim != 2 or any(a.ndim != 1 or a.size != n_seg for a in seg) or n_seg not in (1, 2) or bc.shape[1] != int(seg[2].sum()):
+            raise ValueError("barcodes must be n_samples rows of sum(length) letters, with one src / off / length / mm per segment")
+        n_samples = int(bc.shape[0])
+        cols = [C.c_void_p() for _ in range(6)]
+        n, bad = C.c_int64(0), C.c_int64(-1)
+        rc = lib().fx_fastq_demux(self._h, _ptr(ids), 0 if ids is None else ids.size, n_seg, *[_ptr(a) for a in seg], _ptr(bc), n_samples,
+                                  int(margin), 1 if want_order else 0, *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        m = int(n.value)
+        out = {k: pinned_array(c.value, max(m, 1), np.int32)[:m] for k, c in zip(("sample", "dist", "second"), cols)}
+        out["counts"] = pinned_array(cols[3].value, n_samples + 2, np.int64)
+        if want_order:
+            out["order"] = pinned_array(cols[4].value, max(m, 1), np.int64)[:m]
+            out["bin_off"] = pinned_array(cols[5].value, n_samples + 3, np.int64)
+        return out
 
     def fastq_pair_overlap(self, mate, ids=None, min_overlap=30, max_diff=5, err=(1, 5)):
         """The overlap of every pair (this blob: read 1, `mate`: read 2; fx_fastq_pair_overlap) -> dict of pinned columns diag,

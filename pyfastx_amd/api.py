@@ -2177,6 +2177,42 @@ class Fastq(_fxobj.FastqCore):
                 bases += int(ln[there].sum())
         return {"reads": int(kept), "bases": int(bases), "dropped": int(n - kept)}
 
+    def demux(self, samples, where="header", offset=0, mismatches=1, margin=1, revcomp=False, ids=None):
+        """Extension: barcode demultiplexing on the GPU from the resident stream (csrc/fx_fastq_demux.hpp) -> demux.Demux, one
+        row per id (0-based, any order, repeats allowed; None: every read).  samples: a mapping name -> barcode or name ->
+        (barcode, barcode), or a sequence of the same (names "0", "1", ...): 1..4096 samples of one or two segments, 1..32
+        letters of A C G T N each (N matches anything), the same lengths in every sample.  where: "5p" (the bases from
+        `offset` on), "3p" (the bases that end `offset` before the read's end) or "header" (part `offset`, 0 or 1, of the
+        index field behind the header's last ':', the parts split at '+'; a longer part is compared by its prefix), or one
+        per segment; two header segments with offset left at 0 are parts 0 and 1.  A sample passes when every segment has at
+        most `mismatches` (one value, or one per segment) letters that differ -- a missing base differs, no indels --; the
+        read goes to the passing sample with the smallest total, is unassigned when none passes and ambiguous when the
+        runner-up is fewer than `margin` mismatches behind.  revcomp (a bool, or one per segment) reverse-complements that
+        segment's barcodes first.  A bad id: IndexError; a bad argument: ValueError."""
+        from . import demux as _demux
+        args = _demux.demux_args(samples, where, offset, mismatches, margin, revcomp)
+        return _demux.demux_blob(self._qc_blob(), self._rlen_host, ids, args)
+
+    def demux_write(self, dm, pattern, unassigned=None, ambiguous=None, cut=False, min_len=0, batch_bytes=1 << 30):
+        """Extension: one file per sample of `dm` (what demux returned for this file) through write: `pattern` holds
+        "{sample}"; unassigned / ambiguous: a path for those reads, or None to drop them; cut=True writes the reads without
+        their inline barcodes (dm.intervals()).  A bin without reads gets no file -> {name: (path, records written)}, the
+        two extra bins under "unassigned" and "ambiguous"."""
+        from . import demux as _demux
+        if not isinstance(dm, _demux.Demux) or (dm._ids is None and len(dm) != self._rlen_host.size):
+            raise ValueError("dm must be what demux returned for this file")
+        start, end = dm.intervals() if cut else (None, None)
+        out = {}
+        for key, k, path in _demux.bin_paths(dm, pattern, unassigned, ambiguous):
+            pos = dm.positions(k)
+            if pos.size == 0:
+                continue
+            ids = pos if dm._ids is None else dm._ids[pos]
+            r = self.write(path, ids=ids, start=None if start is None else start[pos], end=None if end is None else end[pos],
+                           min_len=min_len, batch_bytes=batch_bytes)
+            out[key] = (path, r["reads"])
+        return out
+
 
     def raw_many(self, ids_or_names):
         """Batched `Read.raw` (read.c:124-150): whole four-line records, one gather for all of them.

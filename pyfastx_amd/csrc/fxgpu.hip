@@ -49,6 +49,7 @@
 #include "fx_orf.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
+#include "fx_fastq_demux.hpp"
 #include "fx_fastq_pair.hpp"
 #include "fx_kmer.hpp"
 #include "fx_kmer_table.hpp"
@@ -330,10 +331,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group"};
 
 struct Prof {
     bool on = false;
@@ -4605,6 +4606,113 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
     }
     out.release(dst, dst_off);
     *n_rows = n; *n_kept = kept;
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ barcode demultiplexing (fx_fastq_demux.hpp)
+// Extension: the reference has no counterpart.
+extern "C" int fx_fastq_demux(fx_handle *h, const int64_t *ids, int64_t n_ids, int32_t n_seg, const int32_t *src, const int32_t *off,
+                              const int32_t *len, const int32_t *mm, const uint8_t *barcodes, int32_t n_samples, int32_t margin,
+                              int32_t want_order, int32_t **sample, int32_t **dist, int32_t **second, int64_t **counts, int64_t **order,
+                              int64_t **bin_off, int64_t *n_rows, int64_t *first_bad) {
+    if (!h || !sample || !dist || !second || !counts || !n_rows || !first_bad || (want_order && (!order || !bin_off))) return fail(FX_EINVAL, "null argument");
+    *sample = *dist = *second = nullptr; *counts = nullptr; *n_rows = 0; *first_bad = -1;
+    if (order) *order = nullptr;
+    if (bin_off) *bin_off = nullptr;
+    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    if (!src || !off || !len || !mm || !barcodes) return fail(FX_EINVAL, "null argument");
+    if (n_seg < 1 || n_seg > 2) return fail(FX_EINVAL, "%d segments, not 1 or 2", (int)n_seg);
+    if (n_samples < 1 || n_samples > DEMUX_MAX_SAMPLES) return fail(FX_EINVAL, "%d samples outside 1..%d", (int)n_samples, DEMUX_MAX_SAMPLES);
+    if (margin < 1 || margin > 64) return fail(FX_EINVAL, "margin %d outside 1..64", (int)margin);
+    DemuxPar P{};
+    P.n_seg = n_seg; P.n_samples = n_samples; P.margin = margin;
+    int row = 0;
+    for (int g = 0; g < n_seg; ++g) {
+        if (src[g] < DEMUX_SEQ5 || src[g] > DEMUX_HEADER) return fail(FX_EINVAL, "segment %d: source %d", g, (int)src[g]);
+        if (off[g] < 0 || (src[g] == DEMUX_HEADER && off[g] > 1)) return fail(FX_EINVAL, "segment %d: offset %d", g, (int)off[g]);
+        if (len[g] < 1 || len[g] > DEMUX_MAX_LEN) return fail(FX_EINVAL, "segment %d: length %d outside 1..%d", g, (int)len[g], DEMUX_MAX_LEN);
+        if (mm[g] < 0 || mm[g] > len[g]) return fail(FX_EINVAL, "segment %d: %d mismatches outside 0..%d", g, (int)mm[g], (int)len[g]);
+        P.src[g] = src[g]; P.off[g] = off[g]; P.len[g] = len[g]; P.mm[g] = mm[g];
+        row += len[g];
+    }
+    std::vector<uint32_t> set((size_t)n_samples * DEMUX_SET_WORDS, 0u);      // packed as TrimPar::acode / acare
+    for (int s = 0; s < n_samples; ++s) {
+        const uint8_t *b = barcodes + (size_t)s * row;
+        for (int g = 0; g < n_seg; b += len[g], ++g)
+            for (int k = 0; k < len[g]; ++k) {
+                const uint8_t c = b[k];
+                if (c != 'A' && c != 'C' && c != 'G' && c != 'T' && c != 'N')
+                    return fail(FX_EINVAL, "sample %d, segment %d: letter %d is not one of A C G T N", s, g, k);
+                if (c != 'N') {
+                    uint32_t *w = &set[(size_t)s * DEMUX_SET_WORDS + 4 * g];
+                    w[k >> 4] |= (uint32_t)((c >> 1) & 3) << (2 * (k & 15));
+                    w[2 + (k >> 4)] |= 1u << (2 * (k & 15));
+                }
+            }
+    }
+    FqLaunch q;
+    int rc = fq_prepare(h, 0, 0, &q);
+    if (!rc) rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
+    if (rc) return rc;
+    const int64_t n = ids ? n_ids : h->n_reads;
+    if (want_order && n > (1ll << 31)) return fail(FX_EINVAL, "the grouping takes at most 2^31 queries");
+    const int64_t m = std::max<int64_t>(n, 1);
+    const int nb = n_samples + 2;
+    PinnedOut<6> out(h);
+    if (!out.alloc(0, m * 4) || !out.alloc(1, m * 4) || !out.alloc(2, m * 4) || !out.alloc(3, (int64_t)nb * 8) ||
+        (want_order && (!out.alloc(4, m * 8) || !out.alloc(5, (int64_t)(nb + 1) * 8))))
+        return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n);
+    memset(out.p[3], 0, (size_t)nb * 8);
+    if (want_order) memset(out.p[5], 0, (size_t)(nb + 1) * 8);
+    if (n > 0) {
+        Staged st(h);
+        st.reserve_pin((ids ? n_ids : 0) * 8 + (int64_t)set.size() * 4 + 1024);
+        const int64_t *d_ids = nullptr;
+        const uint32_t *d_set = nullptr;
+        if ((rc = st.up(h, ids, ids ? n_ids : 0, &d_ids)) || (rc = st.up(h, set.data(), (int64_t)set.size(), &d_set))) return rc;
+        ScratchBuf<int32_t> cols;                           // sample, dist, second
+        ScratchBuf<unsigned long long> cnt;                 // the bins, then bin_off
+        ScratchBuf<uint64_t> key[2];
+        ScratchBuf<uint32_t> val[2], hist, totals;
+        ScratchBuf<int64_t> ord;
+        if ((rc = cols.alloc(h->device, 3 * n, h->stream)) || (rc = cnt.alloc(h->device, 2 * nb + 1, h->stream))) return rc;
+        RadixScratch rs;
+        if (want_order) {
+            rs.nblk = radix_tiles(n);
+            if ((rc = key[0].alloc(h->device, n, h->stream)) || (rc = key[1].alloc(h->device, n, h->stream)) || (rc = val[0].alloc(h->device, n, h->stream)) ||
+                (rc = val[1].alloc(h->device, n, h->stream)) || (rc = hist.alloc(h->device, rs.nblk * 256, h->stream)) ||
+                (rc = totals.alloc(h->device, 256, h->stream)) || (rc = ord.alloc(h->device, n, h->stream)))
+                return rc;
+            rs.hist = hist.p; rs.totals = totals.p;
+        }
+        HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)nb * 8, h->stream));
+        const FqView v = fq_view(h);
+        with_int<1>(P.len[0] > 16 || P.len[1] > 16, [&](auto WIDE) {      // words of a window the kernel compares: one, or two
+            static const int64_t resident = resident_blocks(h, k_fq_demux<WIDE() != 0>);
+            FX_LAUNCH(h, K_FQ_DEMUX, k_fq_demux<WIDE() != 0>, dim3((unsigned)std::min<int64_t>(nblocks(n, BLOCK), resident)), dim3(BLOCK), v.data, v.base, v.n,
+                      v.rlen, v.soff, v.dlen, d_ids, n, P, d_set, DemuxOut{cols.p, cols.p + n, cols.p + 2 * n, cnt.p, key[0].p, val[0].p});
+        });
+        int cur = 0;
+        if (want_order) {
+            uint64_t *kp[2] = {key[0].p, key[1].p};
+            uint32_t *vp[2] = {val[0].p, val[1].p};
+            int bits = 1;
+            while ((1 << bits) < nb) ++bits;
+            h->prof.begin(K_FQ_DEMUX_GROUP, h->stream);
+            const hipError_t e = radix_sort_rows(kp, vp, cur, n, bits, rs, h->stream);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_fq_demux_bins, dim3(1), dim3(BLOCK), 0, h->stream, (const unsigned long long *)cnt.p, nb, (int64_t *)(cnt.p + nb));
+                hipLaunchKernelGGL(k_fq_demux_order, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, h->stream, (const uint32_t *)vp[cur], n, ord.p);
+            }
+            h->prof.end(h->stream);
+            if (e != hipSuccess) return fail(FX_EDEVICE, "demux grouping: %s", hipGetErrorString(e));
+        }
+        if ((rc = home(h, "demux", {{out.p[0], cols.p, n * 4}, {out.p[1], cols.p + n, n * 4}, {out.p[2], cols.p + 2 * n, n * 4}, {out.p[3], cnt.p, (int64_t)nb * 8},
+                                    {out.p[4], ord.p, want_order ? n * 8 : 0}, {out.p[5], cnt.p + nb, want_order ? (int64_t)(nb + 1) * 8 : 0}})))
+            return rc;
+    }
+    out.release(sample, dist, second, counts, order, bin_off);
+    *n_rows = n;
     return FX_OK;
 }
 

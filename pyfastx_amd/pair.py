@@ -185,6 +185,38 @@ class FastqPair:
             raise RuntimeError("the two files fell out of step (%d, %d records for %d pairs)" % (r1["reads"], r2["reads"], q.size))
         return {"pairs": int(q.size), "bases1": r1["bases"], "bases2": r2["bases"], "dropped": int(n - q.size)}
 
+    def demux(self, samples, mate=1, **demux_kwargs):
+        """Fastq.demux on one mate (1 or 2) with its arguments -> demux.Demux; it remembers the mate for demux_write."""
+        if mate not in (1, 2) or isinstance(mate, bool):
+            raise ValueError("mate must be 1 or 2")
+        dm = (self.fq1 if mate == 1 else self.fq2).demux(samples, **demux_kwargs)
+        dm.mate = mate
+        return dm
+
+    def demux_write(self, dm, pattern1, pattern2, unassigned=None, ambiguous=None, cut=False, min_len=0, batch_bytes=1 << 30):
+        """Both mates of every bin of `dm` through write, in step: pattern1 / pattern2 hold "{sample}"; unassigned / ambiguous:
+        a pair of paths, or None to drop those pairs; cut=True takes the inline barcodes off the mate that was looked at ->
+        {name: (path1, path2, pairs written)}."""
+        from . import demux as _demux
+        if not isinstance(dm, _demux.Demux) or (dm._ids is None and len(dm) != len(self)):
+            raise ValueError("dm must be what demux returned for this pair")
+        for extra in (unassigned, ambiguous):
+            if extra is not None and (not isinstance(extra, (tuple, list)) or len(extra) != 2):
+                raise ValueError("unassigned / ambiguous: a pair of paths, or None")
+        two = lambda k: (None, None) if (unassigned, ambiguous)[k] is None else (unassigned, ambiguous)[k]
+        bins1 = _demux.bin_paths(dm, pattern1, two(0)[0], two(1)[0])
+        bins2 = _demux.bin_paths(dm, pattern2, two(0)[1], two(1)[1])
+        start, end = dm.intervals() if cut else (None, None)
+        out = {}
+        for (key, k, path1), (_, _, path2) in zip(bins1, bins2):
+            pos = dm.positions(k)
+            if pos.size == 0:
+                continue
+            cutk = {} if start is None else {"start%d" % dm.mate: start[pos], "end%d" % dm.mate: end[pos]}
+            r = self.write(path1, path2, ids=pos if dm._ids is None else dm._ids[pos], min_len=min_len, batch_bytes=batch_bytes, **cutk)
+            out[key] = (path1, path2, r["pairs"])
+        return out
+
     def write_merged(self, path, ids=None, diag=None, min_len=0, batch_bytes=1 << 30):
         """The records of merge written to the plain file `path`, in batches of consecutive queries whose upper bound fits
         batch_bytes of pinned memory -> {"merged": records written, "bases": their bases, "unmerged": the ids (int64) of the
