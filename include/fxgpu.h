@@ -353,6 +353,34 @@ int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const uint8_t *rpat
                            uint64_t anchor, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
                            uint8_t **strand, uint8_t **mismatch, int64_t *n_hits, int64_t *counts);
 
+/* ------------------------------------------------------------------ position weight matrices
+ * Extension.  Every window of plen letters of the `seq` of the records -- the text fx_fasta_search walks, with its rules:
+ * bytes 10/13/32 dropped, windows across line ends and never across records, cut at slen -- whose SCORE under one position
+ * weight matrix is at least min_score, on one or both strands, with its score; and the best-scoring window of every record
+ * (pyfastx_amd/csrc/fx_pwm.hpp: a 2-bit history per lane, score tables of four letters at a time in LDS).
+ *   Letters      A C G T in either case and U / u (= T) are the columns 0..3.  Every other kept byte (N, IUPAC codes, '*',
+ *                '-', ...) makes every window that holds it unscorable: no hit, no part in a best score.
+ *   mat, plen    int32 [plen][4], row j = position j of the motif, columns A C G T; 1 <= plen <= 64, every entry in
+ *                -32767..32767.  All scores are exact integers, below 2^21 in size.
+ *   Scores       '+': sum_j mat[j][x[start + j]].  '-': the score of the window's reverse complement under the same matrix,
+ *                sum_j mat[plen - 1 - j][3 - x[start + j]] (the library derives the reverse matrix).  start is the 0-based
+ *                start on the forward strand for both strands, stop = start + plen.
+ *   mode         FX_SEARCH_PLUS | FX_SEARCH_MINUS, nothing else.
+ *   fx_fasta_pwm_scan   the windows with score >= min_score, by (record, start), '+' before '-' at one start.  ids, n_ids,
+ *                cap, rec, start, strand, n_hits, counts: as for fx_fasta_search; score: a fourth pinned block beside rec /
+ *                start / strand, the int32 score of every hit.
+ *   fx_fasta_pwm_best   per searched record k (ids in any order; NULL: all) and strand s (0 '+', 1 '-'): best_score[2k + s]
+ *                the largest score of a scorable window, best_start[2k + s] the smallest start that has it.  A record without
+ *                a scorable window, and a strand that was not asked for, get INT32_MIN and -1.  Host arrays of the caller.
+ * FX_EINVAL: plen outside 1..64, a null matrix, an entry outside -32767..32767, a mode bit other than the two strands, no
+ * strand (these are refused before the handle is looked at), a null output, a byte-range shard.  FX_ESTATE: no table built.
+ * FX_ERANGE: more than cap hits, *n_hits = their number, nothing allocated. */
+int fx_fasta_pwm_scan(fx_handle *h, const int32_t *mat, int32_t plen, int mode, int32_t min_score, const int64_t *ids, int64_t n_ids,
+                      int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int32_t **score, int64_t *n_hits,
+                      int64_t *counts);
+int fx_fasta_pwm_best(fx_handle *h, const int32_t *mat, int32_t plen, int mode, const int64_t *ids, int64_t n_ids, int32_t *best_score,
+                      int64_t *best_start);
+
 /* ------------------------------------------------------------------ regions, windows, class runs
  * Composition of intervals of the records, and the maximal runs of a letter class (pyfastx_amd/csrc/fx_annot.hpp).  The text
  * of a record is the one fx_fasta_search walks: the bytes of [boff, boff + blen) with 10 / 13 / 32 dropped, cut at slen; the

@@ -862,6 +862,37 @@ class Fasta(_fxobj.FastaCore):
         blob = self._search_blob()
         return search.approx_count_blob(blob, pattern, mismatches, anchor, strand, degenerate, self._uppercase, self._st.device)
 
+    def pwm_scan(self, pwm, min_score=None, threshold=None, pvalue=None, strand="both", ids=None, max_hits=10**8):
+        """Extension: every window of len(pwm) letters of a record's `seq` whose score under the position weight matrix
+        `pwm` (pwm.Pwm) reaches a threshold, on strand '+', '-' or 'both'.  Letters A C G T in either case, U = T
+        (uppercase= plays no part); a window that holds any other byte (N, IUPAC codes, ...) has no score; windows run
+        across line ends, never across records.  The '-' score of a window is the score of its reverse complement.
+        Exactly one threshold: min_score (integer units of pwm.ints), threshold (units of the float matrix: a hit iff the
+        integer score is >= ceil(threshold * pwm.scale - 1e-9)) or pvalue (pwm.threshold_for_pvalue).  -> PwmHits(ids,
+        starts, stops, strands, scores): SearchHits' columns and order plus the int32 score of every hit
+        (pwm.to_float for float units).  ids, max_hits: as for search_all.  On the GPU from the resident stream
+        (csrc/fx_pwm.hpp)."""
+        from . import pwm as _pwm
+        t = _pwm.resolve_min_score(pwm, min_score, threshold, pvalue)
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        return _pwm.scan_blob(self._search_blob(), pwm, t, strand, sel, max_hits)
+
+    def pwm_counts(self, pwm, min_score=None, threshold=None, pvalue=None, strand="both"):
+        """Extension: hits of pwm_scan per record -> int64[len(fa), 2] (column 0 '+', column 1 '-'); the hits themselves
+        are never materialised."""
+        from . import pwm as _pwm
+        t = _pwm.resolve_min_score(pwm, min_score, threshold, pvalue)
+        return _pwm.count_blob(self._search_blob(), pwm, t, strand)
+
+    def pwm_best(self, pwm, strand="both", ids=None):
+        """Extension: the best-scoring window of every record under `pwm` -> PwmBest(scores int32[n, 2], starts int64[n, 2]),
+        column 0 '+', column 1 '-', one row per record -- or per entry of ids (names or 0-based ids), in the order given.
+        The largest score, and the smallest start that has it; (INT32_MIN, -1) for a record without a scorable window and
+        for a strand that was not asked for."""
+        from . import pwm as _pwm
+        sel = None if ids is None else self._ids_of(ids)
+        return _pwm.best_blob(self._search_blob(), pwm, strand, sel)
+
     def kmer_counts(self, k, canonical=False, ids=None):
         """Extension: the k-mer spectrum of the `seq` of every record -> int64[4**k] in pinned memory, counted on the GPU
         from the resident stream (csrc/fx_kmer.hpp).  Letters A C G T in either case (A = 0, C = 1, G = 2, T = 3; uppercase=

@@ -44,6 +44,7 @@
 #include "fx_kseq.hpp"
 #include "fx_search.hpp"
 #include "fx_search_approx.hpp"
+#include "fx_pwm.hpp"
 #include "fx_annot.hpp"
 #include "fx_tandem.hpp"
 #include "fx_orf.hpp"
@@ -331,10 +332,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best"};
 
 struct Prof {
     bool on = false;
@@ -3913,6 +3914,164 @@ extern "C" int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const ui
         return fail(FX_EINVAL, "max_mismatch %d outside 0..%d", (int)max_mismatch, std::min(8, plen - 1));
     if (plen < 64 && (anchor >> plen)) return fail(FX_EINVAL, "anchor position at or above the pattern length %d", (int)plen);
     return fasta_search(h, pat, rpat, plen, mode, max_mismatch, anchor, ids, n_ids, cap, rec, start, strand, mismatch, n_hits, counts);
+}
+
+// ------------------------------------------------------------------ position weight matrices (fx_pwm.hpp)
+// What the numbers alone decide: refused before the handle is looked at.
+static int pwm_check(const int32_t *mat, int32_t plen, int mode) {
+    if (plen < 1 || plen > 64) return fail(FX_EINVAL, "matrix length %d outside 1..64", (int)plen);
+    if (!mat) return fail(FX_EINVAL, "null matrix");
+    for (int i = 0; i < plen * 4; ++i)
+        if (mat[i] < -32767 || mat[i] > 32767) return fail(FX_EINVAL, "matrix entry %d at position %d outside -32767..32767", (int)mat[i], i / 4);
+    if (mode & ~(FX_SEARCH_PLUS | FX_SEARCH_MINUS)) return fail(FX_EINVAL, "mode bits other than the two strands");
+    if (!(mode & (FX_SEARCH_PLUS | FX_SEARCH_MINUS))) return fail(FX_EINVAL, "no strand selected");
+    return FX_OK;
+}
+// The G = ceil(W / 4) score tables: entry [g][code8] = the partial scores of the history positions 4g .. 4g + 3 (position p of
+// the history, newest first, is position W - 1 - p of the window; the reverse strand reads mat[p][3 - code] there).
+static std::vector<int2> pwm_tables(const int32_t *mat, int W) {
+    const int G = (W + 3) / 4;
+    std::vector<int2> t((size_t)G * 256);
+    for (int g = 0; g < G; ++g)
+        for (int c8 = 0; c8 < 256; ++c8) {
+            int32_t f = 0, r = 0;
+            for (int q = 0; q < 4; ++q) {
+                const int p = 4 * g + q, c = (c8 >> (2 * q)) & 3;
+                if (p >= W) break;
+                f += mat[(W - 1 - p) * 4 + c];
+                r += mat[p * 4 + (3 - c)];
+            }
+            t[(size_t)g * 256 + c8] = make_int2(f, r);
+        }
+    return t;
+}
+// f(G) for the group count of this call, 1..16 (k_pwm_count alone has a G = 0 form)
+template <class F> static void with_groups(int G, F &&f) {
+    with_int<16>(G, [&](auto N) { if constexpr (decltype(N)::value > 0) f(N); });
+}
+
+// Both matrix entries.  best_score != null: the per-record maximum (fx_fasta_pwm_best); otherwise the scan.  The plan, the
+// scans, the cut, the list and the way home are fasta_search's.
+static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, int32_t min_score, const int64_t *ids, int64_t n_ids,
+                     int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int32_t **score, int64_t *n_hits, int64_t *counts,
+                     int32_t *best_score, int64_t *best_start) {
+    const bool best = best_score != nullptr;
+    if (n_hits) *n_hits = 0;
+    if (rec) *rec = nullptr; if (start) *start = nullptr; if (strand) *strand = nullptr; if (score) *score = nullptr;
+    int rc = pwm_check(mat, plen, mode);
+    if (rc) return rc;
+    if (!h || (!best && !n_hits)) return fail(FX_EINVAL, "null argument");
+    const bool counts_only = cap == 0 && counts;
+    if (best ? !best_start : (cap < 0 || (!counts_only && (!rec || !start || !strand || !score)))) return fail(FX_EINVAL, "null output");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for hits across its cuts");
+    rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (rc) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    if (n_sel == 0) return FX_OK;
+    for (int64_t i = 0; best && i < 2 * n_sel; ++i) { best_score[i] = INT32_MIN; best_start[i] = -1; }
+    const std::vector<int2> tab = pwm_tables(mat, plen);
+    const int G = (plen + 3) / 4;
+    Staged st(h);
+    SearchPlan P;
+    PwmArg A{nullptr, (mode & FX_SEARCH_PLUS) ? (best ? 0 : min_score) : PWM_NEVER, (mode & FX_SEARCH_MINUS) ? (best ? 0 : min_score) : PWM_NEVER};
+    if ((rc = st.up(h, tab.data(), (int64_t)tab.size(), &A.tab))) return rc;
+    P.masks = nullptr;
+    int64_t *tot = (int64_t *)fx_pinned_alloc(64), *d_tot = nullptr;        // tot: where the totals of the scans land
+    if (!tot) return FX_ENOMEM;
+    std::unique_ptr<int64_t, void (*)(int64_t *)> tot_guard(tot, [](int64_t *p) { fx_pinned_free(p); });
+    // 1. runs of every selected record -> run0
+    if ((rc = fasta_run_plan(h, st, K_SEARCH_SCAN, ids, n_ids, plen, &P, &d_tot, tot))) return rc;
+    if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one search grid");
+    if (P.n_runs == 0) {                       // nothing but empty records
+        if (counts) memset(counts, 0, (size_t)n_sel * 16);
+        return FX_OK;
+    }
+    ScratchBuf<uint32_t> packed;
+    ScratchBuf<int64_t> pref;                  // K, Pp, Pm, NZ: 4 x (n_runs + 1) (the best: K alone)
+    const int64_t nr1 = P.n_runs + 1;
+    if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, (best ? 1 : 4) * nr1, h->stream))) return rc;
+    int64_t *K = pref.p, *Pp = pref.p + nr1, *Pm = pref.p + 2 * nr1, *NZ = pref.p + 3 * nr1;
+    const unsigned grid_runs = nblocks(P.n_runs, BLOCK), grid_sel = nblocks(n_sel, BLOCK);
+    if (best) {
+        // 2b. kept bytes per run, their scan, then the best window of every run in front of the cut, reduced per record
+        unsigned long long *keys = nullptr;
+        if ((rc = st.scratch<unsigned long long>(2 * n_sel, &keys))) return rc;
+        HIPCHK(hipMemsetAsync(keys, 0, (size_t)n_sel * 16, h->stream));
+        FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<0>, dim3(grid_runs), dim3(BLOCK), P, A, packed.p);
+        if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{packed.p}, P.n_runs, K, d_tot))) return rc;
+        with_groups(G, [&](auto N) {
+            FX_LAUNCH(h, K_PWM_BEST, k_pwm_best<decltype(N)::value>, dim3(grid_runs), dim3(BLOCK), P, A, (const int64_t *)K, keys);
+        });
+        std::vector<unsigned long long> hk((size_t)(2 * n_sel));
+        if ((rc = home(h, "pwm best", {{hk.data(), keys, n_sel * 16}}))) return rc;
+        for (int64_t i = 0; i < 2 * n_sel; ++i)
+            if (hk[(size_t)i]) {
+                best_score[i] = (int32_t)((int64_t)(hk[(size_t)i] >> PWM_START_BITS) - PWM_BIAS);
+                best_start[i] = (((int64_t)1 << PWM_START_BITS) - 1) - (int64_t)(hk[(size_t)i] & (((unsigned long long)1 << PWM_START_BITS) - 1));
+            }
+        return FX_OK;
+    }
+    // 2. count pass, kept-byte scan, the cut at slen, hit scans
+    with_groups(G, [&](auto N) { FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<decltype(N)::value>, dim3(grid_runs), dim3(BLOCK), P, A, packed.p); });
+    if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{packed.p}, P.n_runs, K, d_tot))) return rc;
+    with_groups(G, [&](auto N) {
+        FX_LAUNCH(h, K_SEARCH_SCAN, k_pwm_fix<decltype(N)::value>, dim3(grid_sel), dim3(BLOCK), P, A, (const int64_t *)K, packed.p);
+    });
+    if ((rc = sscan<3>(h, st, K_SEARCH_SCAN, SrchLdHits{packed.p}, P.n_runs, Pp, d_tot))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
+    if (counts) {
+        int64_t *cnt_dev = nullptr;
+        if ((rc = st.scratch<int64_t>(2 * n_sel, &cnt_dev))) return rc;
+        FX_LAUNCH(h, K_SEARCH_SCAN, k_search_rec_counts, dim3(grid_sel), dim3(BLOCK), (const int64_t *)P.run0, n_sel, (const int64_t *)Pp,
+                  (const int64_t *)Pm, cnt_dev);
+        HIPCHK(hipMemcpyAsync(counts, cnt_dev, (size_t)n_sel * 16, hipMemcpyDeviceToHost, h->stream));
+    }
+    if ((rc = read_home(h, tot, d_tot, 24))) return rc;
+    const int64_t total = tot[0] + tot[1], n_list = tot[2];
+    *n_hits = total;
+    if (counts_only) { h->prof.drain(); return FX_OK; }
+    if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
+    // 3. emit: the runs with hits, at their offsets; the answers home by DMA into pinned blocks
+    PinnedOut<4> out(h);                       // rec, start, strand, score
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m) || !out.alloc(3, m * 4))
+        return fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total);
+    if (total == 0) h->prof.drain();
+    else {
+        ScratchBuf<int64_t> out64, list;
+        ScratchBuf<int32_t> out32;
+        ScratchBuf<uint8_t> out8;
+        if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out32.alloc(h->device, total, h->stream)) ||
+            (rc = out8.alloc(h->device, total, h->stream)) || (rc = list.alloc(h->device, n_list, h->stream)))
+            return rc;
+        hipLaunchKernelGGL(k_search_list, dim3(grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
+        with_groups(G, [&](auto N) {
+            FX_LAUNCH(h, K_PWM_EMIT, k_pwm_emit<decltype(N)::value>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, A, (const int64_t *)list.p, n_list,
+                      (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p, out32.p);
+        });
+        if ((rc = home(h, "pwm emit", {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], out8.p, total},
+                                       {out.p[3], out32.p, total * 4}})))
+            return rc;
+    }
+    out.release(rec, start, strand, score);
+    return FX_OK;
+}
+
+extern "C" int fx_fasta_pwm_scan(fx_handle *h, const int32_t *mat, int32_t plen, int mode, int32_t min_score, const int64_t *ids,
+                                 int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int32_t **score,
+                                 int64_t *n_hits, int64_t *counts) {
+    return fasta_pwm(h, mat, plen, mode, min_score, ids, n_ids, cap, rec, start, strand, score, n_hits, counts, nullptr, nullptr);
+}
+
+extern "C" int fx_fasta_pwm_best(fx_handle *h, const int32_t *mat, int32_t plen, int mode, const int64_t *ids, int64_t n_ids,
+                                 int32_t *best_score, int64_t *best_start) {
+    int rc = pwm_check(mat, plen, mode);
+    if (rc) return rc;
+    if (!best_score || !best_start) return fail(FX_EINVAL, "null output");
+    return fasta_pwm(h, mat, plen, mode, 0, ids, n_ids, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, best_score, best_start);
 }
 
 // ------------------------------------------------------------------ regions, windows, class runs (fx_annot.hpp)
