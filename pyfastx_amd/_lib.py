@@ -404,6 +404,11 @@ def pinned_array(ptr, count, dtype=np.uint8):
     return np.frombuffer(owner, dtype=dt, count=int(count))
 
 
+def _pinned_columns(ptrs, dtypes, t):
+    """The pinned blocks an entry handed out (c_void_p, at least one item each) -> the arrays over their first t items."""
+    return tuple(pinned_array(p.value, max(t, 1), dt)[:t] for p, dt in zip(ptrs, dtypes))
+
+
 def pinned_empty(count, dtype=np.uint8):
     """numpy array of `count` items in pinned host memory (fx_pinned_alloc): query arrays built in it go to the device
     without a staging copy, answers written into it arrive by DMA."""
@@ -1079,13 +1084,7 @@ class Blob:
         cap = 0 with counts: counts only.  (max_mismatch, anchor: how fasta_search_approx comes through here.)"""
         plen = len(pattern if pattern is not None else rpattern)
         ids = None if ids is None else self._i64(ids)
-        if ids is not None:
-            n_sel = ids.size
-        else:
-            n_sel = getattr(self, "_n_fasta", None)
-            if n_sel is None:
-                n_sel = int(self.fasta_build_end().n_seq)     # a build was only enqueued: wait for it, learn the count
-        cnt = np.zeros((n_sel, 2), dtype=np.int64) if counts else None
+        cnt = np.zeros((self._n_selected(ids), 2), dtype=np.int64) if counts else None
         pat = None if pattern is None else np.frombuffer(bytes(pattern), dtype=np.uint8)
         rpat = None if rpattern is None else np.frombuffer(bytes(rpattern), dtype=np.uint8)
         rec, st, sd, mm, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
@@ -1098,14 +1097,9 @@ class Blob:
                                               C.byref(mm), C.byref(n), _ptr(cnt))
         if rc:
             _raise(rc, n_hits=int(n.value))
-        total = int(n.value)
-        hits = None
-        if rec.value:
-            hits = (pinned_array(rec.value, max(total, 1), np.int64)[:total], pinned_array(st.value, max(total, 1), np.int64)[:total],
-                    pinned_array(sd.value, max(total, 1), np.uint8)[:total])
-            if max_mismatch is not None:
-                hits += (pinned_array(mm.value, max(total, 1), np.uint8)[:total],)
-        return total, hits, cnt
+        cols = (rec, st, sd) if max_mismatch is None else (rec, st, sd, mm)
+        hits = _pinned_columns(cols, (np.int64, np.int64, np.uint8, np.uint8), int(n.value)) if rec.value else None
+        return int(n.value), hits, cnt
 
     def fasta_search_approx(self, pattern, rpattern, mode, max_mismatch, anchor=0, ids=None, cap=0, counts=False):
         """fasta_search with up to max_mismatch mismatching letters per hit, none of them at a position whose bit is set in
@@ -1133,12 +1127,8 @@ class Blob:
                                      int(cap), C.byref(rec), C.byref(st), C.byref(sd), C.byref(sc), C.byref(n), _ptr(cnt))
         if rc:
             _raise(rc, n_hits=int(n.value))
-        total = int(n.value)
-        hits = None
-        if rec.value:
-            hits = (pinned_array(rec.value, max(total, 1), np.int64)[:total], pinned_array(st.value, max(total, 1), np.int64)[:total],
-                    pinned_array(sd.value, max(total, 1), np.uint8)[:total], pinned_array(sc.value, max(total, 1), np.int32)[:total])
-        return total, hits, cnt
+        hits = _pinned_columns((rec, st, sd, sc), (np.int64, np.int64, np.uint8, np.int32), int(n.value)) if rec.value else None
+        return int(n.value), hits, cnt
 
     def fasta_pwm_best(self, mat, mode, ids=None):
         """The best-scoring window of every selected record and strand (fx_fasta_pwm_best) -> (scores int32[n_sel, 2],
@@ -1185,8 +1175,7 @@ class Blob:
         if rc:
             _raise(rc, n_rows=int(n.value))
         t = int(n.value)
-        rec, a, b = (pinned_array(p.value, max(t, 1), np.int64)[:t] for p in out[:3])
-        return rec, a, b, pinned_array(out[3].value, max(t, 1) * 7, np.int64)[:t * 7].reshape(t, 7)
+        return _pinned_columns(out[:3], [np.int64] * 3, t) + (pinned_array(out[3].value, max(t, 1) * 7, np.int64)[:t * 7].reshape(t, 7),)
 
     def fasta_class_runs(self, set32, min_len=1, ids=None, cap=10**8):
         """Every maximal interval of letters of the 256-bit set `set32` (32 bytes) of at least min_len letters
@@ -1202,8 +1191,7 @@ class Blob:
                                        *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
         if rc:
             _raise(rc, n_rows=int(tot.value))
-        t = int(n.value)
-        return tuple(pinned_array(p.value, max(t, 1), np.int64)[:t] for p in out)
+        return _pinned_columns(out, [np.int64] * 3, int(n.value))
 
     def fasta_tandem_repeats(self, min_copies, min_len=0, ids=None, cap=10**8):
         """The perfect tandem repeats of period 1..len(min_copies) <= 8 (fx_fasta_tandem_repeats): min_copies[p - 1] copies at
@@ -1217,8 +1205,7 @@ class Blob:
                                            int(cap), *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
         if rc:
             _raise(rc, n_rows=int(tot.value))
-        t = int(n.value)
-        return tuple(pinned_array(p.value, max(t, 1), dt)[:t] for p, dt in zip(out, (np.int64, np.int64, np.int64, np.uint8, np.uint32)))
+        return _pinned_columns(out, (np.int64, np.int64, np.int64, np.uint8, np.uint32), int(n.value))
 
     def fasta_orfs(self, stop_mask, start_mask, mode=1, strands=3, min_len=0, ids=None, cap=10**8):
         """The open reading frames of the six frames (fx_fasta_orfs): masks by codon index 16 c0 + 4 c1 + c2 in A C G T order,
@@ -1232,8 +1219,7 @@ class Blob:
                                  0 if ids is None else ids.size, int(cap), *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
         if rc:
             _raise(rc, n_rows=int(tot.value))
-        t = int(n.value)
-        return tuple(pinned_array(p.value, max(t, 1), dt)[:t] for p, dt in zip(out, (np.int64, np.int64, np.int64, np.int8, np.uint8)))
+        return _pinned_columns(out, (np.int64, np.int64, np.int64, np.int8, np.uint8), int(n.value))
 
     def fasta_translate_alloc(self, seq_id, start, stop, aa64, strand=None, unknown=ord("X")):
         """(record id, start, stop) batches translated by the 64-byte table aa64 (fx_fasta_translate_alloc; strand: None or one

@@ -3775,9 +3775,95 @@ template <class F> static void with_levels(int d, F &&f) {
     else f(std::integral_constant<int, 9>{});
 }
 
+// The head of every pass that looks for windows (exact, approximate and matrix search, the matrix's best window): the pinned
+// words the totals of the scans land in, the plan over the runs of the selected records, one packed word per run and n_pref
+// prefix arrays of n_runs + 1.  P.n_runs == 0 afterwards: nothing but empty records, and `counts` (where given) is zeroed.
+struct HitRuns {
+    SearchPlan P;
+    std::unique_ptr<int64_t, void (*)(void *)> tot{nullptr, fx_pinned_free};
+    int64_t *d_tot = nullptr, nr1 = 1;
+    ScratchBuf<uint32_t> packed;
+    ScratchBuf<int64_t> pref;
+    unsigned grid_runs = 1;
+    int open(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int n_pref, int64_t *counts) {
+        int rc;
+        tot.reset((int64_t *)fx_pinned_alloc(64));
+        if (!tot) return FX_ENOMEM;
+        P.masks = masks;
+        if ((rc = fasta_run_plan(h, st, K_SEARCH_SCAN, ids, n_ids, plen, &P, &d_tot, tot.get()))) return rc;     // runs of every selected record -> run0
+        if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one search grid");
+        if (P.n_runs == 0) {
+            if (counts) memset(counts, 0, (size_t)P.n_sel * 16);
+            return FX_OK;
+        }
+        nr1 = P.n_runs + 1;
+        grid_runs = nblocks(P.n_runs, BLOCK);
+        if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, n_pref * nr1, h->stream))) return rc;
+        return FX_OK;
+    }
+};
+
+// What the window-hit entries (fx_fasta_search, _search_approx, _pwm_scan) do once their arguments are checked and their tables
+// are up: the head above, then
+//   count(R)                                   the form's count kernel: hits per run on both strands, kept bytes -> R.packed
+//   fix(R, K, grid_sel)                        the cut at slen once the kept-byte scan K is there (timed with the scans)
+//   emit(R, list, n_list, K, Pp, Pm, o_rec, o_start, o_strand, o_extra)     the hits of the runs that have some
+// with the scans, the per-record counts, the totals home, the cap, the pinned blocks and the way home between them.
+// extra_size: bytes per hit of the form's fourth column (0: none), whose pinned block goes to *extra.
+template <class Count, class Fix, class Emit>
+static int run_hits(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t *counts,
+                    int extra_size, const char *what, Count &&count, Fix &&fix, Emit &&emit, int64_t **rec, int64_t **start, uint8_t **strand,
+                    void **extra, int64_t *n_hits) {
+    int rc;
+    HitRuns R;
+    if ((rc = R.open(h, st, masks, plen, ids, n_ids, 4, counts)) || R.P.n_runs == 0) return rc;
+    const SearchPlan &P = R.P;
+    int64_t *K = R.pref.p, *Pp = K + R.nr1, *Pm = K + 2 * R.nr1, *NZ = K + 3 * R.nr1;
+    const unsigned grid_sel = nblocks(P.n_sel, BLOCK);
+    // count pass, kept-byte scan, the cut at slen, hit scans
+    count(R);
+    if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{R.packed.p}, P.n_runs, K, R.d_tot))) return rc;
+    fix(R, (const int64_t *)K, grid_sel);
+    if ((rc = sscan<3>(h, st, K_SEARCH_SCAN, SrchLdHits{R.packed.p}, P.n_runs, Pp, R.d_tot))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
+    if (counts) {
+        int64_t *cnt_dev = nullptr;
+        if ((rc = st.scratch<int64_t>(2 * P.n_sel, &cnt_dev))) return rc;
+        FX_LAUNCH(h, K_SEARCH_SCAN, k_search_rec_counts, dim3(grid_sel), dim3(BLOCK), (const int64_t *)P.run0, P.n_sel, (const int64_t *)Pp,
+                  (const int64_t *)Pm, cnt_dev);
+        HIPCHK(hipMemcpyAsync(counts, cnt_dev, (size_t)P.n_sel * 16, hipMemcpyDeviceToHost, h->stream));
+    }
+    const int64_t *tot = R.tot.get();
+    if ((rc = read_home(h, R.tot.get(), R.d_tot, 24))) return rc;
+    const int64_t total = tot[0] + tot[1], n_list = tot[2];
+    *n_hits = total;
+    if (cap == 0 && counts) { h->prof.drain(); return FX_OK; }
+    if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
+    // emit: the runs with hits, at their offsets; the answers home by DMA into pinned blocks
+    PinnedOut<4> out(h);                       // rec, start, strand, the form's own column
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m) || (extra_size && !out.alloc(3, m * extra_size)))
+        return fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total);
+    if (total == 0) h->prof.drain();
+    else {
+        ScratchBuf<int64_t> out64, list;
+        ScratchBuf<uint8_t> out8;              // the form's column, then strand
+        if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out8.alloc(h->device, (extra_size + 1) * total, h->stream)) ||
+            (rc = list.alloc(h->device, n_list, h->stream)))
+            return rc;
+        uint8_t *d_strand = out8.p + extra_size * total;
+        hipLaunchKernelGGL(k_search_list, dim3(R.grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)R.packed.p, (const int64_t *)NZ, P.n_runs, list.p);
+        emit(R, (const int64_t *)list.p, n_list, (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, d_strand,
+             (void *)out8.p);
+        if ((rc = home(h, what, {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], d_strand, total},
+                                 {out.p[3], out8.p, extra_size * total}})))
+            return rc;
+    }
+    out.release(rec, start, strand, extra);
+    return FX_OK;
+}
+
 // Both search entries.  max_mismatch < 0: the exact automaton (fx_search.hpp); otherwise the approximate one
-// (fx_search_approx.hpp) with its anchor and the mismatch column -- the plan, the scans, the cut, the list and the way home
-// are the same.
+// (fx_search_approx.hpp) with its anchor and the mismatch column.
 static int fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int max_mismatch, uint64_t anchor,
                         const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand,
                         uint8_t **mismatch, int64_t *n_hits, int64_t *counts) {
@@ -3808,10 +3894,8 @@ static int fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, i
     if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
     if (n_sel == 0) return FX_OK;
     Staged st(h);
-    SearchPlan P;
     const ulonglong2 *d_masks = nullptr;
     if ((rc = st.up(h, masks.data(), 256, &d_masks))) return rc;
-    P.masks = d_masks;
     const bool wide = plen > 32;
     ApproxArg A{0, 0, 0};
     if (approx) {                              // where a mismatch may fall: the pattern's positions minus the anchor, mirrored for '-'
@@ -3821,82 +3905,40 @@ static int fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, i
         const uint64_t nf = (mode & FX_SEARCH_PLUS) ? valid & ~anchor : 0, nr = (mode & FX_SEARCH_MINUS) ? valid & ~mirror : 0;
         A = wide ? ApproxArg{nf, nr, max_mismatch} : ApproxArg{nf | (nr << 32), 0, max_mismatch};
     }
-    int64_t *tot = (int64_t *)fx_pinned_alloc(64), *d_tot = nullptr;        // tot: where the totals of the scans land
-    if (!tot) return FX_ENOMEM;
-    std::unique_ptr<int64_t, void (*)(int64_t *)> tot_guard(tot, [](int64_t *p) { fx_pinned_free(p); });
-    // 1. runs of every selected record -> run0
-    if ((rc = fasta_run_plan(h, st, K_SEARCH_SCAN, ids, n_ids, plen, &P, &d_tot, tot))) return rc;
-    if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one search grid");
-    int64_t *cnt_dev = nullptr;
-    if (P.n_runs == 0) {                       // nothing but empty records
-        if (counts) memset(counts, 0, (size_t)n_sel * 16);
-        return FX_OK;
-    }
-    // 2. count pass, kept-byte scan, the cut at slen, hit scans
-    ScratchBuf<uint32_t> packed;
-    ScratchBuf<int64_t> pref;                  // K, Pp, Pm, NZ: 4 x (n_runs + 1)
-    const int64_t nr1 = P.n_runs + 1;
-    if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, 4 * nr1, h->stream))) return rc;
-    int64_t *K = pref.p, *Pp = pref.p + nr1, *Pm = pref.p + 2 * nr1, *NZ = pref.p + 3 * nr1;
-    const unsigned grid_runs = nblocks(P.n_runs, BLOCK), grid_sel = nblocks(n_sel, BLOCK);
     // the approximate kernels of this call: f(WIDE, NLEV)
     auto with_form = [&](auto &&f) { with_bool(wide, [&](auto W) { with_levels(A.d, [&](auto N) { f(W, N); }); }); };
-    if (approx)
-        with_form([&](auto W, auto N) {
-            FX_LAUNCH(h, K_ASEARCH_COUNT, (k_asearch_count<decltype(W)::value, decltype(N)::value>), dim3(grid_runs), dim3(BLOCK), P, A, packed.p);
-        });
-    else
-        with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<W()>, dim3(grid_runs), dim3(BLOCK), P, packed.p); });
-    if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{packed.p}, P.n_runs, K, d_tot))) return rc;
-    if (approx)
-        with_form([&](auto W, auto N) {
-            FX_LAUNCH(h, K_SEARCH_SCAN, (k_asearch_fix<decltype(W)::value, decltype(N)::value>), dim3(grid_sel), dim3(BLOCK), P, A, (const int64_t *)K,
-                      packed.p);
-        });
-    else
-        with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<W()>, dim3(grid_sel), dim3(BLOCK), P, (const int64_t *)K, packed.p); });
-    if ((rc = sscan<3>(h, st, K_SEARCH_SCAN, SrchLdHits{packed.p}, P.n_runs, Pp, d_tot))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
-    if (counts) {
-        if ((rc = st.scratch<int64_t>(2 * n_sel, &cnt_dev))) return rc;
-        FX_LAUNCH(h, K_SEARCH_SCAN, k_search_rec_counts, dim3(grid_sel), dim3(BLOCK), (const int64_t *)P.run0, n_sel, (const int64_t *)Pp,
-                  (const int64_t *)Pm, cnt_dev);
-        HIPCHK(hipMemcpyAsync(counts, cnt_dev, (size_t)n_sel * 16, hipMemcpyDeviceToHost, h->stream));
-    }
-    if ((rc = read_home(h, tot, d_tot, 24))) return rc;
-    const int64_t total = tot[0] + tot[1], n_list = tot[2];
-    *n_hits = total;
-    if (counts_only) { h->prof.drain(); return FX_OK; }
-    if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
-    // 3. emit: the runs with hits, at their offsets; the answers home by DMA into pinned blocks
-    PinnedOut<4> out(h);                       // rec, start, strand, mismatch (the approximate search alone)
-    const int64_t m = std::max<int64_t>(total, 1);
-    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m) || (approx && !out.alloc(3, m)))
-        return fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total);
-    if (total == 0) h->prof.drain();
-    else {
-        ScratchBuf<int64_t> out64, list;
-        ScratchBuf<uint8_t> out8;              // strand, then mismatch
-        if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out8.alloc(h->device, (approx ? 2 : 1) * total, h->stream)) ||
-            (rc = list.alloc(h->device, n_list, h->stream)))
-            return rc;
-        hipLaunchKernelGGL(k_search_list, dim3(grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
-        if (approx)
-            with_form([&](auto W, auto N) {
-                FX_LAUNCH(h, K_ASEARCH_EMIT, (k_asearch_emit<decltype(W)::value, decltype(N)::value>), dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, A,
-                          (const int64_t *)list.p, n_list, (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total,
-                          out8.p, out8.p + total);
-            });
-        else
-            with_bool(wide, [&](auto W) {
-                FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<W()>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, (const int64_t *)list.p, n_list,
-                          (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p);
-            });
-        if ((rc = home(h, "search emit", {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], out8.p, total},
-                                          {out.p[3], out8.p + total, approx ? total : 0}})))
-            return rc;
-    }
-    out.release(rec, start, strand, mismatch);
-    return FX_OK;
+    return run_hits(
+        h, st, d_masks, plen, ids, n_ids, cap, counts, approx ? 1 : 0, "search emit",
+        [&](HitRuns &R) {
+            if (approx)
+                with_form([&](auto W, auto N) {
+                    FX_LAUNCH(h, K_ASEARCH_COUNT, (k_asearch_count<decltype(W)::value, decltype(N)::value>), dim3(R.grid_runs), dim3(BLOCK), R.P, A, R.packed.p);
+                });
+            else
+                with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<W()>, dim3(R.grid_runs), dim3(BLOCK), R.P, R.packed.p); });
+        },
+        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
+            if (approx)
+                with_form([&](auto W, auto N) {
+                    FX_LAUNCH(h, K_SEARCH_SCAN, (k_asearch_fix<decltype(W)::value, decltype(N)::value>), dim3(grid_sel), dim3(BLOCK), R.P, A, K, R.packed.p);
+                });
+            else
+                with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<W()>, dim3(grid_sel), dim3(BLOCK), R.P, K, R.packed.p); });
+        },
+        [&](HitRuns &R, const int64_t *list, int64_t n_list, const int64_t *K, const int64_t *Pp, const int64_t *Pm, int64_t *o_rec, int64_t *o_start,
+            uint8_t *o_strand, void *o_mis) {
+            if (approx)
+                with_form([&](auto W, auto N) {
+                    FX_LAUNCH(h, K_ASEARCH_EMIT, (k_asearch_emit<decltype(W)::value, decltype(N)::value>), dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), R.P, A,
+                              list, n_list, K, Pp, Pm, o_rec, o_start, o_strand, (uint8_t *)o_mis);
+                });
+            else
+                with_bool(wide, [&](auto W) {
+                    FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<W()>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), R.P, list, n_list, K, Pp, Pm, o_rec, o_start,
+                              o_strand);
+                });
+        },
+        rec, start, strand, (void **)mismatch, n_hits);
 }
 
 extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, const int64_t *ids,
@@ -3950,8 +3992,8 @@ template <class F> static void with_groups(int G, F &&f) {
     with_int<16>(G, [&](auto N) { if constexpr (decltype(N)::value > 0) f(N); });
 }
 
-// Both matrix entries.  best_score != null: the per-record maximum (fx_fasta_pwm_best); otherwise the scan.  The plan, the
-// scans, the cut, the list and the way home are fasta_search's.
+// Both matrix entries.  best_score != null: the per-record maximum (fx_fasta_pwm_best); otherwise the scan, through
+// run_hits like the searches; the best shares the head (HitRuns) and has a short tail of its own.
 static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, int32_t min_score, const int64_t *ids, int64_t n_ids,
                      int64_t cap, int64_t **rec, int64_t **start, uint8_t **strand, int32_t **score, int64_t *n_hits, int64_t *counts,
                      int32_t *best_score, int64_t *best_start) {
@@ -3976,35 +4018,19 @@ static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, i
     const std::vector<int2> tab = pwm_tables(mat, plen);
     const int G = (plen + 3) / 4;
     Staged st(h);
-    SearchPlan P;
     PwmArg A{nullptr, (mode & FX_SEARCH_PLUS) ? (best ? 0 : min_score) : PWM_NEVER, (mode & FX_SEARCH_MINUS) ? (best ? 0 : min_score) : PWM_NEVER};
     if ((rc = st.up(h, tab.data(), (int64_t)tab.size(), &A.tab))) return rc;
-    P.masks = nullptr;
-    int64_t *tot = (int64_t *)fx_pinned_alloc(64), *d_tot = nullptr;        // tot: where the totals of the scans land
-    if (!tot) return FX_ENOMEM;
-    std::unique_ptr<int64_t, void (*)(int64_t *)> tot_guard(tot, [](int64_t *p) { fx_pinned_free(p); });
-    // 1. runs of every selected record -> run0
-    if ((rc = fasta_run_plan(h, st, K_SEARCH_SCAN, ids, n_ids, plen, &P, &d_tot, tot))) return rc;
-    if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one search grid");
-    if (P.n_runs == 0) {                       // nothing but empty records
-        if (counts) memset(counts, 0, (size_t)n_sel * 16);
-        return FX_OK;
-    }
-    ScratchBuf<uint32_t> packed;
-    ScratchBuf<int64_t> pref;                  // K, Pp, Pm, NZ: 4 x (n_runs + 1) (the best: K alone)
-    const int64_t nr1 = P.n_runs + 1;
-    if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, (best ? 1 : 4) * nr1, h->stream))) return rc;
-    int64_t *K = pref.p, *Pp = pref.p + nr1, *Pm = pref.p + 2 * nr1, *NZ = pref.p + 3 * nr1;
-    const unsigned grid_runs = nblocks(P.n_runs, BLOCK), grid_sel = nblocks(n_sel, BLOCK);
     if (best) {
-        // 2b. kept bytes per run, their scan, then the best window of every run in front of the cut, reduced per record
+        // kept bytes per run, their scan (K alone), then the best window of every run in front of the cut, reduced per record
+        HitRuns R;
+        if ((rc = R.open(h, st, nullptr, plen, ids, n_ids, 1, nullptr)) || R.P.n_runs == 0) return rc;
         unsigned long long *keys = nullptr;
         if ((rc = st.scratch<unsigned long long>(2 * n_sel, &keys))) return rc;
         HIPCHK(hipMemsetAsync(keys, 0, (size_t)n_sel * 16, h->stream));
-        FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<0>, dim3(grid_runs), dim3(BLOCK), P, A, packed.p);
-        if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{packed.p}, P.n_runs, K, d_tot))) return rc;
+        FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<0>, dim3(R.grid_runs), dim3(BLOCK), R.P, A, R.packed.p);
+        if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{R.packed.p}, R.P.n_runs, R.pref.p, R.d_tot))) return rc;
         with_groups(G, [&](auto N) {
-            FX_LAUNCH(h, K_PWM_BEST, k_pwm_best<decltype(N)::value>, dim3(grid_runs), dim3(BLOCK), P, A, (const int64_t *)K, keys);
+            FX_LAUNCH(h, K_PWM_BEST, k_pwm_best<decltype(N)::value>, dim3(R.grid_runs), dim3(BLOCK), R.P, A, (const int64_t *)R.pref.p, keys);
         });
         std::vector<unsigned long long> hk((size_t)(2 * n_sel));
         if ((rc = home(h, "pwm best", {{hk.data(), keys, n_sel * 16}}))) return rc;
@@ -4015,49 +4041,22 @@ static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, i
             }
         return FX_OK;
     }
-    // 2. count pass, kept-byte scan, the cut at slen, hit scans
-    with_groups(G, [&](auto N) { FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<decltype(N)::value>, dim3(grid_runs), dim3(BLOCK), P, A, packed.p); });
-    if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{packed.p}, P.n_runs, K, d_tot))) return rc;
-    with_groups(G, [&](auto N) {
-        FX_LAUNCH(h, K_SEARCH_SCAN, k_pwm_fix<decltype(N)::value>, dim3(grid_sel), dim3(BLOCK), P, A, (const int64_t *)K, packed.p);
-    });
-    if ((rc = sscan<3>(h, st, K_SEARCH_SCAN, SrchLdHits{packed.p}, P.n_runs, Pp, d_tot))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
-    if (counts) {
-        int64_t *cnt_dev = nullptr;
-        if ((rc = st.scratch<int64_t>(2 * n_sel, &cnt_dev))) return rc;
-        FX_LAUNCH(h, K_SEARCH_SCAN, k_search_rec_counts, dim3(grid_sel), dim3(BLOCK), (const int64_t *)P.run0, n_sel, (const int64_t *)Pp,
-                  (const int64_t *)Pm, cnt_dev);
-        HIPCHK(hipMemcpyAsync(counts, cnt_dev, (size_t)n_sel * 16, hipMemcpyDeviceToHost, h->stream));
-    }
-    if ((rc = read_home(h, tot, d_tot, 24))) return rc;
-    const int64_t total = tot[0] + tot[1], n_list = tot[2];
-    *n_hits = total;
-    if (counts_only) { h->prof.drain(); return FX_OK; }
-    if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
-    // 3. emit: the runs with hits, at their offsets; the answers home by DMA into pinned blocks
-    PinnedOut<4> out(h);                       // rec, start, strand, score
-    const int64_t m = std::max<int64_t>(total, 1);
-    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m) || !out.alloc(3, m * 4))
-        return fail(FX_ENOMEM, "pinned blocks for %lld hits", (long long)total);
-    if (total == 0) h->prof.drain();
-    else {
-        ScratchBuf<int64_t> out64, list;
-        ScratchBuf<int32_t> out32;
-        ScratchBuf<uint8_t> out8;
-        if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out32.alloc(h->device, total, h->stream)) ||
-            (rc = out8.alloc(h->device, total, h->stream)) || (rc = list.alloc(h->device, n_list, h->stream)))
-            return rc;
-        hipLaunchKernelGGL(k_search_list, dim3(grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
-        with_groups(G, [&](auto N) {
-            FX_LAUNCH(h, K_PWM_EMIT, k_pwm_emit<decltype(N)::value>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), P, A, (const int64_t *)list.p, n_list,
-                      (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, out8.p, out32.p);
-        });
-        if ((rc = home(h, "pwm emit", {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], out8.p, total},
-                                       {out.p[3], out32.p, total * 4}})))
-            return rc;
-    }
-    out.release(rec, start, strand, score);
-    return FX_OK;
+    return run_hits(
+        h, st, nullptr, plen, ids, n_ids, cap, counts, 4, "pwm emit",
+        [&](HitRuns &R) {
+            with_groups(G, [&](auto N) { FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<decltype(N)::value>, dim3(R.grid_runs), dim3(BLOCK), R.P, A, R.packed.p); });
+        },
+        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
+            with_groups(G, [&](auto N) { FX_LAUNCH(h, K_SEARCH_SCAN, k_pwm_fix<decltype(N)::value>, dim3(grid_sel), dim3(BLOCK), R.P, A, K, R.packed.p); });
+        },
+        [&](HitRuns &R, const int64_t *list, int64_t n_list, const int64_t *K, const int64_t *Pp, const int64_t *Pm, int64_t *o_rec, int64_t *o_start,
+            uint8_t *o_strand, void *o_score) {
+            with_groups(G, [&](auto N) {
+                FX_LAUNCH(h, K_PWM_EMIT, k_pwm_emit<decltype(N)::value>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), R.P, A, list, n_list, K, Pp, Pm, o_rec,
+                          o_start, o_strand, (int32_t *)o_score);
+            });
+        },
+        rec, start, strand, (void **)score, n_hits);
 }
 
 extern "C" int fx_fasta_pwm_scan(fx_handle *h, const int32_t *mat, int32_t plen, int mode, int32_t min_score, const int64_t *ids,
@@ -4233,6 +4232,81 @@ extern "C" int fx_fasta_window_counts(fx_handle *h, const int64_t *ids, int64_t 
     return FX_OK;
 }
 
+// ------------------------------------------------------------------ interval passes over the runs: class runs, tandem repeats, ORFs
+// What such a pass works on: the plan over the runs of the selected records and the rank index; `words` 32-bit words per run,
+// the last row of them the closes of every run; the carry scan NZ (n_carry arrays of n_runs + 1) with the row offsets O behind
+// it; the list (list_rows rows of n_runs).
+struct IvRuns {
+    SearchPlan P;
+    RankIndex X;
+    uint32_t *words = nullptr, *closes = nullptr;
+    int64_t *NZ = nullptr, *O = nullptr, *list = nullptr, *d_tot = nullptr;
+    unsigned grid = 1;
+};
+struct IvCol { int size; void **out; };                    // a column of the entry's own: bytes per row (0: none), where its pinned block goes
+
+// What fx_fasta_class_runs, _tandem_repeats and _orfs do once they have checked their own arguments: the handle and the ids
+// checked, the plan, the work buffers, then
+//   offsets(st, R)                             count, carry scan, list, close and the scan of the closes, each under the entry's ids
+//   emit(R, o_rec, o_start, o_stop, o_c3, o_c4)
+// with the total home, the cap, the pinned blocks (one element for no rows, never null) and the way home between them.  On the
+// device the wider of c3 and c4 lies first.
+template <class Offsets, class Emit>
+static int run_intervals(fx_handle *h, const int64_t *ids, int64_t n_ids, int64_t max_rows, int scan_id, const char *noun, const char *what, int words,
+                         int n_carry, int list_rows, Offsets &&offsets, Emit &&emit, int64_t **rec, int64_t **start, int64_t **stop, IvCol c3, IvCol c4,
+                         int64_t *n, int64_t *n_total) {
+    int rc;
+    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    Staged st(h);
+    IvRuns R;
+    SearchPlan all;
+    rank_view(h, &all, &R.X);
+    R.P.n_runs = 0;
+    int64_t land = 0, total = 0;
+    ScratchBuf<uint32_t> wbuf;
+    ScratchBuf<int64_t> pref, list;
+    if (n_sel > 0) {
+        if ((rc = fasta_run_plan(h, st, scan_id, ids, n_ids, 1, &R.P, &R.d_tot, &land))) return rc;
+        R.P.masks = nullptr;
+        if (R.P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one grid");
+    }
+    if (R.P.n_runs > 0) {
+        const int64_t nr = R.P.n_runs;
+        if ((rc = wbuf.alloc(h->device, words * nr, h->stream)) || (rc = pref.alloc(h->device, (n_carry + 1) * (nr + 1), h->stream)) ||
+            (rc = list.alloc(h->device, list_rows * nr, h->stream)))
+            return rc;
+        R.words = wbuf.p; R.closes = wbuf.p + (words - 1) * nr;
+        R.NZ = pref.p; R.O = pref.p + n_carry * (nr + 1); R.list = list.p;
+        R.grid = nblocks(nr, BLOCK);
+        if ((rc = offsets(st, R)) || (rc = read_home(h, &total, R.d_tot, 8))) return rc;
+    }
+    *n_total = total;
+    if (total > max_rows) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "%lld %s, more than the %lld asked for", (long long)total, noun, (long long)max_rows);
+    }
+    PinnedOut<5> out(h);                                   // rec, start, stop, c3, c4
+    const int64_t m = std::max<int64_t>(total, 1);
+    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8) || (c3.size && !out.alloc(3, m * c3.size)) ||
+        (c4.size && !out.alloc(4, m * c4.size)))
+        return fail(FX_ENOMEM, "pinned blocks for %lld %s", (long long)total, noun);
+    if (total == 0) h->prof.drain();
+    else {
+        ScratchBuf<int64_t> dev;                           // rec, start, stop
+        ScratchBuf<uint8_t> own;                           // c3 and c4
+        if ((rc = dev.alloc(h->device, 3 * total, h->stream)) || (rc = own.alloc(h->device, (c3.size + c4.size) * total, h->stream))) return rc;
+        uint8_t *d3 = own.p + (c4.size > c3.size ? c4.size * total : 0), *d4 = own.p + (c4.size > c3.size ? 0 : c3.size * total);
+        emit(R, dev.p, dev.p + total, dev.p + 2 * total, (void *)d3, (void *)d4);
+        if ((rc = home(h, what, {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, total * 8}, {out.p[2], dev.p + 2 * total, total * 8},
+                                 {out.p[3], d3, c3.size * total}, {out.p[4], d4, c4.size * total}})))
+            return rc;
+    }
+    *n = total;
+    out.release(rec, start, stop, c3.out, c4.out);
+    return FX_OK;
+}
+
 extern "C" int fx_fasta_class_runs(fx_handle *h, const uint8_t *set32, int64_t min_len, const int64_t *ids, int64_t n_ids, int64_t max_runs,
                                    int64_t **rec, int64_t **start, int64_t **stop, int64_t *n, int64_t *n_total) {
     int rc = an_device();
@@ -4242,59 +4316,25 @@ extern "C" int fx_fasta_class_runs(fx_handle *h, const uint8_t *set32, int64_t m
     if (min_len < 1) return fail(FX_EINVAL, "min_len %lld must be at least 1", (long long)min_len);
     if (max_runs < 0) return fail(FX_EINVAL, "max_runs must not be negative");
     if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    Staged st(h);
-    SearchPlan P, all;
-    RankIndex X;
-    rank_view(h, &all, &X);
-    P.n_runs = 0;
-    int64_t *d_tot = nullptr, land = 0, total = 0;
-    ScratchBuf<uint32_t> packed;
-    ScratchBuf<int64_t> pref, list;                        // pref: NZ, O (n_runs + 1 each)
-    int64_t *NZ = nullptr, *O = nullptr;
     RunsArg A{nullptr, min_len};
-    unsigned grid = 1;
-    uint32_t words[8];
-    memcpy(words, set32, 32);                              // bit c of the set = bit c & 7 of byte c >> 3 (little-endian words)
-    if (n_sel > 0) {
-        if ((rc = fasta_run_plan(h, st, K_AN_RUNS_SCAN, ids, n_ids, 1, &P, &d_tot, &land))) return rc;
-        P.masks = nullptr;
-        if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one grid");
-    }
-    if (P.n_runs > 0) {
-        const int64_t nr1 = P.n_runs + 1;
-        if ((rc = st.up(h, words, 8, &A.set)) || (rc = packed.alloc(h->device, P.n_runs, h->stream)) ||
-            (rc = pref.alloc(h->device, 2 * nr1, h->stream)) || (rc = list.alloc(h->device, P.n_runs, h->stream)))
-            return rc;
-        NZ = pref.p; O = pref.p + nr1;
-        grid = nblocks(P.n_runs, BLOCK);
-        FX_LAUNCH(h, K_AN_RUNS_COUNT, k_an_runs_count, dim3(grid), dim3(BLOCK), P, X, A, packed.p);
-        if ((rc = sscan<1>(h, st, K_AN_RUNS_SCAN, AnLdOutside{packed.p}, P.n_runs, NZ, d_tot))) return rc;
-        FX_LAUNCH(h, K_AN_RUNS_SCAN, k_an_runs_list, dim3(grid), dim3(BLOCK), (const uint32_t *)packed.p, (const int64_t *)NZ, P.n_runs, list.p);
-        FX_LAUNCH(h, K_AN_RUNS_SCAN, k_an_runs_close, dim3(grid), dim3(BLOCK), P, X, A, (const int64_t *)NZ, (const int64_t *)list.p, packed.p);
-        if ((rc = sscan<1>(h, st, K_AN_RUNS_SCAN, AnLdCloses{packed.p}, P.n_runs, O, d_tot)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
-    }
-    *n_total = total;
-    if (total > max_runs) {
-        h->prof.drain();
-        return fail(FX_ERANGE, "%lld runs, more than the %lld asked for", (long long)total, (long long)max_runs);
-    }
-    PinnedOut<3> out(h);                                   // rec, start, stop
-    const int64_t m = std::max<int64_t>(total, 1);
-    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld runs", (long long)total);
-    if (total == 0) h->prof.drain();
-    else {
-        ScratchBuf<int64_t> dev;
-        if ((rc = dev.alloc(h->device, 3 * total, h->stream))) return rc;
-        FX_LAUNCH(h, K_AN_RUNS_EMIT, k_an_runs_emit, dim3(grid), dim3(BLOCK), P, X, A, (const uint32_t *)packed.p, (const int64_t *)NZ,
-                  (const int64_t *)list.p, (const int64_t *)O, dev.p, dev.p + total, dev.p + 2 * total);
-        if ((rc = home(h, "class runs", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, total * 8}, {out.p[2], dev.p + 2 * total, total * 8}})))
-            return rc;
-    }
-    *n = total;
-    out.release(rec, start, stop);
-    return FX_OK;
+    uint32_t set[8];
+    memcpy(set, set32, 32);                                // bit c of the set = bit c & 7 of byte c >> 3 (little-endian words)
+    return run_intervals(
+        h, ids, n_ids, max_runs, K_AN_RUNS_SCAN, "runs", "class runs", 1, 1, 1,
+        [&](Staged &st, IvRuns &R) {                       // words: one per run, the outside bits first and the closes afterwards
+            int rc;
+            if ((rc = st.up(h, set, 8, &A.set))) return rc;
+            FX_LAUNCH(h, K_AN_RUNS_COUNT, k_an_runs_count, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, R.words);
+            if ((rc = sscan<1>(h, st, K_AN_RUNS_SCAN, AnLdOutside{R.words}, R.P.n_runs, R.NZ, R.d_tot))) return rc;
+            FX_LAUNCH(h, K_AN_RUNS_SCAN, k_an_runs_list, dim3(R.grid), dim3(BLOCK), (const uint32_t *)R.words, (const int64_t *)R.NZ, R.P.n_runs, R.list);
+            FX_LAUNCH(h, K_AN_RUNS_SCAN, k_an_runs_close, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (const int64_t *)R.NZ, (const int64_t *)R.list, R.words);
+            return sscan<1>(h, st, K_AN_RUNS_SCAN, AnLdCloses{R.words}, R.P.n_runs, R.O, R.d_tot);
+        },
+        [&](IvRuns &R, int64_t *o_rec, int64_t *o_start, int64_t *o_stop, void *, void *) {
+            FX_LAUNCH(h, K_AN_RUNS_EMIT, k_an_runs_emit, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (const uint32_t *)R.words, (const int64_t *)R.NZ,
+                      (const int64_t *)R.list, (const int64_t *)R.O, o_rec, o_start, o_stop);
+        },
+        rec, start, stop, IvCol{0, nullptr}, IvCol{0, nullptr}, n, n_total);
 }
 
 // ------------------------------------------------------------------ tandem repeats (fx_tandem.hpp)
@@ -4322,64 +4362,24 @@ extern "C" int fx_fasta_tandem_repeats(fx_handle *h, const int32_t *min_copies, 
     if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
     int n_track = 0;
     for (int p = 1; p <= TD_MAXP; ++p) A.slot[p - 1] = (A.track4 >> (4 * (p - 1))) & 1u ? n_track++ : 0;
-    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    Staged st(h);
-    SearchPlan P, all;
-    RankIndex X;
-    rank_view(h, &all, &X);
-    P.n_runs = 0;
-    int64_t *d_tot = nullptr, land = 0, total = 0;
-    ScratchBuf<uint32_t> words;                            // pk (n_track rows of n_runs), closes (n_runs)
-    ScratchBuf<int64_t> pref, list;                        // pref: NZ (8 components of n_runs + 1), O (n_runs + 1)
-    int64_t *NZ = nullptr, *O = nullptr;
-    uint32_t *pk = nullptr, *closes = nullptr;
-    unsigned grid = 1;
-    if (n_sel > 0) {
-        if ((rc = fasta_run_plan(h, st, K_TD_SCAN, ids, n_ids, 1, &P, &d_tot, &land))) return rc;
-        P.masks = nullptr;
-        if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one grid");
-    }
-    if (P.n_runs > 0) {
-        const int64_t nr1 = P.n_runs + 1;
-        if ((rc = words.alloc(h->device, (n_track + 1) * P.n_runs, h->stream)) || (rc = pref.alloc(h->device, (TD_MAXP + 1) * nr1, h->stream)) ||
-            (rc = list.alloc(h->device, n_track * P.n_runs, h->stream)))
-            return rc;
-        pk = words.p; closes = words.p + n_track * P.n_runs;
-        NZ = pref.p; O = pref.p + TD_MAXP * nr1;
-        grid = nblocks(P.n_runs, BLOCK);
-        TdLdBreak brk{pk, P.n_runs, {}, A.track4};
-        memcpy(brk.slot, A.slot, sizeof brk.slot);
-        FX_LAUNCH(h, K_TD_COUNT, k_td_count, dim3(grid), dim3(BLOCK), P, X, A, pk, closes);
-        if ((rc = sscan<TD_MAXP>(h, st, K_TD_SCAN, brk, P.n_runs, NZ, d_tot))) return rc;
-        FX_LAUNCH(h, K_TD_SCAN, k_td_list, dim3(grid), dim3(BLOCK), A, (const uint32_t *)pk, (const int64_t *)NZ, P.n_runs, list.p);
-        FX_LAUNCH(h, K_TD_CLOSE, k_td_close, dim3(grid), dim3(BLOCK), P, X, A, (const uint32_t *)pk, (const int64_t *)NZ, (const int64_t *)list.p, closes);
-        if ((rc = sscan<1>(h, st, K_TD_SCAN, TdLdCloses{closes}, P.n_runs, O, d_tot)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
-    }
-    *n_total = total;
-    if (total > max_rows) {
-        h->prof.drain();
-        return fail(FX_ERANGE, "%lld repeats, more than the %lld asked for", (long long)total, (long long)max_rows);
-    }
-    PinnedOut<5> out(h);                                   // rec, start, stop, period, motif
-    const int64_t m = std::max<int64_t>(total, 1);
-    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8) || !out.alloc(3, m) || !out.alloc(4, m * 4))
-        return fail(FX_ENOMEM, "pinned blocks for %lld repeats", (long long)total);
-    if (total == 0) h->prof.drain();
-    else {
-        ScratchBuf<int64_t> dev;                           // rec, start, stop
-        ScratchBuf<uint32_t> dev4;                         // motif, then period (one byte a row)
-        if ((rc = dev.alloc(h->device, 3 * total, h->stream)) || (rc = dev4.alloc(h->device, total + (total + 3) / 4, h->stream))) return rc;
-        uint8_t *d_period = (uint8_t *)(dev4.p + total);
-        FX_LAUNCH(h, K_TD_EMIT, k_td_emit, dim3(grid), dim3(BLOCK), P, X, A, (const uint32_t *)pk, (const int64_t *)NZ, (const int64_t *)list.p,
-                  (const uint32_t *)closes, (const int64_t *)O, dev.p, dev.p + total, dev.p + 2 * total, d_period, dev4.p);
-        if ((rc = home(h, "tandem repeats", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, total * 8}, {out.p[2], dev.p + 2 * total, total * 8},
-                                             {out.p[3], d_period, total}, {out.p[4], dev4.p, total * 4}})))
-            return rc;
-    }
-    *n = total;
-    out.release(rec, start, stop, period, motif);
-    return FX_OK;
+    return run_intervals(
+        h, ids, n_ids, max_rows, K_TD_SCAN, "repeats", "tandem repeats", n_track + 1, TD_MAXP, n_track,
+        [&](Staged &st, IvRuns &R) {                       // words: pk, n_track rows, then the closes
+            int rc;
+            TdLdBreak brk{R.words, R.P.n_runs, {}, A.track4};
+            memcpy(brk.slot, A.slot, sizeof brk.slot);
+            FX_LAUNCH(h, K_TD_COUNT, k_td_count, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, R.words, R.closes);
+            if ((rc = sscan<TD_MAXP>(h, st, K_TD_SCAN, brk, R.P.n_runs, R.NZ, R.d_tot))) return rc;
+            FX_LAUNCH(h, K_TD_SCAN, k_td_list, dim3(R.grid), dim3(BLOCK), A, (const uint32_t *)R.words, (const int64_t *)R.NZ, R.P.n_runs, R.list);
+            FX_LAUNCH(h, K_TD_CLOSE, k_td_close, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (const uint32_t *)R.words, (const int64_t *)R.NZ,
+                      (const int64_t *)R.list, R.closes);
+            return sscan<1>(h, st, K_TD_SCAN, TdLdCloses{R.closes}, R.P.n_runs, R.O, R.d_tot);
+        },
+        [&](IvRuns &R, int64_t *o_rec, int64_t *o_start, int64_t *o_stop, void *o_period, void *o_motif) {
+            FX_LAUNCH(h, K_TD_EMIT, k_td_emit, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (const uint32_t *)R.words, (const int64_t *)R.NZ,
+                      (const int64_t *)R.list, (const uint32_t *)R.closes, (const int64_t *)R.O, o_rec, o_start, o_stop, (uint8_t *)o_period, (uint32_t *)o_motif);
+        },
+        rec, start, stop, IvCol{1, (void **)period}, IvCol{4, (void **)motif}, n, n_total);
 }
 
 // ------------------------------------------------------------------ open reading frames, translation (fx_orf.hpp)
@@ -4409,60 +4409,22 @@ extern "C" int fx_fasta_orfs(fx_handle *h, uint64_t stop_mask, uint64_t start_ma
     if (max_rows < 0) return fail(FX_EINVAL, "max_rows must not be negative");
     if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
     const OrfArg A{{stop_mask, orf_reverse_mask(stop_mask)}, {start_mask, orf_reverse_mask(start_mask)}, std::max<int64_t>(min_len, 3), mode, strands};
-    if ((rc = an_enter(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    Staged st(h);
-    SearchPlan P, all;
-    RankIndex X;
-    rank_view(h, &all, &X);
-    P.n_runs = 0;
-    int64_t *d_tot = nullptr, land = 0, total = 0;
-    ScratchBuf<uint64_t> pk;                               // 6 rows of n_runs
-    ScratchBuf<uint32_t> closes;
-    ScratchBuf<int64_t> pref, list;                        // pref: NZ (12 components of n_runs + 1), O (n_runs + 1); list: 12 rows
-    int64_t *NZ = nullptr, *O = nullptr;
-    unsigned grid = 1;
-    if (n_sel > 0) {
-        if ((rc = fasta_run_plan(h, st, K_ORF_SCAN, ids, n_ids, 1, &P, &d_tot, &land))) return rc;
-        P.masks = nullptr;
-        if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one grid");
-    }
-    if (P.n_runs > 0) {
-        const int64_t nr1 = P.n_runs + 1;
-        if ((rc = pk.alloc(h->device, ORF_NC * P.n_runs, h->stream)) || (rc = closes.alloc(h->device, P.n_runs, h->stream)) ||
-            (rc = pref.alloc(h->device, (2 * ORF_NC + 1) * nr1, h->stream)) || (rc = list.alloc(h->device, 2 * ORF_NC * P.n_runs, h->stream)))
-            return rc;
-        NZ = pref.p; O = pref.p + 2 * ORF_NC * nr1;
-        grid = nblocks(P.n_runs, BLOCK);
-        FX_LAUNCH(h, K_ORF_COUNT, k_orf_count, dim3(grid), dim3(BLOCK), P, X, A, pk.p, closes.p);
-        if ((rc = sscan<2 * ORF_NC>(h, st, K_ORF_SCAN, OrfLdCarry{pk.p, P.n_runs}, P.n_runs, NZ, d_tot))) return rc;
-        FX_LAUNCH(h, K_ORF_SCAN, k_orf_list, dim3(grid), dim3(BLOCK), (const uint64_t *)pk.p, (const int64_t *)NZ, P.n_runs, list.p);
-        FX_LAUNCH(h, K_ORF_CLOSE, k_orf_close, dim3(grid), dim3(BLOCK), P, X, A, (const uint64_t *)pk.p, (const int64_t *)NZ, (const int64_t *)list.p, closes.p);
-        if ((rc = sscan<1>(h, st, K_ORF_SCAN, OrfLdCloses{closes.p}, P.n_runs, O, d_tot)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
-    }
-    *n_total = total;
-    if (total > max_rows) {
-        h->prof.drain();
-        return fail(FX_ERANGE, "%lld open reading frames, more than the %lld asked for", (long long)total, (long long)max_rows);
-    }
-    PinnedOut<5> out(h);                                   // rec, start, stop, frame, flags
-    const int64_t m = std::max<int64_t>(total, 1);
-    if (!out.alloc(0, m * 8) || !out.alloc(1, m * 8) || !out.alloc(2, m * 8) || !out.alloc(3, m) || !out.alloc(4, m))
-        return fail(FX_ENOMEM, "pinned blocks for %lld open reading frames", (long long)total);
-    if (total == 0) h->prof.drain();
-    else {
-        ScratchBuf<int64_t> dev;                           // rec, start, stop
-        ScratchBuf<uint8_t> dev1;                          // frame, flags
-        if ((rc = dev.alloc(h->device, 3 * total, h->stream)) || (rc = dev1.alloc(h->device, 2 * total, h->stream))) return rc;
-        FX_LAUNCH(h, K_ORF_EMIT, k_orf_emit, dim3(grid), dim3(BLOCK), P, X, A, (const uint64_t *)pk.p, (const int64_t *)NZ, (const int64_t *)list.p,
-                  (const uint32_t *)closes.p, (const int64_t *)O, dev.p, dev.p + total, dev.p + 2 * total, (int8_t *)dev1.p, dev1.p + total);
-        if ((rc = home(h, "open reading frames", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, total * 8}, {out.p[2], dev.p + 2 * total, total * 8},
-                                                  {out.p[3], dev1.p, total}, {out.p[4], dev1.p + total, total}})))
-            return rc;
-    }
-    *n = total;
-    out.release(rec, start, stop, frame, flags);
-    return FX_OK;
+    return run_intervals(
+        h, ids, n_ids, max_rows, K_ORF_SCAN, "open reading frames", "open reading frames", 2 * ORF_NC + 1, 2 * ORF_NC, 2 * ORF_NC,
+        [&](Staged &st, IvRuns &R) {                       // words: pk, 6 rows of 64 bits, then the closes
+            int rc;
+            const uint64_t *pk = (const uint64_t *)R.words;
+            FX_LAUNCH(h, K_ORF_COUNT, k_orf_count, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (uint64_t *)R.words, R.closes);
+            if ((rc = sscan<2 * ORF_NC>(h, st, K_ORF_SCAN, OrfLdCarry{(uint64_t *)R.words, R.P.n_runs}, R.P.n_runs, R.NZ, R.d_tot))) return rc;
+            FX_LAUNCH(h, K_ORF_SCAN, k_orf_list, dim3(R.grid), dim3(BLOCK), pk, (const int64_t *)R.NZ, R.P.n_runs, R.list);
+            FX_LAUNCH(h, K_ORF_CLOSE, k_orf_close, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, pk, (const int64_t *)R.NZ, (const int64_t *)R.list, R.closes);
+            return sscan<1>(h, st, K_ORF_SCAN, OrfLdCloses{R.closes}, R.P.n_runs, R.O, R.d_tot);
+        },
+        [&](IvRuns &R, int64_t *o_rec, int64_t *o_start, int64_t *o_stop, void *o_frame, void *o_flags) {
+            FX_LAUNCH(h, K_ORF_EMIT, k_orf_emit, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (const uint64_t *)R.words, (const int64_t *)R.NZ,
+                      (const int64_t *)R.list, (const uint32_t *)R.closes, (const int64_t *)R.O, o_rec, o_start, o_stop, (int8_t *)o_frame, (uint8_t *)o_flags);
+        },
+        rec, start, stop, IvCol{1, (void **)frame}, IvCol{1, (void **)flags}, n, n_total);
 }
 
 extern "C" int fx_fasta_translate_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
