@@ -1268,10 +1268,8 @@ class Blob:
                                        *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        names = (("length", np.int64), ("qsum", np.int64), ("qmin", np.int16), ("qmax", np.int16), ("n_low", np.int32),
-                 ("n_gc", np.int32), ("n_other", np.int32))
-        return {k: pinned_array(c.value, max(m, 1), dt)[:m] for (k, dt), c in zip(names, cols)}
+        names = ("length", "qsum", "qmin", "qmax", "n_low", "n_gc", "n_other")
+        return dict(zip(names, _pinned_columns(cols, [np.int64] * 2 + [np.int16] * 2 + [np.int32] * 3, int(n.value))))
 
     def fastq_cycle_hist(self, cycles):
         """Per-cycle histograms (fx_fastq_cycle_hist) -> (qual int64[cycles, 256], base int64[cycles, 5], depth int64[cycles]), pinned."""
@@ -1287,8 +1285,7 @@ class Blob:
         p, n = C.c_void_p(), C.c_int64(0)
         check(lib().fx_fastq_select(self._h, int(phred), int(low_qual), int(min_len), int(max_len), int(mean_qual[0]), int(mean_qual[1]),
                                     int(low_frac[0]), int(low_frac[1]), int(max_other), C.byref(p), C.byref(n)))
-        m = int(n.value)
-        return pinned_array(p.value, max(m, 1), np.int64)[:m]
+        return _pinned_columns([p], [np.int64], int(n.value))[0]
 
     def fastq_trim(self, ids=None, phred=0, clip_front=0, clip_tail=0, adapter=None, min_overlap=1, err=(0, 1), front_qual=None,
                    window=None, tail_qual=None):
@@ -1305,8 +1302,7 @@ class Blob:
                                  -1 if tail_qual is None else int(tail_qual), C.byref(ps), C.byref(pe), C.byref(n), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        return pinned_array(ps.value, max(m, 1), np.int64)[:m], pinned_array(pe.value, max(m, 1), np.int64)[:m]
+        return _pinned_columns((ps, pe), [np.int64] * 2, int(n.value))
 
     def fastq_format_alloc(self, ids=None, start=None, end=None, min_len=0):
         """Four-line records of the queries cut to [start, end) (fx_fastq_format_alloc; start = end = None: whole reads) ->
@@ -1344,10 +1340,10 @@ class Blob:
         if rc:
             _raise(rc, first_bad=int(bad.value))
         m = int(n.value)
-        out = {k: pinned_array(c.value, max(m, 1), np.int32)[:m] for k, c in zip(("sample", "dist", "second"), cols)}
+        out = dict(zip(("sample", "dist", "second"), _pinned_columns(cols[:3], [np.int32] * 3, m)))
         out["counts"] = pinned_array(cols[3].value, n_samples + 2, np.int64)
         if want_order:
-            out["order"] = pinned_array(cols[4].value, max(m, 1), np.int64)[:m]
+            out["order"] = _pinned_columns(cols[4:5], [np.int64], m)[0]
             out["bin_off"] = pinned_array(cols[5].value, n_samples + 3, np.int64)
         return out
 
@@ -1362,9 +1358,8 @@ class Blob:
                                          int(err[0]), int(err[1]), *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        names = (("diag", np.int32), ("overlap", np.int32), ("mismatches", np.int32), ("end1", np.int64), ("end2", np.int64))
-        return {k: pinned_array(c.value, max(m, 1), dt)[:m] for (k, dt), c in zip(names, cols)}
+        names = ("diag", "overlap", "mismatches", "end1", "end2")
+        return dict(zip(names, _pinned_columns(cols, [np.int32] * 3 + [np.int64] * 2, int(n.value))))
 
     def fastq_pair_merge_alloc(self, mate, diag, ids=None, min_len=0):
         """The merged records of the pairs (fx_fastq_pair_merge_alloc; diag: what fastq_pair_overlap returned for the same
@@ -1408,14 +1403,9 @@ class Blob:
         """k-mer spectrum of the reads `ids` (None: every read) cut to [start, end) (both None: whole reads) of the resident
         FASTQ table (fx_fastq_kmers) -> int64[4**k] in pinned memory.  A bad id or interval raises FxError(FX_ERANGE) with
         .first_bad."""
-        buf, n_ids, _ = self._kmer_ids(ids)
-        start = None if start is None else self._i64(start)
-        end = None if end is None else self._i64(end)
-        if start is not None and start.size == 0:
-            start = end = None                                 # no query, no interval
+        q, keep = self._fastq_queries(ids, start, end)
         p, bad = C.c_void_p(), C.c_int64(-1)
-        rc = lib().fx_fastq_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, _ptr(start), _ptr(end),
-                                  C.byref(p), C.byref(bad))
+        rc = lib().fx_fastq_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, *q, C.byref(p), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
         return pinned_array(p.value, 4 ** int(k), np.int64)
@@ -1426,8 +1416,7 @@ class Blob:
         rc = call(*head, int(min_count), int(max_bytes), C.byref(pc), C.byref(pn), C.byref(nd), C.byref(nw), C.byref(parts), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(nd.value)
-        return pinned_array(pc.value, max(m, 1), np.int64)[:m], pinned_array(pn.value, max(m, 1), np.int64)[:m], int(nw.value), int(parts.value)
+        return _pinned_columns((pc, pn), [np.int64] * 2, int(nd.value)) + (int(nw.value), int(parts.value))
 
     def fasta_kmer_table(self, k, canonical=False, ids=None, min_count=1, max_bytes=0):
         """Sparse k-mer table of the resident FASTA table (fx_fasta_kmer_table), 1 <= k <= 31 -> (codes int64[n] ascending,
@@ -1439,13 +1428,8 @@ class Blob:
 
     def fastq_kmer_table(self, k, canonical=False, ids=None, start=None, end=None, min_count=1, max_bytes=0):
         """Sparse k-mer table of the reads `ids` cut to [start, end) (fx_fastq_kmer_table) -> what fasta_kmer_table returns."""
-        buf, n_ids, _ = self._kmer_ids(ids)
-        start = None if start is None else self._i64(start)
-        end = None if end is None else self._i64(end)
-        if start is not None and start.size == 0:
-            start = end = None                                 # no query, no interval
-        head = (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, _ptr(start), _ptr(end))
-        return self._kmer_table(lib().fx_fastq_kmer_table, head, min_count, max_bytes)
+        q, keep = self._fastq_queries(ids, start, end)
+        return self._kmer_table(lib().fx_fastq_kmer_table, (self._h, int(k), FX_KMER_CANONICAL if canonical else 0) + q, min_count, max_bytes)
 
     def kmer_set(self, k, canonical, codes):
         """A device k-mer set of `codes` on this blob's device (fx_kmer_set_create) -> KmerSet; any blob of the device may use it."""
@@ -1456,8 +1440,7 @@ class Blob:
         rc = call(*head, C.byref(pw), C.byref(ph), C.byref(n), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        return pinned_array(pw.value, max(m, 1), dtype)[:m], pinned_array(ph.value, max(m, 1), dtype)[:m]
+        return _pinned_columns((pw, ph), [dtype] * 2, int(n.value))
 
     def _fastq_queries(self, ids, start, end):
         buf, n_ids, _ = self._kmer_ids(ids)
@@ -1482,8 +1465,7 @@ class Blob:
                                         C.byref(p), C.byref(n), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        return pinned_array(p.value, max(m, 1), np.int64)[:m]
+        return _pinned_columns([p], [np.int64], int(n.value))[0]
 
     def fasta_kmer_hits(self, kset, ids=None):
         """Per selected record the valid windows and the hits in `kset` (fx_fasta_kmer_hits) -> (n_windows, n_hits), int64."""
@@ -1500,8 +1482,7 @@ class Blob:
                                       C.byref(rounds), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        return pinned_array(p.value, max(m, 1), np.int64)[:m], int(groups.value), int(rounds.value)
+        return _pinned_columns([p], [np.int64], int(n.value)) + (int(groups.value), int(rounds.value))
 
     def fastq_dedup(self, ids=None, start=None, end=None, revcomp=False, hash_bits=0, min_copies=1, max_copies=-1, want_copies=False):
         """The ascending positions of the first occurrences whose group has min_copies..max_copies members (fx_fastq_dedup;
@@ -1512,9 +1493,8 @@ class Blob:
                                   C.byref(pc) if want_copies else None, C.byref(n), C.byref(groups), C.byref(rounds), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        copies = pinned_array(pc.value, max(m, 1), np.int64)[:m] if want_copies else None
-        return pinned_array(p.value, max(m, 1), np.int64)[:m], copies, int(groups.value), int(rounds.value)
+        pos, copies = _pinned_columns([p, pc] if want_copies else [p], [np.int64] * 2, int(n.value)) + (() if want_copies else (None,))
+        return pos, copies, int(groups.value), int(rounds.value)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)

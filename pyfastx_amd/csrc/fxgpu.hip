@@ -3408,20 +3408,25 @@ static int home(fx_handle *h, const char *what, std::initializer_list<D2H> c) { 
 
 // An exclusive scan of the C components ld(i, v) gives, over n elements, in chunks of SRCH_CHUNK (fx_search.hpp): the chunk sums
 // (arena; *sums_out) become the chunk offsets, the totals go to d_tot[0..C), out gets C arrays of n + 1 (out = nullptr: the
-// caller's own kernel applies the offsets, and no k_sscan_apply is made for this Ld).  Timed under `id`.
+// caller's own kernel applies the offsets, and no k_sscan_apply is made for this Ld).  Timed under `id`.  sscan_in: the same in
+// a sums buffer of the caller's (the work areas that scan inside a loop own theirs and take nothing from the arena there).
 template <int C, class Ld, class Out>
-static int sscan(fx_handle *h, Staged &st, int id, Ld ld, int64_t n, Out out, int64_t *d_tot, int64_t **sums_out = nullptr) {
+static int sscan_in(fx_handle *h, int id, Ld ld, int64_t n, Out out, int64_t *d_tot, int64_t *sums) {
     const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
-    int64_t *sums = nullptr;
-    int rc = st.scratch<int64_t>(nch * C, &sums);
-    if (rc) return rc;
     FX_LAUNCH(h, id, (k_sscan_sums<C, Ld>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums);
     FX_LAUNCH(h, id, (k_sscan_top<C>), dim3(1), dim3(BLOCK), sums, nch, d_tot);
     if constexpr (!std::is_same_v<Out, std::nullptr_t>)
         FX_LAUNCH(h, id, (k_sscan_apply<C, Ld>), dim3((unsigned)nch), dim3(BLOCK), ld, n, (const int64_t *)sums, (int64_t *)out);
     HIPCHK(hipGetLastError());
-    if (sums_out) *sums_out = sums;
     return FX_OK;
+}
+template <int C, class Ld, class Out>
+static int sscan(fx_handle *h, Staged &st, int id, Ld ld, int64_t n, Out out, int64_t *d_tot, int64_t **sums_out = nullptr) {
+    int64_t *sums = nullptr;
+    int rc = st.scratch<int64_t>((n + SRCH_CHUNK - 1) / SRCH_CHUNK * C, &sums);
+    if (rc) return rc;
+    if (sums_out) *sums_out = sums;
+    return sscan_in<C>(h, id, ld, n, out, d_tot, sums);
 }
 
 // The device's "first bad query" flag: kernels atomicMin the index of a query they reject into *d.
@@ -3461,6 +3466,82 @@ static int lane_groups(int lpr) { return (BLOCK / 64) * (64 / lpr); }           
 template <auto KERN> static unsigned lane_group_grid(fx_handle *h, int64_t nq, int lpr) {
     static const int64_t resident = resident_blocks(h, KERN);
     return (unsigned)std::min<int64_t>(nblocks(nq, lane_groups(lpr)), resident);
+}
+
+// The n queries of a call on the FASTQ table, on the device: the ids (null: every read) and, where given, an interval each.
+// check: the intervals against their reads (k_kmer_fq_check, timed under K_KMER_SCAN; waits); *first_bad = the first one outside.
+struct FqQueries { const int64_t *ids = nullptr, *start = nullptr, *end = nullptr; };
+static int fq_queries(fx_handle *h, Staged &st, const int64_t *ids, int64_t n, const int64_t *start, const int64_t *end, int64_t *first_bad,
+                      FqQueries *Q, bool check = true) {
+    int rc;
+    st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
+    if ((rc = st.up(h, ids, ids ? n : 0, &Q->ids)) || (rc = st.up(h, start, start ? n : 0, &Q->start)) || (rc = st.up(h, end, end ? n : 0, &Q->end))) return rc;
+    if (!start || !check) return FX_OK;
+    BadFlag bad;
+    if ((rc = bad.arm(h, st))) return rc;
+    FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), h->fq_rlen.p, Q->ids, n, Q->start, Q->end, bad.d);
+    HIPCHK(hipGetLastError());
+    if ((rc = bad.read(h, first_bad))) return rc;
+    return *first_bad >= 0 ? fail(FX_ERANGE, kBadInterval, (long long)*first_bad) : FX_OK;
+}
+
+// The flags `pass` of n > 0 elements -> the ascending positions of the set ones in block 0 of `out`, their number in *total.
+// The scan (two launches under id_scan: k_fq_select_emit, under id_emit, applies the chunk offsets itself) leaves the total in
+// d_tot[0], which is waited for; every one of the `cols` pinned blocks gets max(total, 1) words (no_mem: the message without
+// them).  No position: nothing more is launched.  after(positions, total) enqueues what fills the columns behind the first:
+// the device block holds N columns of `total` words.
+template <int N, class After = std::nullptr_t>
+static int emit_passing(fx_handle *h, Staged &st, int id_scan, int id_emit, const char *what, const char *no_mem, const uint8_t *pass, int64_t n,
+                        int64_t *d_tot, PinnedOut<N> &out, int cols, int64_t *total, After after = nullptr) {
+    int rc;
+    int64_t *sums = nullptr;
+    if ((rc = sscan<1>(h, st, id_scan, QcLdPass{pass}, n, nullptr, d_tot, &sums)) || (rc = read_home(h, total, d_tot, 8))) return rc;
+    for (int c = 0; c < cols; ++c)
+        if (!out.alloc(c, std::max<int64_t>(*total, 1) * 8)) return fail(FX_ENOMEM, no_mem, (long long)*total);
+    if (*total == 0) { h->prof.drain(); return FX_OK; }
+    ScratchBuf<int64_t> dev;                                 // the positions, then the columns behind them
+    if ((rc = dev.alloc(h->device, N * *total, h->stream))) return rc;
+    FX_LAUNCH(h, id_emit, k_fq_select_emit, dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), pass, n, (const int64_t *)sums, dev.p);
+    if constexpr (!std::is_same_v<After, std::nullptr_t>) after(dev.p, *total);
+    D2H col[N];
+    for (int c = 0; c < N; ++c) col[c] = {out.p[c], dev.p + c * *total, c < cols ? *total * 8 : 0};
+    return home(h, what, col, N);
+}
+
+// Variable-length records of n queries into pinned memory (*dst, their n + 1 offsets in *dst_off): count(sizes, bad flag) sizes
+// every record (0: dropped) and flags a query it rejects (-> *first_bad, bad_fmt); the scan under id_scan gives the offsets, the
+// bytes and the records there (-> *n_there), both enqueued home before the flag is waited for; emit(offsets, bytes) writes them.
+// The pinned blocks are taken only once the flag is clean.  n == 0: one offset of 0.
+template <class Count, class Emit>
+static int run_records(fx_handle *h, Staged &st, int64_t n, int id_scan, const char *what, const char *bad_fmt, Count count, Emit emit,
+                       uint8_t **dst, int64_t **dst_off, int64_t *n_there, int64_t *first_bad) {
+    int rc;
+    PinnedOut<2> out(h);                                   // the records, their offsets
+    if (n == 0) {
+        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
+        out.as<int64_t>(1)[0] = 0;
+    } else {
+        ScratchBuf<int64_t> cnt, offs;                     // record sizes; exclusive offsets (n + 1), then the records there (n + 1)
+        int64_t *d_tot = nullptr, tot[2] = {0, 0};
+        BadFlag bad;
+        if ((rc = cnt.alloc(h->device, n, h->stream)) || (rc = offs.alloc(h->device, 2 * (n + 1), h->stream)) || (rc = st.scratch<int64_t>(2, &d_tot)) ||
+            (rc = bad.arm(h, st)))
+            return rc;
+        count(cnt.p, bad.d);
+        if ((rc = sscan<2>(h, st, id_scan, FmtLdCnt{cnt.p}, n, offs.p, d_tot))) return rc;
+        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h->stream));             // (lands before the flag does)
+        if ((rc = bad.read(h, first_bad))) return rc;
+        if (*first_bad >= 0) return fail(FX_ERANGE, bad_fmt, (long long)*first_bad);
+        const int64_t total = tot[0];
+        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
+        ScratchBuf<uint8_t> dev;
+        if ((rc = dev.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return rc;
+        if (total > 0) emit((const int64_t *)offs.p, dev.p);
+        if ((rc = home(h, what, {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}}))) return rc;
+        *n_there = tot[1];
+    }
+    out.release(dst, dst_off);
+    return FX_OK;
 }
 
 // The plan of a pass over the runs of the selected FASTA records (fx_search.hpp): the 16-byte aligned view of the blob, the table,
@@ -4568,19 +4649,10 @@ extern "C" int fx_fastq_select(fx_handle *h, int phred, int low_qual, int64_t mi
     if (n > 0) {
         Staged st(h);
         ScratchBuf<uint8_t> pass;
-        int64_t *sums = nullptr, *d_tot = nullptr;
+        int64_t *d_tot = nullptr;
         if ((rc = pass.alloc(h->device, n, h->stream)) || (rc = st.scratch<int64_t>(1, &d_tot))) return rc;
         qc_launch_reads<true>(h, q, nullptr, n, QcCols{}, QcSel{min_len, max_len, mq_num, mq_den, lf_num, lf_den, max_other}, pass.p);
-        // the chunk offsets and the total; k_fq_select_emit applies the offsets itself
-        if ((rc = sscan<1>(h, st, K_FQ_SELECT_SCAN, QcLdPass{pass.p}, n, nullptr, d_tot, &sums)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
-        if (!out.alloc(0, std::max<int64_t>(total, 1) * 8)) return fail(FX_ENOMEM, "pinned block for %lld ids", (long long)total);
-        if (total == 0) h->prof.drain();
-        else {
-            ScratchBuf<int64_t> dev;
-            if ((rc = dev.alloc(h->device, total, h->stream))) return rc;
-            FX_LAUNCH(h, K_FQ_SELECT_EMIT, k_fq_select_emit, dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, dev.p);
-            if ((rc = home(h, "select emit", {{out.p[0], dev.p, total * 8}}))) return rc;
-        }
+        if ((rc = emit_passing(h, st, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, "select emit", "pinned block for %lld ids", pass.p, n, d_tot, out, 1, &total))) return rc;
     } else if (!out.alloc(0, 8)) return FX_ENOMEM;
     out.release(ids);
     *n_ids = total;
@@ -4692,41 +4764,20 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
     if (!rc) rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
     if (rc) return rc;
     const int64_t n = ids ? n_ids : h->n_reads;
-    PinnedOut<2> out(h);                                   // the records, their offsets
-    int64_t kept = 0;
-    if (n == 0) {
-        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
-        out.as<int64_t>(1)[0] = 0;
-    } else {
-        Staged st(h);
-        st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
-        const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
-        if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
-        ScratchBuf<int64_t> cnt, offs;                     // record sizes; exclusive offsets (n + 1), then the kept counts (n + 1)
-        int64_t *d_tot = nullptr, tot[2] = {0, 0};
-        BadFlag bad;
-        if ((rc = cnt.alloc(h->device, n, h->stream)) || (rc = offs.alloc(h->device, 2 * (n + 1), h->stream)) || (rc = st.scratch<int64_t>(2, &d_tot)) ||
-            (rc = bad.arm(h, st)))
-            return rc;
-        const FqView v = fq_view(h);
-        FX_LAUNCH(h, K_FQ_FORMAT_COUNT, k_fq_format_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.data, v.base, v.n, v.rlen, v.soff, v.dlen, d_ids, n,
-                  d_start, d_end, min_len, cnt.p, bad.d);
-        if ((rc = sscan<2>(h, st, K_FQ_FORMAT_SCAN, FmtLdCnt{cnt.p}, n, offs.p, d_tot))) return rc;
-        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h->stream));             // (lands before the flag does)
-        if ((rc = bad.read(h, first_bad))) return rc;
-        if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
-        const int64_t total = tot[0];
-        kept = tot[1];
-        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
-        ScratchBuf<uint8_t> dev;
-        if ((rc = dev.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return rc;
-        if (total > 0)                                     // (every record at once: the grid is not capped at the resident workgroups)
-            FX_LAUNCH(h, K_FQ_FORMAT_EMIT, k_fq_format_emit, dim3(nblocks(n, lane_groups(q.lpr))), dim3(BLOCK), v.data, v.base, v.n, v.soff, v.qoff, v.dlen,
-                      d_ids, n, d_start, (const int64_t *)offs.p, q.lpr, dev.p);
-        if ((rc = home(h, "format", {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}}))) return rc;
-    }
-    out.release(dst, dst_off);
-    *n_rows = n; *n_kept = kept;
+    Staged st(h);
+    FqQueries Q;                                           // (the count kernel checks the intervals itself)
+    if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &Q, false))) return rc;
+    const FqView v = fq_view(h);
+    auto count = [&](int64_t *cnt, unsigned long long *bad) {
+        FX_LAUNCH(h, K_FQ_FORMAT_COUNT, k_fq_format_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.data, v.base, v.n, v.rlen, v.soff, v.dlen, Q.ids, n,
+                  Q.start, Q.end, min_len, cnt, bad);
+    };
+    auto emit = [&](const int64_t *offs, uint8_t *dev) {   // (every record at once: the grid is not capped at the resident workgroups)
+        FX_LAUNCH(h, K_FQ_FORMAT_EMIT, k_fq_format_emit, dim3(nblocks(n, lane_groups(q.lpr))), dim3(BLOCK), v.data, v.base, v.n, v.soff, v.qoff, v.dlen,
+                  Q.ids, n, Q.start, offs, q.lpr, dev);
+    };
+    if ((rc = run_records(h, st, n, K_FQ_FORMAT_SCAN, "format", kBadInterval, count, emit, dst, dst_off, n_kept, first_bad))) return rc;
+    *n_rows = n;
     return FX_OK;
 }
 
@@ -4915,42 +4966,23 @@ extern "C" int fx_fastq_pair_merge_alloc(fx_handle *h1, fx_handle *h2, const int
     if (rc) return rc;
     const int64_t n = ids ? n_ids : h1->n_reads;
     if (n > 0 && !diag) return fail(FX_EINVAL, "null argument");
-    PinnedOut<2> out(h1);                                  // the records, their offsets
-    int64_t merged = 0;
-    if (n == 0) {
-        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
-        out.as<int64_t>(1)[0] = 0;
-    } else {
-        Staged st(h1);
-        st.reserve_pin((ids ? n : 0) * 8 + n * 4 + 1024);
-        const int64_t *d_ids = nullptr;
-        const int32_t *d_diag = nullptr;
-        if ((rc = st.up(h1, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h1, diag, n, &d_diag))) return rc;
-        ScratchBuf<int64_t> cnt, offs;                     // record sizes; exclusive offsets (n + 1), then the merged counts (n + 1)
-        int64_t *d_tot = nullptr, tot[2] = {0, 0};
-        BadFlag bad;
-        if ((rc = cnt.alloc(h1->device, n, h1->stream)) || (rc = offs.alloc(h1->device, 2 * (n + 1), h1->stream)) || (rc = st.scratch<int64_t>(2, &d_tot)) ||
-            (rc = bad.arm(h1, st)))
-            return rc;
-        const PairSrc A = pair_src(h1), B = pair_src(h2);
-        FX_LAUNCH(h1, K_FP_MERGE_COUNT, k_fp_merge_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), A, B, d_ids, n, d_diag, min_len, cnt.p, bad.d);
-        if ((rc = sscan<2>(h1, st, K_FP_MERGE_SCAN, FmtLdCnt{cnt.p}, n, offs.p, d_tot))) return rc;
-        HIPCHK(hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, h1->stream));            // (lands before the flag does)
-        if ((rc = bad.read(h1, first_bad))) return rc;
-        if (*first_bad >= 0) return fail(FX_ERANGE, "the diagonal of query %lld lies outside its pair", (long long)*first_bad);
-        const int64_t total = tot[0];
-        merged = tot[1];
-        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
-        ScratchBuf<uint8_t> dev;
-        if ((rc = dev.alloc(h1->device, std::max<int64_t>(total, 1), h1->stream))) return rc;
-        const int lpr = std::max(q1.lpr, q2.lpr);
-        if (total > 0)                                     // (every record at once: the grid is not capped at the resident workgroups)
-            FX_LAUNCH(h1, K_FP_MERGE_EMIT, k_fp_merge_emit, dim3(nblocks(n, lane_groups(lpr))), dim3(BLOCK), A, B, d_ids, n, d_diag, (const int64_t *)offs.p, lpr,
-                      dev.p);
-        if ((rc = home(h1, "pair merge", {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}}))) return rc;
-    }
-    out.release(dst, dst_off);
-    *n_rows = n; *n_merged = merged;
+    Staged st(h1);
+    st.reserve_pin((ids ? n : 0) * 8 + n * 4 + 1024);
+    const int64_t *d_ids = nullptr;
+    const int32_t *d_diag = nullptr;
+    if ((rc = st.up(h1, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h1, diag, n, &d_diag))) return rc;
+    const PairSrc A = pair_src(h1), B = pair_src(h2);
+    const int lpr = std::max(q1.lpr, q2.lpr);
+    auto count = [&](int64_t *cnt, unsigned long long *bad) {
+        FX_LAUNCH(h1, K_FP_MERGE_COUNT, k_fp_merge_count, dim3(nblocks(n, BLOCK)), dim3(BLOCK), A, B, d_ids, n, d_diag, min_len, cnt, bad);
+    };
+    auto emit = [&](const int64_t *offs, uint8_t *dev) {   // (every record at once: the grid is not capped at the resident workgroups)
+        FX_LAUNCH(h1, K_FP_MERGE_EMIT, k_fp_merge_emit, dim3(nblocks(n, lane_groups(lpr))), dim3(BLOCK), A, B, d_ids, n, d_diag, offs, lpr, dev);
+    };
+    if ((rc = run_records(h1, st, n, K_FP_MERGE_SCAN, "pair merge", "the diagonal of query %lld lies outside its pair", count, emit, dst, dst_off, n_merged,
+                          first_bad)))
+        return rc;
+    *n_rows = n;
     return FX_OK;
 }
 
@@ -5049,18 +5081,9 @@ extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t 
     KmerOut out(h);
     if (n > 0) {
         Staged st(h);
-        st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
-        const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
-        if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+        FqQueries Q;
+        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &Q))) return rc;
         const FqView v = fq_view(h);
-        if (start) {
-            BadFlag bad;
-            if ((rc = bad.arm(h, st))) return rc;
-            FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, d_ids, n, d_start, d_end, bad.d);
-            HIPCHK(hipGetLastError());
-            if ((rc = bad.read(h, first_bad))) return rc;
-            if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
-        }
         if ((rc = out.prepare(h, k, 1, true))) return rc;
         // queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
         const int64_t per = std::max<int64_t>(KMER_MAX_WINDOWS / std::max<int64_t>((int64_t)h->fq_maxlen, 1), 1);
@@ -5069,7 +5092,7 @@ extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t 
                 for (int64_t q0 = 0; q0 < n; q0 += per) {
                     const int64_t q1 = std::min(q0 + per, n);
                     FX_LAUNCH(h, K_KMER_FASTQ, (k_kmer_fastq<C(), L()>), dim3(lane_group_grid<k_kmer_fastq<C(), L()>>(h, q1 - q0, q.lpr)), dim3(BLOCK), v.data,
-                              v.base, v.n, v.rlen, v.soff, d_ids, q0, q1, d_start, d_end, q.lpr, k, out.dev.p);
+                              v.base, v.n, v.rlen, v.soff, Q.ids, q0, q1, Q.start, Q.end, q.lpr, k, out.dev.p);
                 }
             });
         });
@@ -5147,11 +5170,8 @@ struct KtWork {
     }
     // flagged elements among n > 0 -> *total (waits); the chunk offsets stay in `sums` for the compaction that follows
     template <class Ld> int count(int id, Ld ld, int64_t n, int64_t *total) {
-        const int64_t nch = (n + SRCH_CHUNK - 1) / SRCH_CHUNK;
-        FX_LAUNCH(h, id, (k_sscan_sums<1, Ld>), dim3((unsigned)nch), dim3(BLOCK), ld, n, sums.p);
-        FX_LAUNCH(h, id, (k_sscan_top<1>), dim3(1), dim3(BLOCK), sums.p, nch, d_tot);
-        HIPCHK(hipGetLastError());
-        return read_home(h, total, d_tot, 8);
+        const int rc_ = sscan_in<1>(h, id, ld, n, nullptr, d_tot, sums.p);
+        return rc_ ? rc_ : read_home(h, total, d_tot, 8);
     }
     template <class Ld, class Put> void compact(int id, Ld ld, int64_t n, Put put) {
         FX_LAUNCH(h, id, (k_kt_compact<Ld, Put>), dim3((unsigned)((n + SRCH_CHUNK - 1) / SRCH_CHUNK)), dim3(BLOCK), ld, n, (const int64_t *)sums.p, put);
@@ -5360,18 +5380,9 @@ extern "C" int fx_fastq_kmer_table(fx_handle *h, int32_t k, int flags, const int
     KtOut out(h);
     if (n > 0) {
         Staged st(h);
-        st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
-        const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
-        if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+        FqQueries Q;
+        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &Q))) return rc;
         const FqView v = fq_view(h);
-        if (start) {
-            BadFlag bad;
-            if ((rc = bad.arm(h, st))) return rc;
-            FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, d_ids, n, d_start, d_end, bad.d);
-            HIPCHK(hipGetLastError());
-            if ((rc = bad.read(h, first_bad))) return rc;
-            if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
-        }
         const bool canon = flags & FX_KMER_CANONICAL;
         KtSource src;
         src.units = n; src.per_unit = std::max<int64_t>((int64_t)h->fq_maxlen, 1);
@@ -5383,7 +5394,7 @@ extern "C" int fx_fastq_kmer_table(fx_handle *h, int32_t k, int flags, const int
                     for (int64_t q0 = u0; q0 < u1; q0 += per) {
                         const int64_t q1 = std::min(q0 + per, u1);
                         FX_LAUNCH(h, E() ? K_KT_EMIT : K_KT_HIST, (k_kt_fastq<C(), E()>), dim3(lane_group_grid<k_kt_fastq<C(), E()>>(h, q1 - q0, q.lpr)), dim3(BLOCK),
-                                  v.data, v.base, v.n, v.rlen, v.soff, d_ids, q0, q1, d_start, d_end, q.lpr, (int)k, A);
+                                  v.data, v.base, v.n, v.rlen, v.soff, Q.ids, q0, q1, Q.start, Q.end, q.lpr, (int)k, A);
                     }
                 });
             });
@@ -5496,18 +5507,9 @@ struct KsCols {
 static int ks_fastq_run(fx_handle *h, const fx_kmer_set *set, Staged &st, const FqLaunch &q, const int64_t *ids, int64_t n, const int64_t *start,
                         const int64_t *end, int64_t *first_bad, KsCols &o) {
     int rc;
-    st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
-    const int64_t *d_ids = nullptr, *d_start = nullptr, *d_end = nullptr;
-    if ((rc = st.up(h, ids, ids ? n : 0, &d_ids)) || (rc = st.up(h, start, start ? n : 0, &d_start)) || (rc = st.up(h, end, end ? n : 0, &d_end))) return rc;
+    FqQueries Q;
+    if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &Q))) return rc;
     const FqView v = fq_view(h);
-    if (start) {
-        BadFlag bad;
-        if ((rc = bad.arm(h, st))) return rc;
-        FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, d_ids, n, d_start, d_end, bad.d);
-        HIPCHK(hipGetLastError());
-        if ((rc = bad.read(h, first_bad))) return rc;
-        if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
-    }
     const int64_t stride = (n + 63) & ~(int64_t)63;
     if ((rc = o.dev.alloc(h->device, 2 * stride, h->stream))) return rc;
     o.nw = o.dev.p; o.nh = o.dev.p + stride;
@@ -5518,7 +5520,7 @@ static int ks_fastq_run(fx_handle *h, const fx_kmer_set *set, Staged &st, const 
         with_bool(set->in_lds(), [&](auto L) {
             auto kern = k_ks_fastq<C(), L()>;
             FX_LAUNCH_LDS(h, K_KS_FASTQ, kern, dim3(ks_grid(h, kern, lds, nblocks(n, lane_groups(lpr)))), dim3(BLOCK), lds, v.data, v.base, v.n, v.rlen,
-                          v.soff, d_ids, n, d_start, d_end, lpr, k, S, o.nw, o.nh);
+                          v.soff, Q.ids, n, Q.start, Q.end, lpr, k, S, o.nw, o.nh);
         });
     });
     HIPCHK(hipGetLastError());
@@ -5568,21 +5570,12 @@ extern "C" int fx_fastq_kmer_screen(fx_handle *h, const fx_kmer_set *set, const 
         Staged st(h);
         KsCols o;
         ScratchBuf<uint8_t> pass;
-        int64_t *sums = nullptr, *d_tot = nullptr;
+        int64_t *d_tot = nullptr;
         if ((rc = ks_fastq_run(h, set, st, q, ids, n, start, end, first_bad, o))) return rc;
         if ((rc = pass.alloc(h->device, n, h->stream)) || (rc = st.scratch<int64_t>(1, &d_tot))) return rc;
         FX_LAUNCH(h, K_KS_SCREEN, k_ks_pass, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int32_t *)o.nw, (const int32_t *)o.nh, n, min_hits, frac_num, frac_den,
                   invert, pass.p);
-        // the chunk offsets and the total; k_fq_select_emit applies the offsets itself
-        if ((rc = sscan<1>(h, st, K_KS_SCREEN, QcLdPass{pass.p}, n, nullptr, d_tot, &sums)) || (rc = read_home(h, &total, d_tot, 8))) return rc;
-        if (!out.alloc(0, std::max<int64_t>(total, 1) * 8)) return fail(FX_ENOMEM, "pinned block for %lld positions", (long long)total);
-        if (total == 0) h->prof.drain();
-        else {
-            ScratchBuf<int64_t> dev;
-            if ((rc = dev.alloc(h->device, total, h->stream))) return rc;
-            FX_LAUNCH(h, K_KS_SCREEN, k_fq_select_emit, dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, dev.p);
-            if ((rc = home(h, "screen emit", {{out.p[0], dev.p, total * 8}}))) return rc;
-        }
+        if ((rc = emit_passing(h, st, K_KS_SCREEN, K_KS_SCREEN, "screen emit", "pinned block for %lld positions", pass.p, n, d_tot, out, 1, &total))) return rc;
     } else if (!out.alloc(0, 8)) return fail(FX_ENOMEM, "pinned block");
     out.release(pos);
     *n_pos = total;
@@ -5666,26 +5659,8 @@ struct DdWork {
     }
 };
 
-// What the two entries check before anything is allocated, in the order of the screening entries; the queries on the device.
-struct DdArgs { FqLaunch q; int64_t n; const int64_t *d_ids, *d_start, *d_end; };
-static int dd_prepare(fx_handle *h, Staged &st, const int64_t *ids, const int64_t *start, const int64_t *end, int64_t *first_bad, DdArgs *a) {
-    int rc;
-    a->d_ids = a->d_start = a->d_end = nullptr;
-    const int64_t n = a->n;
-    if (n == 0) return FX_OK;
-    st.reserve_pin(((ids ? n : 0) + (start ? 2 * n : 0)) * 8 + 1024);
-    if ((rc = st.up(h, ids, ids ? n : 0, &a->d_ids)) || (rc = st.up(h, start, start ? n : 0, &a->d_start)) || (rc = st.up(h, end, end ? n : 0, &a->d_end))) return rc;
-    if (start) {
-        const FqView v = fq_view(h);
-        BadFlag bad;
-        if ((rc = bad.arm(h, st))) return rc;
-        FX_LAUNCH(h, K_KMER_SCAN, k_kmer_fq_check, dim3(nblocks(n, BLOCK)), dim3(BLOCK), v.rlen, a->d_ids, n, a->d_start, a->d_end, bad.d);
-        HIPCHK(hipGetLastError());
-        if ((rc = bad.read(h, first_bad))) return rc;
-        if (*first_bad >= 0) return fail(FX_ERANGE, kBadInterval, (long long)*first_bad);
-    }
-    return FX_OK;
-}
+// What the two entries check before anything is allocated, in the order of the screening entries; then the queries on the device.
+struct DdArgs { FqLaunch q; int64_t n; FqQueries Q; };
 static int dd_check(fx_handle *h, const int64_t *ids, int64_t n_ids, int flags, int hash_bits, int64_t min_copies, int64_t *first_bad, DdArgs *a) {
     if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
     int rc = fq_prepare(h, 0, 0, &a->q);                       // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
@@ -5706,7 +5681,7 @@ static int dd_run(fx_handle *h, const DdArgs &a, int flags, int hash_bits, bool 
     const int lpr = a.q.lpr, bits = hash_bits ? hash_bits : 64;
     const uint64_t mask = bits == 64 ? ~0ull : (1ull << bits) - 1ull;
     const bool revcomp = flags & FX_DUP_REVCOMP;
-    DdQueries Q{v.rlen, v.soff, a.d_ids, a.d_start, a.d_end, nullptr, v.base};
+    DdQueries Q{v.rlen, v.soff, a.Q.ids, a.Q.start, a.Q.end, nullptr, v.base};
     int64_t m = a.n, groups = 0, rounds = 0;
     int lcur = 0;
     while (m > 0) {
@@ -5724,9 +5699,7 @@ static int dd_run(fx_handle *h, const DdArgs &a, int flags, int hash_bits, bool 
         h->prof.end(h->stream);
         if (e != hipSuccess) return fail(FX_EDEVICE, "duplicate sort: %s", hipGetErrorString(e));
         // head flags -> rank and heads; every sorted element against its head; the group sizes; the unresolved counted
-        const KtLdHead heads{kp[cur]};
-        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_sums<1, KtLdHead>), dim3(nch), dim3(BLOCK), heads, m, w.sums.p);
-        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_top<1>), dim3(1), dim3(BLOCK), w.sums.p, (int64_t)nch, w.d_tot);
+        if ((rc = sscan_in<1>(h, K_DD_VERIFY, KtLdHead{kp[cur]}, m, nullptr, w.d_tot, w.sums.p))) return rc;
         FX_LAUNCH(h, K_DD_VERIFY, k_dd_rank, dim3(nch), dim3(BLOCK), (const uint64_t *)kp[cur], m, (const int64_t *)w.sums.p, w.G.p, w.S.p);
         if (want_copies) HIPCHK(hipMemsetAsync(w.unres.p, 0, (size_t)m * 4, h->stream));
         with_bool(revcomp, [&](auto R) {
@@ -5737,9 +5710,7 @@ static int dd_run(fx_handle *h, const DdArgs &a, int flags, int hash_bits, bool 
             FX_LAUNCH(h, K_DD_VERIFY, k_dd_copies, dim3(nblocks(m, BLOCK)), dim3(BLOCK), (const uint32_t *)w.S.p, (const int64_t *)w.d_tot, m,
                       (const uint32_t *)vp[cur], Q.list, (const uint32_t *)w.unres.p, w.copies.p);
         const QcLdPass left{w.flag.p};
-        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_sums<1, QcLdPass>), dim3(nch), dim3(BLOCK), left, m, w.sums.p);
-        FX_LAUNCH(h, K_DD_VERIFY, (k_sscan_top<1>), dim3(1), dim3(BLOCK), w.sums.p, (int64_t)nch, w.d_tot + 1);
-        HIPCHK(hipGetLastError());
+        if ((rc = sscan_in<1>(h, K_DD_VERIFY, left, m, nullptr, w.d_tot + 1, w.sums.p))) return rc;
         int64_t tot[2] = {0, 0};                              // the runs of this round, what it left unresolved
         if ((rc = read_home(h, tot, w.d_tot, 16))) return rc;
         groups += tot[0];
@@ -5771,7 +5742,7 @@ extern "C" int fx_fastq_dup_first(fx_handle *h, const int64_t *ids, int64_t n_id
     if (n > 0) {
         Staged st(h);
         DdWork w;
-        if ((rc = dd_prepare(h, st, ids, start, end, first_bad, &a)) || (rc = w.alloc(h, st, n, false))) return rc;
+        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &a.Q)) || (rc = w.alloc(h, st, n, false))) return rc;
         if (!out.alloc(0, n * 8)) return fail(FX_ENOMEM, "pinned block for %lld rows", (long long)n);
         if ((rc = dd_run(h, a, flags, hash_bits, false, w, n_groups, n_rounds)) || (rc = home(h, "duplicates", {{out.p[0], w.first.p, n * 8}}))) {
             *n_groups = *n_rounds = 0;
@@ -5796,32 +5767,25 @@ extern "C" int fx_fastq_dedup(fx_handle *h, const int64_t *ids, int64_t n_ids, c
     const int64_t n = a.n;
     int64_t total = 0;
     PinnedOut<2> out(h);
-    auto pinned = [&](int64_t rows) { return out.alloc(0, std::max<int64_t>(rows, 1) * 8) && (!copies || out.alloc(1, std::max<int64_t>(rows, 1) * 8)); };
     if (n > 0) {
         Staged st(h);
         DdWork w;
         ScratchBuf<uint8_t> pass;
-        int64_t *sums = nullptr, groups = 0, rounds = 0;
-        if ((rc = dd_prepare(h, st, ids, start, end, first_bad, &a)) || (rc = w.alloc(h, st, n, true)) ||
+        int64_t groups = 0, rounds = 0;
+        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &a.Q)) || (rc = w.alloc(h, st, n, true)) ||
             (rc = pass.alloc(h->device, n, h->stream)) || (rc = dd_run(h, a, flags, hash_bits, true, w, &groups, &rounds)))
             return rc;
         FX_LAUNCH(h, K_DD_SELECT, k_dd_pass, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)w.first.p, (const uint32_t *)w.copies.p, n, min_copies,
                   max_copies, pass.p);
-        // the chunk offsets and the total; k_fq_select_emit applies the offsets itself
-        if ((rc = sscan<1>(h, st, K_DD_SELECT, QcLdPass{pass.p}, n, nullptr, w.d_tot, &sums)) || (rc = read_home(h, &total, w.d_tot, 8))) return rc;
-        if (!pinned(total)) return fail(FX_ENOMEM, "pinned blocks for %lld positions", (long long)total);
-        if (total == 0) h->prof.drain();
-        else {
-            ScratchBuf<int64_t> dev;                           // the positions, then their copies
-            if ((rc = dev.alloc(h->device, 2 * total, h->stream))) return rc;
-            FX_LAUNCH(h, K_DD_SELECT, k_fq_select_emit, dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), (const uint8_t *)pass.p, n, (const int64_t *)sums, dev.p);
+        auto gather = [&](int64_t *at, int64_t m) {           // the copies of every position, behind the positions
             if (copies)
-                FX_LAUNCH(h, K_DD_SELECT, k_dd_gather, dim3(nblocks(total, BLOCK)), dim3(BLOCK), (const int64_t *)dev.p, total, (const uint32_t *)w.copies.p,
-                          dev.p + total);
-            if ((rc = home(h, "dedup emit", {{out.p[0], dev.p, total * 8}, {out.p[1], dev.p + total, copies ? total * 8 : 0}}))) return rc;
-        }
+                FX_LAUNCH(h, K_DD_SELECT, k_dd_gather, dim3(nblocks(m, BLOCK)), dim3(BLOCK), (const int64_t *)at, m, (const uint32_t *)w.copies.p, at + m);
+        };
+        if ((rc = emit_passing(h, st, K_DD_SELECT, K_DD_SELECT, "dedup emit", "pinned blocks for %lld positions", pass.p, n, w.d_tot, out, copies ? 2 : 1, &total,
+                               gather)))
+            return rc;
         *n_groups = groups; *n_rounds = rounds;
-    } else if (!pinned(0)) return fail(FX_ENOMEM, "pinned blocks");
+    } else if (!out.alloc(0, 8) || (copies && !out.alloc(1, 8))) return fail(FX_ENOMEM, "pinned blocks");
     out.release(pos, copies);
     *n_pos = total;
     return FX_OK;
