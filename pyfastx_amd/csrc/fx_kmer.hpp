@@ -19,6 +19,8 @@
 //   counts the windows that END in its piece and warms up on the last k - 1 <= 12 bytes of the piece in front (one more
 //   16-byte load; it hits the cache, the neighbour lane loads the same bytes).  A read longer than 16 * lpr is covered by
 //   further steps of the same lanes.  Bytes in front of `start` are skipped, so no window begins before it.
+// Both walks (kmer_walk, kmer_fq_pieces) and the rolling state are templates on the code word: the sparse table and the screen
+//   (fx_kmer_table.hpp, fx_kmer_screen.hpp, k <= 31) run the same code with 64-bit words and a warm-up of up to 32 bytes.
 //
 // Counters.  Every lane first aggregates: it remembers the last two distinct codes and how often it has met each, and
 // only a third code makes it add the older pair.  A single-letter run (one code) and a dinucleotide run (two codes that
@@ -49,17 +51,18 @@ __device__ __forceinline__ uint32_t kmer_code(uint32_t c) {
     return u == ((QC_EX_LO >> (8 * x)) & 0xFFu) ? x ^ (x >> 1) : KMER_INVALID;
 }
 
-template <bool CANON>
+// Word: uint32_t holds the codes of the dense form (k <= 13), uint64_t those of the table and the screen (k <= 31)
+template <class Word, bool CANON>
 struct KmerRoll {
-    uint32_t fw = 0, rc = 0;
+    Word fw = 0, rc = 0;
     int v = 0;                                               // valid bases in a row, capped at k
-    __device__ __forceinline__ void step(uint32_t code, int k, uint32_t mask, int sh) {
+    __device__ __forceinline__ void step(uint32_t code, int k, Word mask, int sh) {
         if (code > 3u) { v = 0; return; }
         fw = ((fw << 2) | code) & mask;
-        if (CANON) rc = (rc >> 2) | ((3u - code) << sh);
+        if (CANON) rc = (rc >> 2) | ((Word)(3u - code) << sh);
         v = v < k ? v + 1 : k;
     }
-    __device__ __forceinline__ uint32_t value() const { return CANON ? (fw < rc ? fw : rc) : fw; }
+    __device__ __forceinline__ Word value() const { return CANON ? (fw < rc ? fw : rc) : fw; }
 };
 
 // the last two distinct codes of a lane and their counts; add(code, n) is called when a third one pushes the older out
@@ -81,58 +84,75 @@ struct KmerAgg {
 };
 
 // Walk one run: raw bytes [lo, hi) of the address space of a record that begins at b.  Every valid window that ends at a
-// kept byte whose local index (0 at lo) is at least `from` goes to on_win(code).  -> kept bytes in [lo, hi).
-template <bool CANON, class F>
-__device__ __forceinline__ uint32_t kmer_walk(const SearchPlan &P, int k, int64_t b, int64_t lo, int64_t hi, int64_t from, F &&on_win) {
-    const uint32_t mask = (1u << (2 * k)) - 1u;
+// kept byte whose local index (0 at lo) lies in [from, limit) goes to on_win(code).  -> kept bytes in [lo, hi).
+template <class Word, bool CANON, class F>
+__device__ __forceinline__ uint32_t kmer_walk(const SearchPlan &P, int k, int64_t b, int64_t lo, int64_t hi, int64_t from, int64_t limit,
+                                              F &&on_win) {
+    const Word mask = ((Word)1 << (2 * k)) - 1;
     const int sh = 2 * (k - 1);
-    KmerRoll<CANON> st;
+    KmerRoll<Word, CANON> st;
+    auto step = [&](uint32_t c) { st.step(kmer_code(c), k, mask, sh); };
     if (k > 1 && lo > b) {                                   // warm-up on the k - 1 kept bytes in front of the run
         int kept = 0;
-        if ((lo & 15) == 0 && lo - 16 >= b) {
-            const uint4 pv = *reinterpret_cast<const uint4 *>(P.base + lo - 16);
-            const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
+        const int64_t reach = (sizeof(Word) == 4 || k - 1 <= 12) ? 16 : 32;    // one aligned load, or two (a 32-bit code has k <= 13)
+        if ((lo & 15) == 0 && lo - reach >= b) {
+            for (int64_t q = lo - reach; q < lo; q += 16) {
+                const uint4 pv = *reinterpret_cast<const uint4 *>(P.base + q);
+                const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const uint32_t c = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-                if (!srch_space(c)) { st.step(kmer_code(c), k, mask, sh); ++kept; }
+                for (int i = 0; i < 16; ++i) {
+                    const uint32_t c = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+                    if (!srch_space(c)) { step(c); ++kept; }
+                }
             }
         }
-        if (kept < k - 1) {                                  // white space hides them, or the record begins inside the 16 bytes
-            st = KmerRoll<CANON>();
-            int64_t ws = lo;
-            for (int need = k - 1; need > 0 && ws > b;) {
-                --ws;
-                need -= srch_space(P.base[ws]) ? 0 : 1;
-            }
-            for (int64_t p = ws; p < lo; ++p) {
-                const uint32_t c = P.base[p];
-                if (!srch_space(c)) st.step(kmer_code(c), k, mask, sh);
-            }
+        if (kept < k - 1) {                                  // white space hides them, or the record begins inside the reach
+            st = KmerRoll<Word, CANON>();
+            run_warm(P, b, lo, k - 1, step);
         }
     }
-    int64_t kidx = 0;
-    auto feed = [&](uint32_t c, bool live) {
-        if (!live || srch_space(c)) return;
-        st.step(kmer_code(c), k, mask, sh);
-        if (st.v >= k && kidx >= from) on_win(st.value());
+    uint32_t kidx = 0;                                       // 32 bits: a bound the caller passes as a constant costs no compare
+    run_walk(P, lo, hi, [&](uint32_t c) {
+        step(c);
+        if (st.v >= k && (int64_t)kidx >= from && (int64_t)kidx < limit) on_win(st.value());
         ++kidx;
-    };
-    int64_t c = lo & ~(int64_t)15;
-    uint4 v = *reinterpret_cast<const uint4 *>(P.base + c);
-    for (; c < hi; c += 16) {
-        const uint4 cur = v;
-        if (c + 16 < hi) v = *reinterpret_cast<const uint4 *>(P.base + c + 16);     // the next chunk in flight while this one is walked
-        const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
-        if (c >= lo && c + 16 <= hi) {
+    });
+    return kidx;
+}
+
+// The pieces of one lane of a FASTQ query: lane `sub` of the lpr lanes of a read whose bytes begin at data[so] takes the bytes
+// [p, p + 16) of the read, p = 16 sub, 16 (sub + lpr), ...  Every valid window of [a, b) that ENDS in such a piece -- at a byte of
+// [a + k - 1, b) -- goes to on_win(code); the state is warmed up on the k - 1 bytes in front of the piece, from `a` on: they lie
+// in the piece in front (k - 1 <= 16) or in the two in front.
+template <class Word, bool CANON, class F>
+__device__ __forceinline__ void kmer_fq_pieces(const uint8_t *__restrict__ data, int64_t so, int64_t n_bytes, int64_t a, int64_t b, int sub,
+                                               int lpr, int k, F &&on_win) {
+    constexpr bool DENSE = sizeof(Word) == 4;                // k - 1 <= 12: one piece in front, its first 4 bytes never
+    const Word mask = ((Word)1 << (2 * k)) - 1;
+    const int sh = 2 * (k - 1);
+    for (int64_t p = (int64_t)sub * 16; p < b; p += (int64_t)lpr * 16) {
+        if (p + 16 <= a + k - 1) continue;
+        KmerRoll<Word, CANON> st;
+        if (k > 1 && p > a) {
+            const int64_t ws = max(a, p - (k - 1));
+            for (int64_t f = (DENSE || k - 1 <= 16) ? p - 16 : p - 32; f < p; f += 16) {
+                if (f + 16 <= ws) continue;
+                const uint4 pv = qc_load16(data, so + f, n_bytes);
+                const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
 #pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, true);
-        } else {
+                for (int i = DENSE ? 4 : 0; i < 16; ++i)
+                    if (f + i >= ws) st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
+            }
+        }
+        const uint4 cv = qc_load16(data, so + p, n_bytes);
+        const uint32_t w[4] = {cv.x, cv.y, cv.z, cv.w};
 #pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, c + i >= lo && c + i < hi);
+        for (int i = 0; i < 16; ++i) {
+            if (p + i < a || p + i >= b) continue;
+            st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
+            if (st.v >= k) on_win(st.value());
         }
     }
-    return (uint32_t)kidx;
 }
 
 // ------------------------------------------------------------------ the LDS table of a workgroup
@@ -179,7 +199,7 @@ __global__ __launch_bounds__(BLOCK) void k_kmer_fasta(SearchPlan P, int k, int64
                 else atomicAdd(&lds[mine + code], n);
             };
             KmerAgg agg;
-            const uint32_t kept = kmer_walk<CANON>(P, k, b, lo, hi, 0, [&](uint32_t code) { agg.put(code, add); });
+            const uint32_t kept = kmer_walk<uint32_t, CANON>(P, k, b, lo, hi, 0, INT64_MAX, [&](uint32_t code) { agg.put(code, add); });
             agg.flush(add);
             packed[g] = srch_pack(0, 0, kept);
         }
@@ -209,7 +229,7 @@ __global__ __launch_bounds__(BLOCK) void k_kmer_fix(SearchPlan P, int k, const i
         const int64_t base = K[g] - K[g0];
         int64_t r, b, lo, hi;
         srch_run(P, g, s, r, b, lo, hi);
-        kmer_walk<CANON>(P, k, b, lo, hi, max(slen - base, (int64_t)0), [&](uint32_t code) { atomicAdd(row + code, ~0ull); });
+        kmer_walk<uint32_t, CANON>(P, k, b, lo, hi, max(slen - base, (int64_t)0), INT64_MAX, [&](uint32_t code) { atomicAdd(row + code, ~0ull); });
     }
 }
 
@@ -233,8 +253,7 @@ __global__ __launch_bounds__(BLOCK) void k_kmer_fastq(const uint8_t *__restrict_
                                                      unsigned long long *__restrict__ table) {
     __shared__ uint32_t lds[LDS ? KMER_LDS_WORDS : 1];
     const int lane = lane_id(), grp = lane / lpr, sub = lane - grp * lpr, ngrp = 64 / lpr;
-    const int kb = 2 * k, sh = 2 * (k - 1);
-    const uint32_t mask = (1u << kb) - 1u;
+    const int kb = 2 * k;
     const uint32_t mine = LDS ? (uint32_t)(lane & (kmer_lds_copies(k) - 1)) << kb : 0u;
     if (LDS) { kmer_lds_clear(lds); __syncthreads(); }
     auto add = [&](uint32_t code, uint32_t n) {
@@ -248,26 +267,7 @@ __global__ __launch_bounds__(BLOCK) void k_kmer_fastq(const uint8_t *__restrict_
         const int64_t id = ids ? ids[q] : q;
         const int64_t L = rlen[id] > 0 ? rlen[id] : 0, so = soff[id] - gbase;
         const int64_t a = start ? start[q] : 0, b = end ? end[q] : L;
-        // the pieces of this lane: bytes [p, p + 16) of the read; the windows that end there end in [a + k - 1, b)
-        for (int64_t p = (int64_t)sub * 16; p < b; p += (int64_t)lpr * 16) {
-            if (p + 16 <= a + k - 1) continue;
-            KmerRoll<CANON> st;
-            if (k > 1 && p > a) {                            // the last k - 1 bytes of the piece in front, from `a` on
-                const uint4 pv = qc_load16(data, so + p - 16, n_bytes);
-                const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-                for (int i = 4; i < 16; ++i)
-                    if (i >= 17 - k && p - 16 + i >= a) st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
-            }
-            const uint4 cv = qc_load16(data, so + p, n_bytes);
-            const uint32_t w[4] = {cv.x, cv.y, cv.z, cv.w};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                if (p + i < a || p + i >= b) continue;
-                st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
-                if (st.v >= k) agg.put(st.value(), add);
-            }
-        }
+        kmer_fq_pieces<uint32_t, CANON>(data, so, n_bytes, a, b, sub, lpr, k, [&](uint32_t code) { agg.put(code, add); });
     }
     agg.flush(add);
     if (LDS) { __syncthreads(); kmer_lds_flush(lds, k, table); }

@@ -19,10 +19,10 @@
 //   LDS = false   8-byte loads from global memory.
 //
 // Walks.
-//   k_ks_fastq    the lane groups, pieces and warm-up of k_kt_fastq, start / end intervals and reads longer than 16 * lpr
-//                 included; a lane counts its valid windows and its hits, qc_group_reduce brings the lanes of a group together
-//                 and its first lane stores n_windows[q], n_hits[q] (int32): no atomics, no cursor.
-//   k_ks_fasta    one lane per run as k_kt_fasta, kt_walk with limit = slen - kept bytes in front of the run (k_kt_kept and its
+//   k_ks_fastq    the lane groups of k_kt_fastq and the pieces of kmer_fq_pieces (fx_kmer.hpp), start / end intervals and reads
+//                 longer than 16 * lpr included; a lane counts its valid windows and its hits, qc_group_reduce brings the lanes
+//                 of a group together and its first lane stores n_windows[q], n_hits[q] (int32): no atomics, no cursor.
+//   k_ks_fasta    one lane per run as k_kt_fasta, kmer_walk with limit = slen - kept bytes in front of the run (k_kt_kept and its
 //                 scan come first), so nothing behind the cut at slen counts.  A lane adds its two sums to the int64 pair of its
 //                 row -- the position of its record in the selection, so a record listed twice has two rows -- with one 64-bit
 //                 atomicAdd each, left out when zero; the rows are zeroed first.
@@ -115,8 +115,6 @@ __global__ __launch_bounds__(BLOCK) void k_ks_fastq(const uint8_t *__restrict__ 
     int p2 = 1;
     while (p2 < lpr) p2 <<= 1;
     p2 >>= 1;
-    const int sh = 2 * (k - 1);
-    const uint64_t mask = (1ull << (2 * k)) - 1ull;
     const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
     const int64_t stride = (((int64_t)gridDim.x * BLOCK) >> 6) * ngrp;
     for (int64_t q = wave * ngrp + grp; q - grp < nq; q += stride) {              // wave-uniform trip count
@@ -125,32 +123,10 @@ __global__ __launch_bounds__(BLOCK) void k_ks_fastq(const uint8_t *__restrict__ 
             const int64_t id = ids ? ids[q] : q;
             const int64_t L = rlen[id] > 0 ? rlen[id] : 0, so = soff[id] - gbase;
             const int64_t a = start ? start[q] : 0, b = end ? end[q] : L;
-            // the pieces of this lane: bytes [p, p + 16) of the read; the windows that end there end in [a + k - 1, b)
-            for (int64_t p = (int64_t)sub * 16; p < b; p += (int64_t)lpr * 16) {
-                if (p + 16 <= a + k - 1) continue;
-                KmerRoll64<CANON> st;
-                if (k > 1 && p > a) {                        // the k - 1 <= 30 bytes in front of the piece, from `a` on: one or two pieces
-                    for (int64_t f = k - 1 <= 16 ? p - 16 : p - 32; f < p; f += 16) {
-                        if (f < 0 || f + 16 <= a) continue;
-                        const uint4 pv = qc_load16(data, so + f, n_bytes);
-                        const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-                        for (int i = 0; i < 16; ++i)
-                            if (f + i >= a) st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
-                    }
-                }
-                const uint4 cv = qc_load16(data, so + p, n_bytes);
-                const uint32_t w[4] = {cv.x, cv.y, cv.z, cv.w};
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    if (p + i < a || p + i >= b) continue;
-                    st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
-                    if (st.v >= k) {
-                        ++nw;
-                        nh += LDS ? ks_probe(ks_lds, S.log2, st.value()) : ks_probe(S.slots, S.log2, st.value());
-                    }
-                }
-            }
+            kmer_fq_pieces<uint64_t, CANON>(data, so, n_bytes, a, b, sub, lpr, k, [&](uint64_t code) {
+                ++nw;
+                nh += LDS ? ks_probe(ks_lds, S.log2, code) : ks_probe(S.slots, S.log2, code);
+            });
         }
         nw = qc_group_reduce(nw, lane, sub, lpr, p2, [](uint32_t x, uint32_t y) { return x + y; });
         nh = qc_group_reduce(nh, lane, sub, lpr, p2, [](uint32_t x, uint32_t y) { return x + y; });
@@ -171,7 +147,7 @@ __global__ __launch_bounds__(BLOCK) void k_ks_fasta(SearchPlan P, int k, const i
         const int64_t limit = P.slen[r] - (K[g] - K[P.run0[slot]]);          // windows may end at the kept bytes of the run below it
         if (limit <= 0) continue;
         unsigned long long nw = 0, nh = 0;
-        kt_walk<CANON>(P, k, b, lo, hi, limit, [&](uint64_t code) {
+        kmer_walk<uint64_t, CANON>(P, k, b, lo, hi, 0, limit, [&](uint64_t code) {
             ++nw;
             nh += LDS ? ks_probe(ks_lds, S.log2, code) : ks_probe(S.slots, S.log2, code);
         });

@@ -2,17 +2,19 @@
 // Extension: the definition is the one of fx_kmer.hpp / include/fxgpu.h; where the dense form keeps 4^k counters, this one
 // returns the codes that occur, ascending, each with its exact count.  DESIGN.md 4.6.
 //
-// Codes.  2k <= 62 bits: KmerRoll64 is KmerRoll with 64-bit words (forward code masked to 2k bits, the complement shifted in
+// Codes.  2k <= 62 bits: KmerRoll of fx_kmer.hpp with 64-bit words (forward code masked to 2k bits, the complement shifted in
 // at bit 2(k - 1) <= 60).  The dense kernels keep their 32-bit registers.
 //
 // Walks.  The stream is walked once for a histogram and once per partition for the codes:
 //   k_kt_kept   one lane per run: its kept bytes (the form SrchLdKept reads).  Their scan K gives every run the kept index
 //               it starts at, so that no walk produces a window that ends at or behind slen -- a sorted list cannot take a
 //               window off again with an add of -1 as k_kmer_fix does.
-//   k_kt_fasta  one lane per run as k_kmer_fasta.  The warm-up over the k - 1 <= 30 kept bytes in front of a run comes from
-//               one (k - 1 <= 12) or two aligned 16-byte loads; where they hold fewer than k - 1 kept bytes or reach in
-//               front of the record the lane goes back byte by byte.
-//   k_kt_fastq  the lane groups of k_kmer_fastq; the warm-up reads the one or two 16-byte pieces in front.
+//   k_kt_fasta  one lane per run as k_kmer_fasta: kmer_walk of fx_kmer.hpp with 64-bit words and an upper bound on the kept
+//               index.  The warm-up over the k - 1 <= 30 kept bytes in front of a run comes from one (k - 1 <= 12) or two
+//               aligned 16-byte loads; where they hold fewer than k - 1 kept bytes or reach in front of the record the lane
+//               goes back byte by byte.
+//   k_kt_fastq  the lane groups of k_kmer_fastq and its pieces (kmer_fq_pieces); the warm-up reads the k - 1 bytes in front of a
+//               piece from the one or two 16-byte pieces there.
 //   EMIT = false: the top min(2k, 12) bits of every counted code go to a 16 KiB table of 32-bit counters in LDS (a lane adds a
 //               bin when the next window falls into another one), the table to 4096 int64 bins when the workgroup is done.
 //   EMIT = true:  codes in [lo, hi) are stored at a cursor in global memory: the lanes of a wave that have one ballot, the
@@ -33,19 +35,6 @@ constexpr int KT_MAX_K = 31;
 constexpr int KT_BIN_BITS = 12;                             // the partitions are ranges of the top min(2k, 12) bits of a code
 constexpr int KT_BINS = 1 << KT_BIN_BITS;
 static_assert(KT_BINS == KMER_LDS_WORDS, "the histogram uses the LDS table of the dense form");
-
-template <bool CANON>
-struct KmerRoll64 {
-    uint64_t fw = 0, rc = 0;
-    int v = 0;                                               // valid bases in a row, capped at k
-    __device__ __forceinline__ void step(uint32_t code, int k, uint64_t mask, int sh) {
-        if (code > 3u) { v = 0; return; }
-        fw = ((fw << 2) | code) & mask;
-        if (CANON) rc = (rc >> 2) | ((uint64_t)(3u - code) << sh);
-        v = v < k ? v + 1 : k;
-    }
-    __device__ __forceinline__ uint64_t value() const { return CANON ? (fw < rc ? fw : rc) : fw; }
-};
 
 // where the windows of a walk go
 struct KtArgs {
@@ -96,64 +85,8 @@ __device__ __forceinline__ void kt_lds_flush(uint32_t *lds, unsigned long long *
     }
 }
 
-// kmer_walk with 64-bit codes: raw bytes [lo, hi) of the address space of a record that begins at b.  Every valid window that
-// ends at a kept byte whose local index (0 at lo) is below `limit` goes to on_win(code).
-template <bool CANON, class F>
-__device__ __forceinline__ void kt_walk(const SearchPlan &P, int k, int64_t b, int64_t lo, int64_t hi, int64_t limit, F &&on_win) {
-    const uint64_t mask = (1ull << (2 * k)) - 1ull;
-    const int sh = 2 * (k - 1);
-    KmerRoll64<CANON> st;
-    if (k > 1 && lo > b) {                                   // warm-up on the k - 1 kept bytes in front of the run
-        int kept = 0;
-        const int64_t reach = k - 1 <= 12 ? 16 : 32;
-        if ((lo & 15) == 0 && lo - reach >= b) {
-            for (int64_t q = lo - reach; q < lo; q += 16) {
-                const uint4 pv = *reinterpret_cast<const uint4 *>(P.base + q);
-                const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const uint32_t c = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-                    if (!srch_space(c)) { st.step(kmer_code(c), k, mask, sh); ++kept; }
-                }
-            }
-        }
-        if (kept < k - 1) {                                  // white space hides them, or the record begins inside the reach
-            st = KmerRoll64<CANON>();
-            int64_t ws = lo;
-            for (int need = k - 1; need > 0 && ws > b;) {
-                --ws;
-                need -= srch_space(P.base[ws]) ? 0 : 1;
-            }
-            for (int64_t p = ws; p < lo; ++p) {
-                const uint32_t c = P.base[p];
-                if (!srch_space(c)) st.step(kmer_code(c), k, mask, sh);
-            }
-        }
-    }
-    int64_t kidx = 0;
-    auto feed = [&](uint32_t c, bool live) {
-        if (!live || srch_space(c)) return;
-        st.step(kmer_code(c), k, mask, sh);
-        if (st.v >= k && kidx < limit) on_win(st.value());
-        ++kidx;
-    };
-    int64_t c = lo & ~(int64_t)15;
-    uint4 v = *reinterpret_cast<const uint4 *>(P.base + c);
-    for (; c < hi; c += 16) {
-        const uint4 cur = v;
-        if (c + 16 < hi) v = *reinterpret_cast<const uint4 *>(P.base + c + 16);     // the next chunk in flight while this one is walked
-        const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
-        if (c >= lo && c + 16 <= hi) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, true);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, c + i >= lo && c + i < hi);
-        }
-    }
-}
-
-// packed[g] = the kept bytes of run g, as srch_pack lays them
+// packed[g] = the kept bytes of run g, as srch_pack lays them.  A loop of its own, not run_walk: a count does not depend on the
+// order of the bytes, so every load of the run may be in flight at once (measured at half the time of the one-ahead walk).
 __global__ __launch_bounds__(BLOCK) void k_kt_kept(SearchPlan P, uint32_t *__restrict__ packed) {
     const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (g >= P.n_runs) return;
@@ -183,13 +116,13 @@ __global__ __launch_bounds__(BLOCK) void k_kt_fasta(SearchPlan P, int k, int64_t
         if (limit <= 0) continue;
         KtSink<EMIT> sink{};
         if constexpr (EMIT) sink.a = A; else { sink.lds = lds; sink.shift = A.shift; }
-        kt_walk<CANON>(P, k, b, lo, hi, limit, [&](uint64_t code) { sink.put(code); });
+        kmer_walk<uint64_t, CANON>(P, k, b, lo, hi, 0, limit, [&](uint64_t code) { sink.put(code); });
         sink.flush();
     }
     if (!EMIT) { __syncthreads(); kt_lds_flush(lds, A.bins); }
 }
 
-// Queries [q_begin, q_end); start / end null: whole reads.  The lanes and pieces of k_kmer_fastq.
+// Queries [q_begin, q_end); start / end null: whole reads.  The lanes and pieces of k_kmer_fastq, 64-bit words.
 template <bool CANON, bool EMIT>
 __global__ __launch_bounds__(BLOCK) void k_kt_fastq(const uint8_t *__restrict__ data, int64_t gbase, int64_t n_bytes,
                                                    const int64_t *__restrict__ rlen, const int64_t *__restrict__ soff,
@@ -197,8 +130,6 @@ __global__ __launch_bounds__(BLOCK) void k_kt_fastq(const uint8_t *__restrict__ 
                                                    const int64_t *__restrict__ start, const int64_t *__restrict__ end, int lpr, int k, KtArgs A) {
     __shared__ uint32_t lds[EMIT ? 1 : KT_BINS];
     const int lane = lane_id(), grp = lane / lpr, sub = lane - grp * lpr, ngrp = 64 / lpr;
-    const int sh = 2 * (k - 1);
-    const uint64_t mask = (1ull << (2 * k)) - 1ull;
     if (!EMIT) { kmer_lds_clear(lds); __syncthreads(); }
     KtSink<EMIT> sink{};
     if constexpr (EMIT) sink.a = A; else { sink.lds = lds; sink.shift = A.shift; }
@@ -208,29 +139,7 @@ __global__ __launch_bounds__(BLOCK) void k_kt_fastq(const uint8_t *__restrict__ 
         const int64_t id = ids ? ids[q] : q;
         const int64_t L = rlen[id] > 0 ? rlen[id] : 0, so = soff[id] - gbase;
         const int64_t a = start ? start[q] : 0, b = end ? end[q] : L;
-        // the pieces of this lane: bytes [p, p + 16) of the read; the windows that end there end in [a + k - 1, b)
-        for (int64_t p = (int64_t)sub * 16; p < b; p += (int64_t)lpr * 16) {
-            if (p + 16 <= a + k - 1) continue;
-            KmerRoll64<CANON> st;
-            if (k > 1 && p > a) {                            // the k - 1 <= 30 bytes in front of the piece, from `a` on: one or two pieces
-                for (int64_t f = k - 1 <= 16 ? p - 16 : p - 32; f < p; f += 16) {
-                    if (f < 0 || f + 16 <= a) continue;
-                    const uint4 pv = qc_load16(data, so + f, n_bytes);
-                    const uint32_t w[4] = {pv.x, pv.y, pv.z, pv.w};
-#pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        if (f + i >= a) st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
-                }
-            }
-            const uint4 cv = qc_load16(data, so + p, n_bytes);
-            const uint32_t w[4] = {cv.x, cv.y, cv.z, cv.w};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                if (p + i < a || p + i >= b) continue;
-                st.step(kmer_code((w[i >> 2] >> (8 * (i & 3))) & 0xFFu), k, mask, sh);
-                if (st.v >= k) sink.put(st.value());
-            }
-        }
+        kmer_fq_pieces<uint64_t, CANON>(data, so, n_bytes, a, b, sub, lpr, k, [&](uint64_t code) { sink.put(code); });
     }
     sink.flush();
     if (!EMIT) { __syncthreads(); kt_lds_flush(lds, A.bins); }

@@ -56,7 +56,7 @@ __device__ __forceinline__ unsigned long long pwm_key(int32_t score, int64_t sta
     return ((unsigned long long)(score + PWM_BIAS) << PWM_START_BITS) | (unsigned long long)((((int64_t)1 << PWM_START_BITS) - 1) - start);
 }
 
-// srch_walk with the history: every scorable window that ends at a kept byte whose local index (0 at lo) is below `limit`
+// srch_walk (run_warm and run_walk of fx_search.hpp) with the history: every scorable window that ends at a kept byte whose local index (0 at lo) is below `limit`
 // goes to on_win(kidx, score on +, score on -).  G = 0: nothing is scored, the kept bytes are counted.  -> kept bytes in [lo, hi).
 template <int G, class F>
 __device__ __forceinline__ uint32_t pwm_walk(const SearchPlan &P, const int2 *tab, int64_t b, int64_t lo, int64_t hi, int64_t limit,
@@ -73,19 +73,9 @@ __device__ __forceinline__ uint32_t pwm_walk(const SearchPlan &P, const int2 *ta
         h0 = (h0 << 2) | (q ^ (q >> 1));
         cnt = ok ? min(cnt + 1, 64) : 0;
     };
-    // warm-up: back over the W - 1 kept bytes in front of the run (at most to the record's first byte), then forward
-    int64_t ws = lo;
-    for (int need = W - 1; need > 0 && ws > b;) {
-        --ws;
-        need -= srch_space(P.base[ws]) ? 0 : 1;
-    }
-    for (int64_t p = ws; p < lo; ++p) {
-        const uint32_t c = P.base[p];
-        if (!srch_space(c)) step(c);
-    }
+    run_warm(P, b, lo, W - 1, step);
     int64_t kidx = 0;
-    auto feed = [&](uint32_t c, bool live) {
-        if (!live || srch_space(c)) return;
+    run_walk(P, lo, hi, [&](uint32_t c) {
         step(c);
         if (G > 0 && cnt >= W && kidx < limit) {
             int32_t sf = 0, sr = 0;
@@ -101,21 +91,7 @@ __device__ __forceinline__ uint32_t pwm_walk(const SearchPlan &P, const int2 *ta
             on_win(kidx, sf, sr);
         }
         ++kidx;
-    };
-    int64_t c = lo & ~(int64_t)15;
-    uint4 v = *reinterpret_cast<const uint4 *>(P.base + c);
-    for (; c < hi; c += 16) {
-        const uint4 cur = v;
-        if (c + 16 < hi) v = *reinterpret_cast<const uint4 *>(P.base + c + 16);     // the next chunk in flight while this one is walked
-        const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
-        if (c >= lo && c + 16 <= hi) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, true);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, c + i >= lo && c + i < hi);
-        }
-    }
+    });
     return (uint32_t)kidx;
 }
 

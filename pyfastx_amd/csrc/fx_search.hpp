@@ -58,24 +58,13 @@ __device__ __forceinline__ void srch_load_tab(const SearchPlan &P, ulonglong2 *t
     }
 }
 
-// Walk one run: raw bytes [lo, hi) of the address space, after a warm-up from the record start b.  Kept bytes whose local
-// index (0 at lo) is below `limit` may end a hit; hits go to on_hit(kidx, fwd, rev).  -> kept bytes in [lo, hi).
-template <bool WIDE, class F>
-__device__ __forceinline__ uint32_t srch_walk(const SearchPlan &P, const ulonglong2 *tab, int64_t b, int64_t lo, int64_t hi,
-                                              int64_t limit, F &&on_hit) {
-    const int L = P.plen;
-    uint64_t Df = 0, Dr = 0;
-    auto step = [&](uint32_t c) {
-        if (WIDE) {
-            Df = ((Df << 1) | 1ull) & tab[c].x;
-            Dr = ((Dr << 1) | 1ull) & tab[c].y;
-        } else {
-            Df = ((Df << 1) | 0x100000001ull) & tab[c].x;
-        }
-    };
-    // warm-up: back over the L - 1 kept bytes in front of the run (at most to the record's first byte), then forward
+// ------------------------------------------------------------------ the skeleton of every walk over the windows of a run
+// Warm-up: back from lo over `need` kept bytes (at most to the record's first byte b), then every kept byte from there to lo,
+// in order, to step(c).
+template <class S>
+__device__ __forceinline__ void run_warm(const SearchPlan &P, int64_t b, int64_t lo, int need, S &&step) {
     int64_t ws = lo;
-    for (int need = L - 1; need > 0 && ws > b;) {
+    while (need > 0 && ws > b) {
         --ws;
         need -= srch_space(P.base[ws]) ? 0 : 1;
     }
@@ -83,14 +72,14 @@ __device__ __forceinline__ uint32_t srch_walk(const SearchPlan &P, const ulonglo
         const uint32_t c = P.base[p];
         if (!srch_space(c)) step(c);
     }
-    const int shf = L - 1, shr = WIDE ? L - 1 : 31 + L;
-    int64_t kidx = 0;
-    auto feed = [&](uint32_t c, bool live) {
-        if (!live || srch_space(c)) return;
-        step(c);
-        const uint32_t f = (uint32_t)(Df >> shf) & 1u, r = (uint32_t)((WIDE ? Dr : Df) >> shr) & 1u;
-        if ((f | r) && kidx < limit) on_hit(kidx, f, r);
-        ++kidx;
+}
+
+// Every kept byte of the raw bytes [lo, hi), in order, to f(c): aligned 16-byte chunks, the first and the last one masked.
+template <class F>
+__device__ __forceinline__ void run_walk(const SearchPlan &P, int64_t lo, int64_t hi, F &&f) {
+    auto feed = [&](uint32_t x, bool live) {
+        if (!live || srch_space(x)) return;
+        f(x);
     };
     int64_t c = lo & ~(int64_t)15;
     uint4 v = *reinterpret_cast<const uint4 *>(P.base + c);
@@ -106,6 +95,32 @@ __device__ __forceinline__ uint32_t srch_walk(const SearchPlan &P, const ulonglo
             for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, c + i >= lo && c + i < hi);
         }
     }
+}
+
+// Walk one run: raw bytes [lo, hi) of the address space, after a warm-up on the L - 1 kept bytes in front of it.  Kept bytes
+// whose local index (0 at lo) is below `limit` may end a hit; hits go to on_hit(kidx, fwd, rev).  -> kept bytes in [lo, hi).
+template <bool WIDE, class F>
+__device__ __forceinline__ uint32_t srch_walk(const SearchPlan &P, const ulonglong2 *tab, int64_t b, int64_t lo, int64_t hi,
+                                              int64_t limit, F &&on_hit) {
+    const int L = P.plen;
+    uint64_t Df = 0, Dr = 0;
+    auto step = [&](uint32_t c) {
+        if (WIDE) {
+            Df = ((Df << 1) | 1ull) & tab[c].x;
+            Dr = ((Dr << 1) | 1ull) & tab[c].y;
+        } else {
+            Df = ((Df << 1) | 0x100000001ull) & tab[c].x;
+        }
+    };
+    run_warm(P, b, lo, L - 1, step);
+    const int shf = L - 1, shr = WIDE ? L - 1 : 31 + L;
+    int64_t kidx = 0;
+    run_walk(P, lo, hi, [&](uint32_t c) {
+        step(c);
+        const uint32_t f = (uint32_t)(Df >> shf) & 1u, r = (uint32_t)((WIDE ? Dr : Df) >> shr) & 1u;
+        if ((f | r) && kidx < limit) on_hit(kidx, f, r);
+        ++kidx;
+    });
     return (uint32_t)kidx;
 }
 

@@ -50,7 +50,7 @@ __device__ __forceinline__ void asrch_load_tab(const SearchPlan &P, asrch_tab_t<
     }
 }
 
-// srch_walk with the d + 1 levels: hits go to on_hit(kidx, fwd, rev, dist_fwd, dist_rev) (the distances only under DIST,
+// srch_walk (run_warm and run_walk of fx_search.hpp) with the d + 1 levels: hits go to on_hit(kidx, fwd, rev, dist_fwd, dist_rev) (the distances only under DIST,
 // and only that of a strand that hit means anything).  -> kept bytes in [lo, hi).
 template <bool WIDE, int NLEV, bool DIST, class F>
 __device__ __forceinline__ uint32_t asrch_walk(const SearchPlan &P, const ApproxArg &A, const asrch_tab_t<WIDE> *tab, int64_t b, int64_t lo,
@@ -82,20 +82,10 @@ __device__ __forceinline__ uint32_t asrch_walk(const SearchPlan &P, const Approx
             Rf[0] = ((Rf[0] << 1) | 0x100000001ull) & m;
         }
     };
-    // warm-up: back over the L - 1 kept bytes in front of the run (at most to the record's first byte), then forward
-    int64_t ws = lo;
-    for (int need = L - 1; need > 0 && ws > b;) {
-        --ws;
-        need -= srch_space(P.base[ws]) ? 0 : 1;
-    }
-    for (int64_t p = ws; p < lo; ++p) {
-        const uint32_t c = P.base[p];
-        if (!srch_space(c)) step(c);
-    }
+    run_warm(P, b, lo, L - 1, step);
     const int shf = L - 1, shr = WIDE ? L - 1 : 31 + L;
     int64_t kidx = 0;
-    auto feed = [&](uint32_t c, bool live) {
-        if (!live || srch_space(c)) return;
+    run_walk(P, lo, hi, [&](uint32_t c) {
         step(c);
         const uint32_t f = (uint32_t)(Rf[NLEV - 1] >> shf) & 1u, r = (uint32_t)((WIDE ? Rr[NLEV - 1] : Rf[NLEV - 1]) >> shr) & 1u;
         if ((f | r) && kidx < limit) {
@@ -111,21 +101,7 @@ __device__ __forceinline__ uint32_t asrch_walk(const SearchPlan &P, const Approx
             on_hit(kidx, f, r, df, dr);
         }
         ++kidx;
-    };
-    int64_t c = lo & ~(int64_t)15;
-    uint4 v = *reinterpret_cast<const uint4 *>(P.base + c);
-    for (; c < hi; c += 16) {
-        const uint4 cur = v;
-        if (c + 16 < hi) v = *reinterpret_cast<const uint4 *>(P.base + c + 16);     // the next chunk in flight while this one is walked
-        const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
-        if (c >= lo && c + 16 <= hi) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, true);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, c + i >= lo && c + i < hi);
-        }
-    }
+    });
     return (uint32_t)kidx;
 }
 
