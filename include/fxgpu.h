@@ -381,6 +381,40 @@ int fx_fasta_pwm_scan(fx_handle *h, const int32_t *mat, int32_t plen, int mode, 
 int fx_fasta_pwm_best(fx_handle *h, const int32_t *mat, int32_t plen, int mode, const int64_t *ids, int64_t n_ids, int32_t *best_score,
                       int64_t *best_start);
 
+/* ------------------------------------------------------------------ minimizers
+ * Extension (the reference has no counterpart: it has no k-mer of any kind).  The (w, k) minimizers of the `seq` of the
+ * records: of every w consecutive k-mers the smallest, each distinct choice once -- the sampling step in front of seeding,
+ * overlap and containment indexes, k-mer bucketing and sketching (pyfastx_amd/csrc/fx_minimizer.hpp: the 64-bit rolling code
+ * of the k-mer tables, a ring of the last w keys per lane in LDS, the passes of fx_fasta_search).
+ *   Sequence     the text fx_fasta_search walks, with its rules: bytes 10/13/32 dropped, windows across line ends and never
+ *                across records, cut at slen.  No upper-casing plays a part.
+ *   k-mers       1 <= k <= 31.  Position p (0 <= p <= slen - k) holds the k-mer seq[p .. p + k).  It is VALID when all its
+ *                letters are ACGTacgt (U, N, IUPAC codes and every other byte are not).  fw: its base-4 code, A = 0 C = 1 G = 2
+ *                T = 3, first letter most significant; rc: the code of its reverse complement.  With FX_MZ_CANONICAL
+ *                code = min(fw, rc) and the strand is '+' when fw <= rc (a k-mer that is its own reverse complement is '+'),
+ *                '-' otherwise; without it code = fw and the strand is '+'.
+ *   Order        FX_MZ_LEX: key = code.  Otherwise key = mix(code), with m = 4^k - 1 and unsigned 64-bit arithmetic:
+ *                    x = (~x + (x << 21)) & m;  x ^= x >> 24
+ *                    x = (x + (x << 3) + (x << 8)) & m;  x ^= x >> 14
+ *                    x = (x + (x << 2) + (x << 4)) & m;  x ^= x >> 28
+ *                    x = (x + (x << 31)) & m
+ *                a bijection of the 2k-bit words for every k, so equal keys mean equal codes.
+ *   Windows      1 <= w <= 32.  Window j (0 <= j <= slen - k - w + 1) holds the positions j .. j + w - 1.  Its SELECTION is
+ *                the leftmost position with the smallest key among its valid k-mers; a window without a valid k-mer has none.
+ *                A record shorter than w + k - 1 letters has no window and gives no row.
+ *   Rows         the distinct selections of all windows of a record, each as (record, start = position, strand, code), by
+ *                (record, start).  Selections never move left as j grows, so the rows are exactly the windows whose selection
+ *                exists and differs from that of window j - 1.
+ *   ids, n_ids, cap, rec, start, strand, n_hits, counts: as for fx_fasta_search (counts: rows per searched record on '+' and
+ *                on '-'; cap = 0 with counts != NULL: counts only); code: a fourth pinned block beside rec / start / strand, the
+ *                uint64 code of every row (stop = start + k).
+ * FX_EINVAL: k outside 1..31, w outside 1..32, a flag bit other than the two (these are refused before the handle is looked
+ * at), a null output, a byte-range shard (no halo).  FX_ESTATE: no table built.  FX_ERANGE: more than cap rows, *n_hits =
+ * their number, nothing allocated. */
+enum { FX_MZ_CANONICAL = 1, FX_MZ_LEX = 2 };
+int fx_fasta_minimizers(fx_handle *h, int32_t k, int32_t w, int flags, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec,
+                        int64_t **start, uint8_t **strand, uint64_t **code, int64_t *n_hits, int64_t *counts);
+
 /* ------------------------------------------------------------------ regions, windows, class runs
  * Composition of intervals of the records, and the maximal runs of a letter class (pyfastx_amd/csrc/fx_annot.hpp).  The text
  * of a record is the one fx_fasta_search walks: the bytes of [boff, boff + blen) with 10 / 13 / 32 dropped, cut at slen; the

@@ -14,6 +14,7 @@ FX_HOST, FX_DEVICE = 0, 1
 FX_UPPER, FX_REVERSE, FX_COMPLEMENT, FX_RAW = 1, 2, 4, 8
 FX_SEARCH_DEGENERATE, FX_SEARCH_UPPER, FX_SEARCH_PLUS, FX_SEARCH_MINUS = 1, 2, 4, 8
 FX_KMER_CANONICAL = 1
+FX_MZ_CANONICAL, FX_MZ_LEX = 1, 2
 FX_DUP_REVCOMP = 1
 FX_OK, FX_ENOENT, FX_EFORMAT, FX_EIO, FX_EDEVICE, FX_ENOMEM, FX_ERANGE, FX_EINVAL, FX_ESTATE = \
     0, -1, -2, -3, -4, -5, -6, -7, -8
@@ -51,7 +52,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_pwm_scan", "fx_fasta_pwm_best", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_demux", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_pwm_scan", "fx_fasta_pwm_best", "fx_fasta_minimizers", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_demux", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -230,6 +231,8 @@ def lib():
     L.fx_fasta_pwm_scan.argtypes = [vp, vp, i32, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                     C.POINTER(i64), vp]
     L.fx_fasta_pwm_best.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp]
+    L.fx_fasta_minimizers.argtypes = [vp, i32, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                      C.POINTER(i64), vp]
     L.fx_fasta_rank_build.argtypes = [vp]
     L.fx_fasta_rank_free.argtypes = [vp]
     L.fx_fasta_region_counts.argtypes = [vp, i32, i64, vp, vp, vp, vp, C.POINTER(i64)]
@@ -1141,6 +1144,20 @@ class Blob:
         check(lib().fx_fasta_pwm_best(self._h, _ptr(mat), mat.shape[0], int(mode), _ptr(ids), 0 if ids is None else ids.size,
                                       _ptr(scores), _ptr(starts)))
         return scores, starts
+
+    def fasta_minimizers(self, k, w, flags, ids=None, cap=0, counts=False):
+        """The (w, k) minimizers of the selected records (fx_fasta_minimizers; flags: FX_MZ_CANONICAL | FX_MZ_LEX) -> (n_hits,
+        (rec, start, strand, code) pinned arrays or None, counts int64[n_sel, 2] or None); more than `cap` rows raise
+        FxError(FX_ERANGE) whose .n_hits is the true count.  cap = 0 with counts: counts only."""
+        ids = None if ids is None else self._i64(ids)
+        cnt = np.zeros((self._n_selected(ids), 2), dtype=np.int64) if counts else None
+        rec, st, sd, cd, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        rc = lib().fx_fasta_minimizers(self._h, int(k), int(w), int(flags), _ptr(ids), 0 if ids is None else ids.size, int(cap), C.byref(rec),
+                                       C.byref(st), C.byref(sd), C.byref(cd), C.byref(n), _ptr(cnt))
+        if rc:
+            _raise(rc, n_hits=int(n.value))
+        rows = _pinned_columns((rec, st, sd, cd), (np.int64, np.int64, np.uint8, np.uint64), int(n.value)) if rec.value else None
+        return int(n.value), rows, cnt
 
     def fasta_rank_build(self):
         """The rank index of the resident table (fx_fasta_rank_build); a second call does nothing."""

@@ -893,6 +893,30 @@ class Fasta(_fxobj.FastaCore):
         sel = None if ids is None else self._ids_of(ids)
         return _pwm.best_blob(self._search_blob(), pwm, strand, sel)
 
+    def minimizers(self, k, w, canonical=True, order="hash", ids=None, max_hits=10**8):
+        """Extension: the (w, k) minimizers of every record's `seq` -- of every w consecutive k-mers the smallest, each
+        distinct choice once.  1 <= k <= 31, 1 <= w <= 32.  Position p holds the k-mer seq[p:p+k], valid when all its letters
+        are ACGTacgt (uppercase= plays no part; U, N, IUPAC codes and everything else are not); windows run across line ends,
+        never across records.  fw: its base-4 code (A=0 C=1 G=2 T=3, first letter most significant), rc: that of its reverse
+        complement.  canonical=True: code = min(fw, rc), strand '+' when fw <= rc (a k-mer that is its own reverse
+        complement is '+'), else '-'; canonical=False: code = fw, strand '+'.  order="lex": key = code; order="hash":
+        key = minimizer.mix(code, k), a bijection of the 2k-bit words.  Window j holds the positions j .. j+w-1; its selection
+        is the leftmost position with the smallest key among its valid k-mers (none: no selection).  A record shorter than
+        w + k - 1 letters has no window.  -> Minimizers(ids, starts, stops, strands, codes): the distinct selections, by
+        (record, start); int64, int64, int64 (starts + k), uint8, uint64, in pinned memory.  ids, max_hits: as for
+        search_all.  On the GPU from the resident stream (csrc/fx_minimizer.hpp)."""
+        from . import minimizer
+        minimizer.check_args(k, w, order)
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        return minimizer.minimizers_blob(self._search_blob(), k, w, canonical, order, sel, max_hits)
+
+    def minimizer_counts(self, k, w, canonical=True, order="hash"):
+        """Extension: rows of minimizers per record -> int64[len(fa), 2] (column 0 '+', column 1 '-'); the rows themselves
+        are never materialised."""
+        from . import minimizer
+        minimizer.check_args(k, w, order)
+        return minimizer.count_blob(self._search_blob(), k, w, canonical, order)
+
     def kmer_counts(self, k, canonical=False, ids=None):
         """Extension: the k-mer spectrum of the `seq` of every record -> int64[4**k] in pinned memory, counted on the GPU
         from the resident stream (csrc/fx_kmer.hpp).  Letters A C G T in either case (A = 0, C = 1, G = 2, T = 3; uppercase=

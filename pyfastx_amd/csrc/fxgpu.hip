@@ -53,6 +53,7 @@
 #include "fx_fastq_demux.hpp"
 #include "fx_fastq_pair.hpp"
 #include "fx_kmer.hpp"
+#include "fx_minimizer.hpp"
 #include "fx_kmer_table.hpp"
 #include "fx_kmer_screen.hpp"
 #include "fx_fastq_dedup.hpp"
@@ -332,10 +333,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit"};
 
 struct Prof {
     bool on = false;
@@ -4152,6 +4153,62 @@ extern "C" int fx_fasta_pwm_best(fx_handle *h, const int32_t *mat, int32_t plen,
     if (rc) return rc;
     if (!best_score || !best_start) return fail(FX_EINVAL, "null output");
     return fasta_pwm(h, mat, plen, mode, 0, ids, n_ids, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, best_score, best_start);
+}
+
+// ------------------------------------------------------------------ minimizers (fx_minimizer.hpp)
+// What the numbers alone decide is refused first, before the handle is looked at; then run_hits with the three kernels of the
+// form, each with the lanes' key rings in dynamic LDS (BLOCK * w * 8 bytes).
+extern "C" int fx_fasta_minimizers(fx_handle *h, int32_t k, int32_t w, int flags, const int64_t *ids, int64_t n_ids, int64_t cap,
+                                   int64_t **rec, int64_t **start, uint8_t **strand, uint64_t **code, int64_t *n_hits, int64_t *counts) {
+    if (n_hits) *n_hits = 0;
+    if (rec) *rec = nullptr; if (start) *start = nullptr; if (strand) *strand = nullptr; if (code) *code = nullptr;
+    if (k < 1 || k > MZ_MAX_K) return fail(FX_EINVAL, "k = %d outside 1..%d", (int)k, MZ_MAX_K);
+    if (w < 1 || w > MZ_MAX_W) return fail(FX_EINVAL, "w = %d outside 1..%d", (int)w, MZ_MAX_W);
+    if (flags & ~(FX_MZ_CANONICAL | FX_MZ_LEX)) return fail(FX_EINVAL, "unknown flag bits %d", flags);
+    if (!h || !n_hits) return fail(FX_EINVAL, "null argument");
+    const bool counts_only = cap == 0 && counts;
+    if (cap < 0 || (!counts_only && (!rec || !start || !strand || !code))) return fail(FX_EINVAL, "null output");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
+    int rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (rc) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    if (n_sel == 0) return FX_OK;
+    const size_t lds = (size_t)BLOCK * w * sizeof(uint64_t);
+    // the kernels of this call: f(CANON, LEX)
+    auto with_form = [&](auto &&f) { with_bool(flags & FX_MZ_CANONICAL, [&](auto C) { with_bool(flags & FX_MZ_LEX, [&](auto L) { f(C, L); }); }); };
+    with_form([&](auto C, auto L) {                          // 64 KiB at w = 32: the most a launch takes without asking
+        constexpr bool c = decltype(C)::value, l = decltype(L)::value;
+        (void)hipFuncSetAttribute((const void *)k_mz_count<c, l>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
+        (void)hipFuncSetAttribute((const void *)k_mz_fix<c, l>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
+        (void)hipFuncSetAttribute((const void *)k_mz_emit<c, l>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
+    });
+    Staged st(h);
+    return run_hits(
+        h, st, nullptr, k, ids, n_ids, cap, counts, 8, "minimizer emit",
+        [&](HitRuns &R) {
+            with_form([&](auto C, auto L) {
+                FX_LAUNCH_LDS(h, K_MZ_COUNT, (k_mz_count<decltype(C)::value, decltype(L)::value>), dim3(R.grid_runs), dim3(BLOCK), lds, R.P, (int)k, (int)w,
+                              R.packed.p);
+            });
+        },
+        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
+            with_form([&](auto C, auto L) {
+                FX_LAUNCH_LDS(h, K_SEARCH_SCAN, (k_mz_fix<decltype(C)::value, decltype(L)::value>), dim3(grid_sel), dim3(BLOCK), lds, R.P, (int)k, (int)w, K,
+                              R.packed.p);
+            });
+        },
+        [&](HitRuns &R, const int64_t *list, int64_t n_list, const int64_t *K, const int64_t *Pp, const int64_t *Pm, int64_t *o_rec, int64_t *o_start,
+            uint8_t *o_strand, void *o_code) {
+            with_form([&](auto C, auto L) {
+                FX_LAUNCH_LDS(h, K_MZ_EMIT, (k_mz_emit<decltype(C)::value, decltype(L)::value>), dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), lds, R.P, (int)k,
+                              (int)w, list, n_list, K, Pp, Pm, o_rec, o_start, o_strand, (uint64_t *)o_code);
+            });
+        },
+        rec, start, strand, (void **)code, n_hits);
 }
 
 // ------------------------------------------------------------------ regions, windows, class runs (fx_annot.hpp)
