@@ -801,6 +801,68 @@ int fx_fastq_kmer_screen(fx_handle *h, const fx_kmer_set *set, const int64_t *id
 int fx_fasta_kmer_hits(fx_handle *h, const fx_kmer_set *set, const int64_t *ids, int64_t n_ids,
                        int64_t **n_windows, int64_t **n_hits, int64_t *n_rows, int64_t *first_bad);
 
+/* ------------------------------------------------------------------ sketches (extension)
+ * MinHash and FracMinHash sketches of records and read sets, and their comparison on the device
+ * (pyfastx_amd/csrc/fx_sketch.hpp): what Mash and sourmash answer -- how similar are these contigs, assemblies or read sets,
+ * which reference is contained in this sample, what is the approximate ANI.  The reference has no counterpart.
+ * Windows.  The alphabet, code, canonical form, windows and the cut at slen are those of fx_fasta_kmer_table and
+ *   fx_fastq_kmer_table, word for word: 1 <= k <= 31; valid letters are ACGTacgt (U, N, IUPAC codes and every other byte are
+ *   not); A = 0 C = 1 G = 2 T = 3, the first letter most significant; windows run across line ends, never across records, and
+ *   never past slen; FASTQ windows are those of s[start:end] of the selected reads.
+ * Key.  key = mix(code) with m = 4^k - 1: exactly the hash of fx_fasta_minimizers, a bijection of the 2k-bit words.  With
+ *   FX_SK_CANONICAL code = min(fw, rc), otherwise code = fw.  Keys are uint64, below 2^62.
+ * Sets.  FASTA: one set per selected record, in ascending record order (ids, n_ids as for fx_fasta_minimizers: ids = NULL
+ *   means every record; the caller passes distinct ascending ids).  FASTA with FX_SK_POOLED: one set for all selected records
+ *   together, such as a multi-contig assembly.  FASTQ: always one pooled set of the selected reads; ids, start, end as for
+ *   fx_fastq_kmer_table.  No selected record or read: no set (one empty set when pooled).
+ * What a set keeps.  max_key (1 .. 4^k) and size (>= 0) decide.  The FracMinHash part of a set is the set of distinct keys of
+ *   its valid windows with key < max_key.  With size > 0 the set is the `size` smallest of those, or all of them when there
+ *   are fewer; size = 0 puts no cap on the count.  max_key = 4^k with size = s is the classic bottom-s MinHash.  (In Python
+ *   `scaled`, an integer >= 1, maps to max_key = ceil(4^k / scaled): key * scaled < 4^k without the overflow.)  Every set is
+ *   stored ascending and distinct.
+ * Rounds.  With size > 0 not every window below max_key is emitted: round 0 gives each set a threshold near
+ *   4^k * oversample * size / windows, capped at max_key; a set is final when it holds at least `size` distinct keys below
+ *   its threshold, or when its threshold equals max_key; the other sets get their threshold times 8, saturating, and are
+ *   walked again alone.  *n_rounds = the rounds that ran (0 without a window to walk).  oversample: 1 .. 64, 0 = the default
+ *   of 4; it exists so that tests can reach the retry path.  No result depends on it, only *n_rounds does.
+ * Comparison.  Sets A and B, a limit L >= 0 and a restriction max_key (0: none; otherwise both sets are first cut to their
+ *   keys below it, a prefix of each).  U = the ascending distinct union, U_L = its first min(L, |U|) elements, or all of U
+ *   when L = 0.  total = |U_L| and shared = |{x in U_L : x in A and x in B}|.  From these follow: Jaccard = shared / total;
+ *   containment of A in B = shared / |A| at L = 0; Mash distance = -ln(2j / (1 + j)) / k with j taken at L = the sketch size,
+ *   clipped to [0, 1], and 1 when j = 0; ANI estimate = containment^(1/k).
+ * fx_sketch is opaque and tied to a device, like fx_kmer_set; it needs no handle after its creation.
+ *   fx_fasta_sketch, fx_fastq_sketch   build one from the resident stream.
+ *   fx_sketch_info        the parameters and sizes (any output may be NULL).  flags: as given, FASTQ with FX_SK_POOLED set.
+ *   fx_sketch_read        *off (n_sets + 1 offsets) and *keys (n_keys keys; one item when there is none): pinned blocks of
+ *                         fx_pinned_alloc that belong to the caller (fx_pinned_free each).
+ *   fx_sketch_from_host   a sketch from host arrays; off[0] = 0, off[n_sets] = the number of keys.  The checks run on the
+ *                         device before anything is kept: offsets that do not ascend, keys that are not strictly ascending
+ *                         within a set, a key >= max_key, or a set longer than size (> 0) give FX_EINVAL.
+ *   fx_sketch_compare     all pairs of the selected sets of a (ia, n_a; ia = NULL: all sets, in order) with the selected sets
+ *                         of b: *shared and *total, row-major int64[n_a * n_b], pinned blocks that belong to the caller (one
+ *                         item each without a pair).  Selections may repeat and come in any order.
+ *   fx_sketch_free        NULL: nothing to do.
+ * Errors.  k outside 1..31, unknown flag bits, max_key outside 1..4^k, size < 0, oversample outside 0..64, a null output:
+ * FX_EINVAL, refused before the handle is looked at; then a null handle, start without end: FX_EINVAL; before fx_fasta_build /
+ * fx_fastq_build: FX_ESTATE; a byte-range shard: FX_EINVAL; an id outside the table, or an interval outside 0 <= start <= end
+ * <= rlen (*first_bad = its position among the queries): FX_ERANGE; more than 2^31 - 1 rows of keys below the thresholds in
+ * one round, or rows the scratch pool cannot hold: FX_ERANGE with the count in the message, nothing allocated (a larger scaled
+ * gives fewer); no device: FX_EDEVICE (there is no CPU path).  fx_sketch_compare: different k or canonical form, or different
+ * devices: FX_EINVAL; a selected set outside the sketch, or more than max_pairs pairs: FX_ERANGE. */
+enum { FX_SK_CANONICAL = 1, FX_SK_POOLED = 2 };
+typedef struct fx_sketch fx_sketch;
+int fx_fasta_sketch(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, uint64_t max_key, int64_t size, int32_t oversample,
+                    fx_sketch **sk, int32_t *n_rounds);
+int fx_fastq_sketch(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                    uint64_t max_key, int64_t size, int32_t oversample, fx_sketch **sk, int32_t *n_rounds, int64_t *first_bad);
+int fx_sketch_info(const fx_sketch *sk, int32_t *k, int *flags, uint64_t *max_key, int64_t *size, int64_t *n_sets, int64_t *n_keys);
+int fx_sketch_read(fx_sketch *sk, int64_t **off, uint64_t **keys);
+int fx_sketch_from_host(int device, int32_t k, int flags, uint64_t max_key, int64_t size, int64_t n_sets, const int64_t *off, const uint64_t *keys,
+                        fx_sketch **sk);
+int fx_sketch_compare(fx_sketch *a, fx_sketch *b, const int64_t *ia, int64_t n_a, const int64_t *ib, int64_t n_b, int64_t limit, uint64_t max_key,
+                      int64_t max_pairs, int64_t **shared, int64_t **total);
+int fx_sketch_free(fx_sketch *sk);
+
 /* ------------------------------------------------------------------ duplicate reads (extension)
  * Exact duplicate detection on the resident FASTQ stream (pyfastx_amd/csrc/fx_fastq_dedup.hpp): what FastQC's duplication
  * levels, `seqkit rmdup -s` or `fastp --dedup` answer, without a base leaving the device.  The reference has no counterpart.

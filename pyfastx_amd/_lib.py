@@ -15,6 +15,7 @@ FX_UPPER, FX_REVERSE, FX_COMPLEMENT, FX_RAW = 1, 2, 4, 8
 FX_SEARCH_DEGENERATE, FX_SEARCH_UPPER, FX_SEARCH_PLUS, FX_SEARCH_MINUS = 1, 2, 4, 8
 FX_KMER_CANONICAL = 1
 FX_MZ_CANONICAL, FX_MZ_LEX = 1, 2
+FX_SK_CANONICAL, FX_SK_POOLED = 1, 2
 FX_DUP_REVCOMP = 1
 FX_OK, FX_ENOENT, FX_EFORMAT, FX_EIO, FX_EDEVICE, FX_ENOMEM, FX_ERANGE, FX_EINVAL, FX_ESTATE = \
     0, -1, -2, -3, -4, -5, -6, -7, -8
@@ -52,7 +53,7 @@ SYMBOLS = [
     "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
     "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
     "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_pwm_scan", "fx_fasta_pwm_best", "fx_fasta_minimizers", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_demux", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
+    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_pwm_scan", "fx_fasta_pwm_best", "fx_fasta_minimizers", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_demux", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fasta_sketch", "fx_fastq_sketch", "fx_sketch_info", "fx_sketch_read", "fx_sketch_from_host", "fx_sketch_compare", "fx_sketch_free", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
     "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
     "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
     "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
@@ -260,6 +261,14 @@ def lib():
     L.fx_kmer_set_create.argtypes = [vp, i32, i32, vp, i64, C.POINTER(vp)]
     L.fx_kmer_set_free.argtypes = [vp]
     L.fx_kmer_set_contains.argtypes = [vp, vp, i64, vp]
+    u64 = C.c_uint64
+    L.fx_fasta_sketch.argtypes = [vp, i32, i32, vp, i64, u64, i64, i32, C.POINTER(vp), C.POINTER(i32)]
+    L.fx_fastq_sketch.argtypes = [vp, i32, i32, vp, i64, vp, vp, u64, i64, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64)]
+    L.fx_sketch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.fx_sketch_read.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fx_sketch_from_host.argtypes = [i32, i32, i32, u64, i64, i64, vp, vp, C.POINTER(vp)]
+    L.fx_sketch_compare.argtypes = [vp, vp, vp, i64, vp, i64, i64, u64, i64, C.POINTER(vp), C.POINTER(vp)]
+    L.fx_sketch_free.argtypes = [vp]
     L.fx_fastq_kmer_hits.argtypes = [vp, vp, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fastq_kmer_screen.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.fx_fasta_kmer_hits.argtypes = [vp, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
@@ -499,6 +508,61 @@ class Comm:
         if self._c:
             lib().fx_comm_destroy(self._c)
             self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SketchObj:
+    """Owning wrapper of an fx_sketch: the sorted key lists of its sets in device memory, independent of the blob that made it
+    (pyfastx_amd/sketch.py builds the public object on it)."""
+
+    def __init__(self, ptr):
+        self._s = ptr
+        k, fl, mk, sz, ns, nk = C.c_int(0), C.c_int(0), C.c_uint64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().fx_sketch_info(self._s, C.byref(k), C.byref(fl), C.byref(mk), C.byref(sz), C.byref(ns), C.byref(nk)))
+        self.k, self.flags, self.max_key, self.size, self.n_sets, self.n_keys = k.value, fl.value, mk.value, sz.value, ns.value, nk.value
+
+    @classmethod
+    def from_host(cls, device, k, flags, max_key, size, off, keys):
+        """fx_sketch_from_host: off int64[n_sets + 1], keys uint64[off[-1]]; what the device checks refuse raises FxError(FX_EINVAL)."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        s = C.c_void_p()
+        check(lib().fx_sketch_from_host(int(device), int(k), int(flags), int(max_key), int(size), off.size - 1, _ptr(off), _ptr(keys) if keys.size else None,
+                                        C.byref(s)))
+        return cls(s)
+
+    def _live(self):
+        if self._s is None:
+            raise FxError(FX_ESTATE, "the sketch has been freed")
+        return self._s
+
+    def read(self):
+        """(off int64[n_sets + 1], keys uint64[n_keys]) in pinned memory (fx_sketch_read)."""
+        po, pk = C.c_void_p(), C.c_void_p()
+        check(lib().fx_sketch_read(self._live(), C.byref(po), C.byref(pk)))
+        return pinned_array(po.value, self.n_sets + 1, np.int64), pinned_array(pk.value, max(self.n_keys, 1), np.uint64)[:self.n_keys]
+
+    def compare(self, other, ia=None, ib=None, limit=0, max_key=0, max_pairs=10**8):
+        """(shared, total), int64[n_a, n_b] in pinned memory (fx_sketch_compare); ia / ib: the sets that take part, None: all."""
+        ia = None if ia is None else np.ascontiguousarray(ia, dtype=np.int64)
+        ib = None if ib is None else np.ascontiguousarray(ib, dtype=np.int64)
+        na, nb = (self.n_sets if ia is None else ia.size), (other.n_sets if ib is None else ib.size)
+        keep = [np.zeros(1, dtype=np.int64) if a is not None and a.size == 0 else a for a in (ia, ib)]      # an empty selection still hands over a pointer
+        ps, pt = C.c_void_p(), C.c_void_p()
+        check(lib().fx_sketch_compare(self._live(), other._live(), _ptr(keep[0]), na, _ptr(keep[1]), nb, int(limit), int(max_key), int(max_pairs),
+                                      C.byref(ps), C.byref(pt)))
+        sh, tot = _pinned_columns((ps, pt), (np.int64, np.int64), na * nb)
+        return sh.reshape(na, nb), tot.reshape(na, nb)
+
+    def close(self):
+        if self._s:
+            lib().fx_sketch_free(self._s)
+            self._s = None
 
     def __del__(self):
         try:
@@ -1451,6 +1515,24 @@ class Blob:
     def kmer_set(self, k, canonical, codes):
         """A device k-mer set of `codes` on this blob's device (fx_kmer_set_create) -> KmerSet; any blob of the device may use it."""
         return KmerSet(self, k, canonical, codes)
+
+    def fasta_sketch(self, k, flags, ids=None, max_key=1, size=0, oversample=0):
+        """Sketches of the selected records (fx_fasta_sketch; flags: FX_SK_CANONICAL | FX_SK_POOLED; ids: distinct ascending
+        record ids, None: every record) -> (SketchObj, n_rounds)."""
+        buf, n_ids, _ = self._kmer_ids(ids)
+        s, nr = C.c_void_p(), C.c_int(0)
+        check(lib().fx_fasta_sketch(self._h, int(k), int(flags), _ptr(buf), n_ids, int(max_key), int(size), int(oversample), C.byref(s), C.byref(nr)))
+        return SketchObj(s), int(nr.value)
+
+    def fastq_sketch(self, k, flags, ids=None, start=None, end=None, max_key=1, size=0, oversample=0):
+        """The pooled sketch of the reads `ids` cut to [start, end) (fx_fastq_sketch) -> (SketchObj, n_rounds); a bad id or
+        interval raises FxError(FX_ERANGE) with .first_bad."""
+        q, keep = self._fastq_queries(ids, start, end)
+        s, nr, bad = C.c_void_p(), C.c_int(0), C.c_int64(-1)
+        rc = lib().fx_fastq_sketch(self._h, int(k), int(flags), *q, int(max_key), int(size), int(oversample), C.byref(s), C.byref(nr), C.byref(bad))
+        if rc:
+            _raise(rc, first_bad=int(bad.value))
+        return SketchObj(s), int(nr.value)
 
     def _kmer_hits(self, call, head, dtype):
         pw, ph, n, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(-1)

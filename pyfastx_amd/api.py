@@ -917,6 +917,25 @@ class Fasta(_fxobj.FastaCore):
         minimizer.check_args(k, w, order)
         return minimizer.count_blob(self._search_blob(), k, w, canonical, order)
 
+    def sketch(self, k=21, scaled=None, size=None, canonical=True, ids=None, pooled=False, oversample=None):
+        """Extension: MinHash / FracMinHash sketches of the records -> sketch.Sketch, one set per selected record in ascending
+        record order (ids: names or 0-based ids, None: every record), or one set for all of them with pooled=True, such as a
+        multi-contig assembly.  The windows and codes are kmer_table's; key = minimizer.mix(code, k).  A set keeps the distinct
+        keys below max_key = ceil(4^k / scaled) (scaled None: 4^k) and, with size, the `size` smallest of them; at least one of
+        scaled and size must be given.  The sets stay in device memory: Sketch.compare / jaccard / containment / mash_distance /
+        ani compare them there.  oversample (1..64, None: 4) sizes the first threshold of a bottom-`size` sketch; no result
+        depends on it, only Sketch.n_rounds does.  On the GPU from the resident stream (csrc/fx_sketch.hpp)."""
+        from . import sketch
+        sketch.check_args(k, scaled, size)
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        blob = self._search_blob()
+        names = [r[0] for r in self._db.execute("SELECT chrom FROM seq ORDER BY ID")]
+        if sel is not None:
+            names = [names[i] for i in sel.tolist()]
+        if pooled:
+            names = [os.path.basename(self.file_name)]
+        return sketch.fasta_sketch_blob(blob, k, scaled, size, canonical, sel, pooled, names, oversample or 0, self._st.device)
+
     def kmer_counts(self, k, canonical=False, ids=None):
         """Extension: the k-mer spectrum of the `seq` of every record -> int64[4**k] in pinned memory, counted on the GPU
         from the resident stream (csrc/fx_kmer.hpp).  Letters A C G T in either case (A = 0, C = 1, G = 2, T = 3; uppercase=
@@ -2152,6 +2171,15 @@ class Fastq(_fxobj.FastqCore):
         from . import kmer
         kmer.check_table(k, min_count, max_bytes)
         return kmer.fastq_table_blob(self._qc_blob(), self._rlen_host.size, k, canonical, ids, start, end, min_count, max_bytes)
+
+    def sketch(self, k=21, scaled=None, size=None, canonical=True, ids=None, start=None, end=None, oversample=None):
+        """Extension: the MinHash / FracMinHash sketch of the read set -> sketch.Sketch with one pooled set of the windows of
+        seq[start:end] of the reads `ids`; k, scaled, size, canonical and oversample are Fasta.sketch's, ids / start / end follow
+        kmer_counts."""
+        from . import sketch
+        sketch.check_args(k, scaled, size)
+        return sketch.fastq_sketch_blob(self._qc_blob(), self._rlen_host.size, k, scaled, size, canonical, ids, start, end,
+                                        os.path.basename(self.file_name), oversample or 0, self._st.device)
 
     def kmer_hits(self, table, ids=None, start=None, end=None):
         """Extension: per query, the valid k-mer windows of seq[start:end] and how many of them occur in `table` (a

@@ -56,6 +56,7 @@
 #include "fx_minimizer.hpp"
 #include "fx_kmer_table.hpp"
 #include "fx_kmer_screen.hpp"
+#include "fx_sketch.hpp"
 #include "fx_fastq_dedup.hpp"
 
 using namespace fx;
@@ -333,10 +334,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce"};
 
 struct Prof {
     bool on = false;
@@ -5686,6 +5687,453 @@ extern "C" int fx_fasta_kmer_hits(fx_handle *h, const fx_kmer_set *set, const in
     }
     out.release(n_windows, n_hits);
     *n_rows = n_sel;
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ sketches (fx_sketch.hpp)
+struct fx_sketch {
+    int device = 0, k = 0, flags = 0;
+    uint64_t max_key = 0;
+    int64_t size = 0, n_sets = 0, n_keys = 0;
+    uint64_t *keys = nullptr;                                // n_keys, every set ascending and distinct
+    int64_t *off = nullptr;                                  // n_sets + 1
+    hipStream_t stream = nullptr;                            // fx_sketch_read and fx_sketch_compare run on it: a sketch needs no handle
+};
+
+extern "C" int fx_sketch_free(fx_sketch *sk) {
+    if (!sk) return FX_OK;
+    (void)hipSetDevice(sk->device);
+    if (sk->stream) { (void)hipStreamSynchronize(sk->stream); (void)hipStreamDestroy(sk->stream); }
+    if (sk->keys) (void)hipFree(sk->keys);
+    if (sk->off) (void)hipFree(sk->off);
+    delete sk;
+    return FX_OK;
+}
+struct SketchDrop { void operator()(fx_sketch *s) const { (void)fx_sketch_free(s); } };
+using SketchPtr = std::unique_ptr<fx_sketch, SketchDrop>;
+
+// what the numbers alone decide, for every entry that takes them
+static int sketch_args(int32_t k, int flags, uint64_t max_key, int64_t size) {
+    if (k < 1 || k > SK_MAX_K) return fail(FX_EINVAL, "k = %d outside 1..%d", (int)k, SK_MAX_K);
+    if (flags & ~(FX_SK_CANONICAL | FX_SK_POOLED)) return fail(FX_EINVAL, "unknown flag bits %d", flags);
+    if (max_key < 1 || max_key > ((uint64_t)1 << (2 * k))) return fail(FX_EINVAL, "max_key %llu outside 1..4^%d", (unsigned long long)max_key, (int)k);
+    if (size < 0) return fail(FX_EINVAL, "size %lld below 0", (long long)size);
+    return FX_OK;
+}
+static int sketch_oversample(int32_t oversample) {
+    if (oversample < 0 || oversample > SK_MAX_OVERSAMPLE) return fail(FX_EINVAL, "oversample %d outside 1..%d (0: the default)", (int)oversample, SK_MAX_OVERSAMPLE);
+    return FX_OK;
+}
+static int bits_of(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+
+// a sketch of the device with room for n_keys keys and n_sets + 1 offsets, nothing in them yet
+static int sketch_new(int device, int k, int flags, uint64_t max_key, int64_t size, int64_t n_sets, int64_t n_keys, SketchPtr *out) {
+    SketchPtr s(new fx_sketch());
+    s->device = device; s->k = k; s->flags = flags; s->max_key = max_key; s->size = size; s->n_sets = n_sets; s->n_keys = n_keys;
+    HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if (dev_malloc((void **)&s->keys, (size_t)std::max<int64_t>(n_keys, 1) * 8) != hipSuccess ||
+        dev_malloc((void **)&s->off, (size_t)(n_sets + 1) * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FX_ENOMEM, "device memory for a sketch of %lld keys in %lld sets", (long long)n_keys, (long long)n_sets);
+    }
+    *out = std::move(s);
+    return FX_OK;
+}
+// ... of n_sets empty sets
+static int sketch_empty(fx_handle *h, int k, int flags, uint64_t max_key, int64_t size, int64_t n_sets, fx_sketch **sk, int32_t *n_rounds) {
+    SketchPtr s;
+    int rc = sketch_new(h->device, k, flags, max_key, size, n_sets, 0, &s);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(s->off, 0, (size_t)(n_sets + 1) * 8, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *sk = s.release();
+    *n_rounds = 0;
+    return FX_OK;
+}
+
+// buf: `have` elements -> the same in a block of `need` (the old block goes back to the pool once the stream has passed the copy)
+template <class T> static int scratch_grow(ScratchBuf<T> &buf, int device, hipStream_t s, int64_t have, int64_t need) {
+    ScratchBuf<T> nb;
+    int rc = nb.alloc(device, need, s);
+    if (rc) return rc;
+    if (have > 0) HIPCHK(hipMemcpyAsync(nb.p, buf.p, (size_t)have * sizeof(T), hipMemcpyDeviceToDevice, s));
+    std::swap(buf.p, nb.p); std::swap(buf.cap_bytes, nb.cap_bytes); std::swap(buf.dev, nb.dev); std::swap(buf.stream, nb.stream);
+    return FX_OK;
+}
+
+// The per-set state of the rounds on the device: threshold, letters, keys kept, bounds among the distinct rows, the flags.
+struct SkState {
+    ScratchBuf<uint64_t> T;
+    ScratchBuf<unsigned long long> W, left;
+    ScratchBuf<int64_t> cnt, seg;
+    ScratchBuf<uint8_t> active, now;
+    int alloc(fx_handle *h, int64_t n_sets) {
+        int rc;
+        const int d = h->device;
+        hipStream_t s = h->stream;
+        if ((rc = T.alloc(d, n_sets, s)) || (rc = W.alloc(d, n_sets, s)) || (rc = left.alloc(d, 1, s)) || (rc = cnt.alloc(d, n_sets, s)) ||
+            (rc = seg.alloc(d, n_sets + 1, s)) || (rc = active.alloc(d, n_sets, s)) || (rc = now.alloc(d, n_sets, s)))
+            return rc;
+        HIPCHK(hipMemsetAsync(W.p, 0, (size_t)n_sets * 8, s));
+        return FX_OK;
+    }
+};
+struct SkShape { int k, flags; uint64_t max_key; int64_t size; int oversample; int64_t n_sets; };
+
+// n rows (keys in kp[0]; with several sets their sets in vp[0]) -> by (set, key).  kx: a third key buffer (several sets).
+// -> the sorted rows in *s_key / *s_set, and the buffers that are free afterwards in *f_key / *f_set.
+static hipError_t sketch_sort(hipStream_t s, bool multi, int key_bits, int set_bits, int64_t n, uint64_t *kp[2], uint32_t *vp[2], uint64_t *kx,
+                              const RadixScratch &rs, const uint64_t **s_key, const uint32_t **s_set, uint64_t **f_key, uint32_t **f_set) {
+    int cur = 0;
+    hipError_t e = multi ? radix_sort_rows(kp, vp, cur, n, key_bits, rs, s) : radix_sort_keys(kp, cur, n, key_bits, rs, s);
+    if (e != hipSuccess) return e;
+    if (!multi) { *s_key = kp[cur]; *s_set = nullptr; *f_key = kp[cur ^ 1]; *f_set = nullptr; return hipSuccess; }
+    uint64_t *kk[2] = {kp[cur ^ 1], kx};
+    int c2 = 0;
+    hipLaunchKernelGGL(k_sk_pack, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, s, (const uint32_t *)vp[cur], n, kk[0]);
+    if ((e = radix_sort_keys(kk, c2, n, set_bits, rs, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sk_gather, dim3(nblocks(n, BLOCK)), dim3(BLOCK), 0, s, (const uint64_t *)kk[c2], (const uint64_t *)kp[cur], n, kk[c2 ^ 1], vp[cur ^ 1]);
+    *s_key = kk[c2 ^ 1]; *s_set = vp[cur ^ 1]; *f_key = kp[cur]; *f_set = vp[cur];
+    return hipGetLastError();
+}
+
+// The rounds of one sketch.  src.count(round, &n): the rows of the sets that are still active, under their thresholds (waits);
+// src.emit(n, keys, sets): those rows (sets = null with one set).  S.W holds the letters of every set.
+template <class Src>
+static int sketch_rounds(fx_handle *h, const SkShape &p, SkState &S, int64_t *d_tot, Src &src, fx_sketch **out, int32_t *n_rounds) {
+    int rc;
+    const int dev = h->device;
+    hipStream_t s = h->stream;
+    const bool multi = p.n_sets > 1;
+    const int key_bits = bits_of(p.max_key - 1), set_bits = bits_of((uint64_t)(p.n_sets - 1));
+    const unsigned grid_sets = nblocks(p.n_sets + 1, BLOCK);
+    ScratchBuf<uint64_t> acc_key;
+    ScratchBuf<uint32_t> acc_set;
+    ScratchBuf<int64_t> sums;
+    int64_t acc_n = 0, acc_cap = 0;
+    int appended = 0;
+    auto no_room = [&](int64_t n) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "%lld rows of keys below the thresholds: more than the sort takes (%lld) or than the device's scratch memory holds; a larger scaled gives fewer",
+                    (long long)n, (long long)SK_MAX_ROWS);
+    };
+    FX_LAUNCH(h, K_SK_SCAN, k_sk_thresh, dim3(grid_sets), dim3(BLOCK), (const unsigned long long *)S.W.p, p.n_sets, p.k, p.max_key, p.size, p.oversample,
+              S.T.p, S.active.p, S.cnt.p);
+    for (int round = 0;; ++round) {
+        int64_t n = 0, nd = 0;
+        if ((rc = src.count(round, &n))) return rc;
+        if (n > SK_MAX_ROWS) return no_room(n);
+        ScratchBuf<uint64_t> kb[3];
+        ScratchBuf<uint32_t> vb[2], hist, totals;
+        const uint64_t *DK = nullptr;                        // the distinct rows of this round, by (set, key)
+        const uint32_t *DS = nullptr;
+        if ((rc = sums.alloc(dev, std::max(n, p.n_sets) / SRCH_CHUNK + 2, s))) return rc;
+        if (n > 0) {
+            RadixScratch rs;
+            rs.nblk = radix_tiles(n);
+            if (kb[0].alloc(dev, n, s) || kb[1].alloc(dev, n, s) || hist.alloc(dev, rs.nblk * 256, s) || totals.alloc(dev, 256, s) ||
+                (multi && (kb[2].alloc(dev, n, s) || vb[0].alloc(dev, n, s) || vb[1].alloc(dev, n, s))))
+                return no_room(n);
+            rs.hist = hist.p; rs.totals = totals.p;
+            src.emit(n, kb[0].p, multi ? vb[0].p : nullptr);
+            uint64_t *kp[2] = {kb[0].p, kb[1].p}, *f_key = nullptr;
+            uint32_t *vp[2] = {vb[0].p, vb[1].p}, *f_set = nullptr;
+            const uint64_t *s_key = nullptr;
+            const uint32_t *s_set = nullptr;
+            h->prof.begin(K_SK_SORT, s);
+            const hipError_t e = sketch_sort(s, multi, key_bits, set_bits, n, kp, vp, kb[2].p, rs, &s_key, &s_set, &f_key, &f_set);
+            h->prof.end(s);
+            if (e != hipSuccess) return fail(FX_EDEVICE, "sketch sort: %s", hipGetErrorString(e));
+            const SkLdHead head{s_key, s_set};
+            if ((rc = sscan_in<1>(h, K_SK_REDUCE, head, n, nullptr, d_tot, sums.p)) || (rc = read_home(h, &nd, d_tot, 8))) return rc;
+            FX_LAUNCH(h, K_SK_REDUCE, (k_kt_compact<SkLdHead, SkPutHead>), dim3(nblocks(n, SRCH_CHUNK)), dim3(BLOCK), head, n, (const int64_t *)sums.p,
+                      SkPutHead{s_key, s_set, f_key, f_set});
+            DK = f_key; DS = f_set;
+        }
+        FX_LAUNCH(h, K_SK_REDUCE, k_sk_bounds, dim3(grid_sets), dim3(BLOCK), DS, nd, p.n_sets, S.seg.p);
+        HIPCHK(hipMemsetAsync(S.left.p, 0, 8, s));
+        FX_LAUNCH(h, K_SK_REDUCE, k_sk_decide, dim3(grid_sets), dim3(BLOCK), (const int64_t *)S.seg.p, p.n_sets, p.max_key, p.size, S.T.p, S.active.p, S.now.p,
+                  S.cnt.p, S.left.p);
+        if (nd > 0) {
+            int64_t na = 0;
+            const SkLdTake take{DS, S.seg.p, S.now.p, p.size};
+            if ((rc = sscan_in<1>(h, K_SK_REDUCE, take, nd, nullptr, d_tot, sums.p)) || (rc = read_home(h, &na, d_tot, 8))) return rc;
+            if (na > 0) {
+                if (acc_n + na > acc_cap) {
+                    const int64_t cap = std::max(acc_n + na, 2 * acc_cap);
+                    if ((rc = scratch_grow(acc_key, dev, s, acc_n, cap)) || (multi && (rc = scratch_grow(acc_set, dev, s, acc_n, cap)))) return rc;
+                    acc_cap = cap;
+                }
+                FX_LAUNCH(h, K_SK_REDUCE, (k_kt_compact<SkLdTake, SkPutHead>), dim3(nblocks(nd, SRCH_CHUNK)), dim3(BLOCK), take, nd, (const int64_t *)sums.p,
+                          SkPutHead{DK, DS, acc_key.p + acc_n, multi ? acc_set.p + acc_n : nullptr});
+                acc_n += na;
+                ++appended;
+            }
+        }
+        unsigned long long left = 0;
+        if ((rc = read_home(h, &left, S.left.p, 8))) return rc;   // (the buffers of the round are read for the last time before this wait)
+        ++*n_rounds;
+        if (!left) break;
+    }
+    // a set became final in whatever round: once more by set where more than one round gave keys; then the offsets
+    ScratchBuf<uint64_t> fb[3];
+    ScratchBuf<uint32_t> hist, totals;
+    const uint64_t *keys = acc_key.p;
+    if (multi && appended > 1) {
+        RadixScratch rs;
+        rs.nblk = radix_tiles(acc_n);
+        if ((rc = fb[0].alloc(dev, acc_n, s)) || (rc = fb[1].alloc(dev, acc_n, s)) || (rc = fb[2].alloc(dev, acc_n, s)) ||
+            (rc = hist.alloc(dev, rs.nblk * 256, s)) || (rc = totals.alloc(dev, 256, s)))
+            return rc;
+        rs.hist = hist.p; rs.totals = totals.p;
+        uint64_t *kk[2] = {fb[0].p, fb[1].p};
+        int c2 = 0;
+        h->prof.begin(K_SK_SORT, s);
+        hipLaunchKernelGGL(k_sk_pack, dim3(nblocks(acc_n, BLOCK)), dim3(BLOCK), 0, s, (const uint32_t *)acc_set.p, acc_n, kk[0]);
+        const hipError_t e = radix_sort_keys(kk, c2, acc_n, set_bits, rs, s);
+        if (e == hipSuccess)
+            hipLaunchKernelGGL(k_sk_gather, dim3(nblocks(acc_n, BLOCK)), dim3(BLOCK), 0, s, (const uint64_t *)kk[c2], (const uint64_t *)acc_key.p, acc_n, fb[2].p,
+                               acc_set.p);
+        h->prof.end(s);
+        if (e != hipSuccess) return fail(FX_EDEVICE, "sketch sort: %s", hipGetErrorString(e));
+        keys = fb[2].p;
+    }
+    SketchPtr sk;
+    if ((rc = sketch_new(dev, p.k, p.flags, p.max_key, p.size, p.n_sets, acc_n, &sk))) return rc;
+    if ((rc = sums.alloc(dev, p.n_sets / SRCH_CHUNK + 2, s)) || (rc = sscan_in<1>(h, K_SK_REDUCE, SkLdCnt{S.cnt.p}, p.n_sets, sk->off, d_tot, sums.p))) return rc;
+    if (acc_n > 0) HIPCHK(hipMemcpyAsync(sk->keys, keys, (size_t)acc_n * 8, hipMemcpyDeviceToDevice, s));
+    int64_t kept = 0;
+    if ((rc = home(h, "sketch", {{&kept, d_tot, 8}}))) return rc;
+    if (kept != acc_n) return fail(FX_EDEVICE, "sketch: %lld keys where the sets count %lld", (long long)acc_n, (long long)kept);
+    *out = sk.release();
+    return FX_OK;
+}
+
+// FASTA: the head of the window passes (HitRuns: plan, packed, two prefix arrays), then count, kept-byte scan (round 0), the cut
+// at slen and the row scan per round.
+struct SkFastaSrc {
+    fx_handle *h;
+    HitRuns &R;
+    SkState &S;
+    int k, pooled;
+    bool canon;
+    ScratchBuf<int64_t> sums;
+    int count(int round, int64_t *n_rows) {
+        int rc;
+        const SearchPlan &P = R.P;
+        int64_t *K = R.pref.p, *Rw = K + R.nr1;
+        if (round == 0 && (rc = sums.alloc(h->device, P.n_runs / SRCH_CHUNK + 2, h->stream))) return rc;
+        with_bool(canon, [&](auto C) {
+            FX_LAUNCH(h, K_SK_COUNT, k_sk_count<C()>, dim3(R.grid_runs), dim3(BLOCK), P, k, pooled, (const uint64_t *)S.T.p, (const uint8_t *)S.active.p, R.packed.p);
+        });
+        if (round == 0 && (rc = sscan_in<1>(h, K_SK_SCAN, SrchLdKept{R.packed.p}, P.n_runs, K, R.d_tot, sums.p))) return rc;
+        with_bool(canon, [&](auto C) {
+            FX_LAUNCH(h, K_SK_SCAN, k_sk_fix<C()>, dim3(nblocks(P.n_sel, BLOCK)), dim3(BLOCK), P, k, pooled, (const uint64_t *)S.T.p, (const int64_t *)K, R.packed.p);
+        });
+        if ((rc = sscan_in<1>(h, K_SK_SCAN, SkLdRows{R.packed.p}, P.n_runs, Rw, R.d_tot, sums.p))) return rc;
+        return read_home(h, n_rows, R.d_tot, 8);
+    }
+    void emit(int64_t n, uint64_t *keys, uint32_t *sets) {
+        const int64_t *K = R.pref.p, *Rw = K + R.nr1;
+        with_bool(canon, [&](auto C) {
+            FX_LAUNCH(h, K_SK_EMIT, k_sk_emit<C()>, dim3(R.grid_runs), dim3(BLOCK), R.P, k, pooled, (const uint64_t *)S.T.p, (const uint32_t *)R.packed.p, K, Rw, n,
+                      keys, sets);
+        });
+    }
+};
+
+extern "C" int fx_fasta_sketch(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, uint64_t max_key, int64_t size, int32_t oversample,
+                               fx_sketch **sk, int32_t *n_rounds) {
+    if (sk) *sk = nullptr;
+    if (n_rounds) *n_rounds = 0;
+    int rc = sketch_args(k, flags, max_key, size);
+    if (!rc) rc = sketch_oversample(oversample);
+    if (rc) return rc;
+    if (!h || !sk || !n_rounds) return fail(FX_EINVAL, "null argument");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
+    rc = use_device(h);
+    if (!rc) rc = finish_build(h);
+    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord);
+    if (rc) return rc;
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    const int pooled = (flags & FX_SK_POOLED) ? 1 : 0;
+    const SkShape p{(int)k, flags, max_key, size, oversample ? (int)oversample : 4, pooled ? 1 : n_sel};
+    if (n_sel == 0) return sketch_empty(h, k, flags, max_key, size, p.n_sets, sk, n_rounds);
+    if (p.n_sets > 0xFFFFFFFFll) return fail(FX_ERANGE, "%lld sets: more than a 32-bit slot numbers", (long long)p.n_sets);
+    Staged st(h);
+    st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
+    HitRuns R;
+    if ((rc = R.open(h, st, nullptr, k, ids, n_ids, 2, nullptr))) return rc;
+    if (R.P.n_runs == 0) return sketch_empty(h, k, flags, max_key, size, p.n_sets, sk, n_rounds);
+    SkState S;
+    if ((rc = S.alloc(h, p.n_sets))) return rc;
+    FX_LAUNCH(h, K_SK_SCAN, k_sk_letters_fa, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), R.P, pooled, S.W.p);
+    SkFastaSrc src{h, R, S, (int)k, pooled, (flags & FX_SK_CANONICAL) != 0, {}};
+    return sketch_rounds(h, p, S, R.d_tot, src, sk, n_rounds);
+}
+
+// FASTQ: one pooled set; the rows are counted and then stored at one cursor.
+struct SkFastqSrc {
+    fx_handle *h;
+    SkState &S;
+    FqView v;
+    FqQueries Q;
+    int64_t n;
+    int lpr, k;
+    bool canon;
+    unsigned long long *cursor;
+    template <bool EMIT> void walk(uint64_t *out, uint64_t cap) {
+        with_bool(canon, [&](auto C) {
+            FX_LAUNCH(h, EMIT ? K_SK_EMIT : K_SK_COUNT, (k_sk_fastq<C(), EMIT>), dim3(lane_group_grid<k_sk_fastq<C(), EMIT>>(h, n, lpr)), dim3(BLOCK), v.data, v.base,
+                      v.n, v.rlen, v.soff, Q.ids, (int64_t)0, n, Q.start, Q.end, lpr, k, (const uint64_t *)S.T.p, out, cap, cursor);
+        });
+    }
+    int count(int, int64_t *n_rows) {
+        HIPCHK(hipMemsetAsync(cursor, 0, 8, h->stream));
+        walk<false>(nullptr, 0);
+        HIPCHK(hipGetLastError());
+        return read_home(h, n_rows, cursor, 8);
+    }
+    void emit(int64_t rows, uint64_t *keys, uint32_t *) {
+        (void)hipMemsetAsync(cursor, 0, 8, h->stream);
+        walk<true>(keys, (uint64_t)rows);
+    }
+};
+
+extern "C" int fx_fastq_sketch(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                               uint64_t max_key, int64_t size, int32_t oversample, fx_sketch **sk, int32_t *n_rounds, int64_t *first_bad) {
+    if (sk) *sk = nullptr;
+    if (n_rounds) *n_rounds = 0;
+    if (first_bad) *first_bad = -1;
+    int rc = sketch_args(k, flags, max_key, size);
+    if (!rc) rc = sketch_oversample(oversample);
+    if (rc) return rc;
+    if (!h || !sk || !n_rounds || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    FqLaunch q;
+    if ((rc = fq_prepare(h, 0, 0, &q))) return rc;             // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+    const int64_t n = ids ? n_ids : h->n_reads;
+    if ((rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead))) return rc;
+    const SkShape p{(int)k, flags | FX_SK_POOLED, max_key, size, oversample ? (int)oversample : 4, 1};
+    if (n == 0) return sketch_empty(h, k, p.flags, max_key, size, 1, sk, n_rounds);
+    Staged st(h);
+    SkState S;
+    SkFastqSrc src{h, S, fq_view(h), {}, n, q.lpr, (int)k, (flags & FX_SK_CANONICAL) != 0, nullptr};
+    if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &src.Q))) return rc;
+    int64_t *d_tot = nullptr;
+    if ((rc = S.alloc(h, 1)) || (rc = st.scratch<int64_t>(8, &d_tot)) || (rc = st.scratch<unsigned long long>(1, &src.cursor))) return rc;
+    FX_LAUNCH(h, K_SK_SCAN, k_sk_letters_fq, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)h->fq_rlen.p, src.Q.ids, n, src.Q.start, src.Q.end, S.W.p);
+    return sketch_rounds(h, p, S, d_tot, src, sk, n_rounds);
+}
+
+extern "C" int fx_sketch_info(const fx_sketch *sk, int32_t *k, int *flags, uint64_t *max_key, int64_t *size, int64_t *n_sets, int64_t *n_keys) {
+    if (!sk) return fail(FX_EINVAL, "null argument");
+    if (k) *k = sk->k;
+    if (flags) *flags = sk->flags;
+    if (max_key) *max_key = sk->max_key;
+    if (size) *size = sk->size;
+    if (n_sets) *n_sets = sk->n_sets;
+    if (n_keys) *n_keys = sk->n_keys;
+    return FX_OK;
+}
+
+// two pinned blocks of the caller's, freed again when the call fails
+struct SkPinned {
+    void *p[2] = {nullptr, nullptr};
+    bool alloc(int64_t b0, int64_t b1) { return (p[0] = fx_pinned_alloc(b0)) && (p[1] = fx_pinned_alloc(b1)); }
+    ~SkPinned() { fx_pinned_free(p[0]); fx_pinned_free(p[1]); }
+    template <class A, class B> void release(A **a, B **b) { *a = (A *)p[0]; *b = (B *)p[1]; p[0] = p[1] = nullptr; }
+};
+
+extern "C" int fx_sketch_read(fx_sketch *sk, int64_t **off, uint64_t **keys) {
+    if (off) *off = nullptr;
+    if (keys) *keys = nullptr;
+    if (!sk || !off || !keys) return fail(FX_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(sk->device));
+    SkPinned pin;
+    if (!pin.alloc((sk->n_sets + 1) * 8, std::max<int64_t>(sk->n_keys, 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld keys", (long long)sk->n_keys);
+    HIPCHK(hipMemcpyAsync(pin.p[0], sk->off, (size_t)(sk->n_sets + 1) * 8, hipMemcpyDeviceToHost, sk->stream));
+    if (sk->n_keys > 0) HIPCHK(hipMemcpyAsync(pin.p[1], sk->keys, (size_t)sk->n_keys * 8, hipMemcpyDeviceToHost, sk->stream));
+    HIPCHK(hipStreamSynchronize(sk->stream));
+    pin.release(off, keys);
+    return FX_OK;
+}
+
+extern "C" int fx_sketch_from_host(int device, int32_t k, int flags, uint64_t max_key, int64_t size, int64_t n_sets, const int64_t *off, const uint64_t *keys,
+                                   fx_sketch **sk) {
+    if (sk) *sk = nullptr;
+    int rc = sketch_args(k, flags, max_key, size);
+    if (rc) return rc;
+    if (!sk || !off || n_sets < 0) return fail(FX_EINVAL, "null argument, or a negative number of sets");
+    const int64_t n_keys = off[n_sets];
+    if (off[0] != 0 || n_keys < 0 || (n_keys > 0 && !keys)) return fail(FX_EINVAL, "the offsets begin at %lld and end at %lld, or the keys are null", (long long)off[0], (long long)n_keys);
+    if ((rc = an_device())) return rc;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(FX_EDEVICE, "device %d out of range (have %d)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    SketchPtr s;
+    if ((rc = sketch_new(device, k, flags, max_key, size, n_sets, n_keys, &s))) return rc;
+    ScratchBuf<unsigned long long> bad;                      // every offset and key is looked at on the device before the sketch is handed out
+    if ((rc = bad.alloc(device, 1, s->stream))) return rc;
+    HIPCHK(hipMemsetAsync(bad.p, 0xFF, 8, s->stream));
+    HIPCHK(hipMemcpyAsync(s->off, off, (size_t)(n_sets + 1) * 8, hipMemcpyHostToDevice, s->stream));
+    if (n_keys > 0) HIPCHK(hipMemcpyAsync(s->keys, keys, (size_t)n_keys * 8, hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_sk_check, dim3(nblocks(n_sets + n_keys, BLOCK)), dim3(BLOCK), 0, s->stream, (const int64_t *)s->off, n_sets, (const uint64_t *)s->keys,
+                       n_keys, max_key, size, bad.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long first = ~0ull;
+    HIPCHK(hipMemcpyAsync(&first, bad.p, 8, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (first != ~0ull) {
+        if ((int64_t)first < n_sets)
+            return fail(FX_EINVAL, "set %lld: its offsets do not ascend, or it holds more than size = %lld keys", (long long)first, (long long)size);
+        return fail(FX_EINVAL, "key %lld is not below max_key, or not above the key in front of it in its set", (long long)((int64_t)first - n_sets));
+    }
+    *sk = s.release();
+    return FX_OK;
+}
+
+extern "C" int fx_sketch_compare(fx_sketch *a, fx_sketch *b, const int64_t *ia, int64_t n_a, const int64_t *ib, int64_t n_b, int64_t limit, uint64_t max_key,
+                                 int64_t max_pairs, int64_t **shared, int64_t **total) {
+    if (shared) *shared = nullptr;
+    if (total) *total = nullptr;
+    if (!a || !b || !shared || !total) return fail(FX_EINVAL, "null argument");
+    if (limit < 0 || max_pairs < 0 || (ia && n_a < 0) || (ib && n_b < 0)) return fail(FX_EINVAL, "a negative limit, max_pairs or number of sets");
+    if (a->k != b->k || ((a->flags ^ b->flags) & FX_SK_CANONICAL))
+        return fail(FX_EINVAL, "sketches of k = %d%s and k = %d%s do not compare", a->k, a->flags & FX_SK_CANONICAL ? " canonical" : "", b->k,
+                    b->flags & FX_SK_CANONICAL ? " canonical" : "");
+    if (a->device != b->device) return fail(FX_EINVAL, "the sketches live on devices %d and %d", a->device, b->device);
+    const int64_t nA = ia ? n_a : a->n_sets, nB = ib ? n_b : b->n_sets;
+    for (int64_t i = 0; ia && i < n_a; ++i)
+        if (ia[i] < 0 || ia[i] >= a->n_sets) return fail(FX_ERANGE, "set %lld outside the %lld sets of the first sketch", (long long)ia[i], (long long)a->n_sets);
+    for (int64_t i = 0; ib && i < n_b; ++i)
+        if (ib[i] < 0 || ib[i] >= b->n_sets) return fail(FX_ERANGE, "set %lld outside the %lld sets of the second sketch", (long long)ib[i], (long long)b->n_sets);
+    if (nA > 0 && nB > max_pairs / nA) return fail(FX_ERANGE, "%lld x %lld pairs, more than the %lld asked for", (long long)nA, (long long)nB, (long long)max_pairs);
+    const int64_t pairs = nA * nB;
+    HIPCHK(hipSetDevice(a->device));
+    SkPinned pin;
+    if (!pin.alloc(std::max<int64_t>(pairs, 1) * 8, std::max<int64_t>(pairs, 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld pairs", (long long)pairs);
+    if (pairs > 0) {
+        int rc;
+        hipStream_t s = a->stream;
+        ScratchBuf<int64_t> out, sel;
+        if ((rc = out.alloc(a->device, 2 * pairs, s)) || (rc = sel.alloc(a->device, (ia ? n_a : 0) + (ib ? n_b : 0), s))) return rc;
+        int64_t *d_ia = ia ? sel.p : nullptr, *d_ib = ib ? sel.p + (ia ? n_a : 0) : nullptr;
+        if (ia) HIPCHK(hipMemcpyAsync(d_ia, ia, (size_t)n_a * 8, hipMemcpyHostToDevice, s));
+        if (ib) HIPCHK(hipMemcpyAsync(d_ib, ib, (size_t)n_b * 8, hipMemcpyHostToDevice, s));
+        const int64_t want = (pairs + BLOCK / 64 - 1) / (BLOCK / 64);                  // a wave per pair; beyond 2^20 workgroups the waves stride
+        hipLaunchKernelGGL(k_sk_compare, dim3((unsigned)std::min<int64_t>(want, 1 << 20)), dim3(BLOCK), 0, s, SkSide{a->keys, a->off, d_ia, nA},
+                           SkSide{b->keys, b->off, d_ib, nB}, limit, max_key, out.p, out.p + pairs);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(pin.p[0], out.p, (size_t)pairs * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(pin.p[1], out.p + pairs, (size_t)pairs * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    pin.release(shared, total);
     return FX_OK;
 }
 
