@@ -3367,6 +3367,26 @@ static int check_ids(const int64_t *ids, int64_t n_ids, int64_t limit, int64_t *
         if (ids[k] < 0 || ids[k] >= limit) { if (first_bad) *first_bad = k; return fail(FX_ERANGE, fmt, (long long)ids[k]); }
     return FX_OK;
 }
+// What an entry on the runs of the selected FASTA records checks, in three steps with the entry's own checks between them where
+// it has some.  fasta_state: the id array, the table, the shard (noun: what a byte-range shard carries no halo for).
+// fasta_device: the device, the build waited for.  fasta_enter: fasta_device, then the ids against the table (*first_bad where
+// asked for) -> *n_sel, the records selected.
+static int fasta_state(fx_handle *h, const char *noun, const int64_t *ids, int64_t n_ids) {
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
+    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for %s across its cuts", noun);
+    return FX_OK;
+}
+static int fasta_device(fx_handle *h) {
+    const int rc = use_device(h);
+    return rc ? rc : finish_build(h);
+}
+static int fasta_enter(fx_handle *h, const int64_t *ids, int64_t n_ids, int64_t *first_bad, int64_t *n_sel) {
+    int rc;
+    if ((rc = fasta_device(h)) || (rc = check_ids(ids, n_ids, h->n_hdr, first_bad, kBadRecord))) return rc;
+    *n_sel = ids ? n_ids : h->n_hdr;
+    return FX_OK;
+}
 
 // The pinned result blocks of one call.  Unless release() has handed them to the caller they go back to the pool when the call
 // ends -- and a copy into them may still be in flight when something fails, so the stream is waited for first.
@@ -3858,9 +3878,10 @@ template <class F> static void with_levels(int d, F &&f) {
     else f(std::integral_constant<int, 9>{});
 }
 
-// The head of every pass that looks for windows (exact, approximate and matrix search, the matrix's best window): the pinned
-// words the totals of the scans land in, the plan over the runs of the selected records, one packed word per run and n_pref
-// prefix arrays of n_runs + 1.  P.n_runs == 0 afterwards: nothing but empty records, and `counts` (where given) is zeroed.
+// The head of every pass that looks for windows (exact, approximate and matrix search, the matrix's best window, minimizers,
+// spectra, tables, screening, sketches): the pinned words the totals of the scans land in, the plan over the runs of the
+// selected records (timed under scan_id), one packed word per run and n_pref prefix arrays of n_runs + 1.  P.n_runs == 0
+// afterwards: nothing but empty records, and `counts` (where given) is zeroed.
 struct HitRuns {
     SearchPlan P;
     std::unique_ptr<int64_t, void (*)(void *)> tot{nullptr, fx_pinned_free};
@@ -3868,12 +3889,14 @@ struct HitRuns {
     ScratchBuf<uint32_t> packed;
     ScratchBuf<int64_t> pref;
     unsigned grid_runs = 1;
-    int open(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int n_pref, int64_t *counts) {
+    int scan_id = 0;
+    int open(fx_handle *h, Staged &st, int id, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int n_pref, int64_t *counts) {
         int rc;
         tot.reset((int64_t *)fx_pinned_alloc(64));
         if (!tot) return FX_ENOMEM;
         P.masks = masks;
-        if ((rc = fasta_run_plan(h, st, K_SEARCH_SCAN, ids, n_ids, plen, &P, &d_tot, tot.get()))) return rc;     // runs of every selected record -> run0
+        scan_id = id;
+        if ((rc = fasta_run_plan(h, st, id, ids, n_ids, plen, &P, &d_tot, tot.get()))) return rc;     // runs of every selected record -> run0
         if (P.n_runs >= ((int64_t)1 << 31) * BLOCK) return fail(FX_ERANGE, "stream too large for one search grid");
         if (P.n_runs == 0) {
             if (counts) memset(counts, 0, (size_t)P.n_sel * 16);
@@ -3883,6 +3906,12 @@ struct HitRuns {
         grid_runs = nblocks(P.n_runs, BLOCK);
         if ((rc = packed.alloc(h->device, P.n_runs, h->stream)) || (rc = pref.alloc(h->device, n_pref * nr1, h->stream))) return rc;
         return FX_OK;
+    }
+    // the kept bytes of every run and their scan into the first prefix array: the cut at slen is known before the first window
+    // is produced (the passes whose count kernel leaves the kept bytes in `packed` itself scan them on their own)
+    int kept(fx_handle *h, Staged &st) {
+        FX_LAUNCH(h, K_KT_KEPT, k_kt_kept, dim3(grid_runs), dim3(BLOCK), P, packed.p);
+        return sscan<1>(h, st, scan_id, SrchLdKept{packed.p}, P.n_runs, pref.p, d_tot);
     }
 };
 
@@ -3899,7 +3928,7 @@ static int run_hits(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen,
                     void **extra, int64_t *n_hits) {
     int rc;
     HitRuns R;
-    if ((rc = R.open(h, st, masks, plen, ids, n_ids, 4, counts)) || R.P.n_runs == 0) return rc;
+    if ((rc = R.open(h, st, K_SEARCH_SCAN, masks, plen, ids, n_ids, 4, counts)) || R.P.n_runs == 0) return rc;
     const SearchPlan &P = R.P;
     int64_t *K = R.pref.p, *Pp = K + R.nr1, *Pm = K + 2 * R.nr1, *NZ = K + 3 * R.nr1;
     const unsigned grid_sel = nblocks(P.n_sel, BLOCK);
@@ -3959,13 +3988,9 @@ static int fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, i
     if (((mode & FX_SEARCH_PLUS) && !pat) || ((mode & FX_SEARCH_MINUS) && !rpat)) return fail(FX_EINVAL, "null pattern");
     const bool counts_only = cap == 0 && counts;
     if (cap < 0 || (!counts_only && (!rec || !start || !strand || (approx && !mismatch)))) return fail(FX_EINVAL, "null output");
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for hits across its cuts");
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (rc) return rc;
-    std::vector<ulonglong2> masks(256);
+    int rc;
+    if ((rc = fasta_state(h, "hits", ids, n_ids)) || (rc = fasta_device(h))) return rc;
+    std::vector<ulonglong2> masks(256);                    // (the letters of the pattern are looked at before the ids: fasta_enter in two parts)
     {
         std::vector<uint64_t> f(256, 0), r(256, 0);
         if (((mode & FX_SEARCH_PLUS) && !search_masks(pat, plen, mode, f.data())) ||
@@ -4088,14 +4113,8 @@ static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, i
     if (!h || (!best && !n_hits)) return fail(FX_EINVAL, "null argument");
     const bool counts_only = cap == 0 && counts;
     if (best ? !best_start : (cap < 0 || (!counts_only && (!rec || !start || !strand || !score)))) return fail(FX_EINVAL, "null output");
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for hits across its cuts");
-    rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (rc) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    int64_t n_sel = 0;
+    if ((rc = fasta_state(h, "hits", ids, n_ids)) || (rc = fasta_enter(h, ids, n_ids, nullptr, &n_sel))) return rc;
     if (n_sel == 0) return FX_OK;
     for (int64_t i = 0; best && i < 2 * n_sel; ++i) { best_score[i] = INT32_MIN; best_start[i] = -1; }
     const std::vector<int2> tab = pwm_tables(mat, plen);
@@ -4106,7 +4125,7 @@ static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, i
     if (best) {
         // kept bytes per run, their scan (K alone), then the best window of every run in front of the cut, reduced per record
         HitRuns R;
-        if ((rc = R.open(h, st, nullptr, plen, ids, n_ids, 1, nullptr)) || R.P.n_runs == 0) return rc;
+        if ((rc = R.open(h, st, K_SEARCH_SCAN, nullptr, plen, ids, n_ids, 1, nullptr)) || R.P.n_runs == 0) return rc;
         unsigned long long *keys = nullptr;
         if ((rc = st.scratch<unsigned long long>(2 * n_sel, &keys))) return rc;
         HIPCHK(hipMemsetAsync(keys, 0, (size_t)n_sel * 16, h->stream));
@@ -4169,14 +4188,9 @@ extern "C" int fx_fasta_minimizers(fx_handle *h, int32_t k, int32_t w, int flags
     if (!h || !n_hits) return fail(FX_EINVAL, "null argument");
     const bool counts_only = cap == 0 && counts;
     if (cap < 0 || (!counts_only && (!rec || !start || !strand || !code))) return fail(FX_EINVAL, "null output");
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (rc) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    int rc;
+    int64_t n_sel = 0;
+    if ((rc = fasta_state(h, "windows", ids, n_ids)) || (rc = fasta_enter(h, ids, n_ids, nullptr, &n_sel))) return rc;
     if (n_sel == 0) return FX_OK;
     const size_t lds = (size_t)BLOCK * w * sizeof(uint64_t);
     // the kernels of this call: f(CANON, LEX)
@@ -4261,9 +4275,7 @@ static int an_enter(fx_handle *h) {
     int rc = an_device();
     if (rc) return rc;
     if (!h) return fail(FX_EINVAL, "null handle");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for intervals across its cuts");
-    if ((rc = use_device(h)) || (rc = finish_build(h))) return rc;
+    if ((rc = fasta_state(h, "intervals", nullptr, 0)) || (rc = fasta_device(h))) return rc;
     return rank_build(h);
 }
 
@@ -4646,6 +4658,36 @@ static int fq_prepare(fx_handle *h, int phred, int low_qual, FqLaunch *q) {
     q->lpr = (int)std::clamp<int64_t>((mean_len + 15) / 16, 1, 64);
     return FX_OK;
 }
+// The query batch of a k-mer, sketch or duplicate entry on the FASTQ table -- the caller's ids (null: every read) and, where
+// given, an interval each -- in the steps all of them take, an entry's own checks between the steps where it has some:
+//   enter   the id count (args), the state of the handle (prepare) -> q, n
+//   check   the ids against the table (*first_bad)
+//   up      the arrays on the device, the intervals against their reads (fq_queries) -> Q, v
+// ("start and end come together" stays in the entries: it is refused before they clear their outputs, the count after.)
+struct FqBatch {
+    const int64_t *ids;
+    int64_t n_ids;
+    const int64_t *start, *end;
+    FqLaunch q = {};
+    int64_t n = 0;
+    FqQueries Q = {};
+    FqView v = {};
+    int args() const { return ids && n_ids < 0 ? fail(FX_EINVAL, "negative id count") : FX_OK; }
+    int prepare(fx_handle *h) {                            // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+        const int rc = fq_prepare(h, 0, 0, &q);
+        if (!rc) n = ids ? n_ids : h->n_reads;
+        return rc;
+    }
+    int enter(fx_handle *h) {
+        const int rc = args();
+        return rc ? rc : prepare(h);
+    }
+    int check(fx_handle *h, int64_t *first_bad) const { return check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead); }
+    int up(fx_handle *h, Staged &st, int64_t *first_bad) {
+        v = fq_view(h);
+        return fq_queries(h, st, ids, n, start, end, first_bad, &Q);
+    }
+};
 template <bool SELECT>
 static void qc_launch_reads(fx_handle *h, const FqLaunch &q, const int64_t *d_ids, int64_t nq, const QcCols &cols, const QcSel &sel, uint8_t *pass) {
     const FqView v = fq_view(h);
@@ -5064,56 +5106,56 @@ struct KmerOut {
     int home(fx_handle *h) { return ::home(h, "k-mer count", {{pin.p[0], dev.p, words * 8}}); }
 };
 
+// The units [u0, u1) of a pass whose workgroups count windows in 32-bit words, in launches of so few units that no counter
+// can wrap: launch(a, b) enqueues the pass over the units [a, b).
+template <class F> static void walk_chunks(int64_t u0, int64_t u1, int64_t per, F &&launch) {
+    for (int64_t a = u0; a < u1; a += per) launch(a, std::min(a + per, u1));
+}
+// runs per launch: no 32-bit counter of a workgroup can wrap
+template <class F> static void walk_runs(int64_t u0, int64_t u1, F &&launch) { walk_chunks(u0, u1, KMER_MAX_WINDOWS / SRCH_RUN, launch); }
+// queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
+template <class F> static void walk_queries(const fx_handle *h, int64_t u0, int64_t u1, F &&launch) {
+    walk_chunks(u0, u1, std::max<int64_t>(KMER_MAX_WINDOWS / std::max<int64_t>((int64_t)h->fq_maxlen, 1), 1), launch);
+}
+
 template <bool CANON, int MODE>
 static void kmer_fasta_launch(fx_handle *h, const SearchPlan &P, int k, unsigned long long *table, uint32_t *packed) {
     static const int64_t resident = resident_blocks(h, k_kmer_fasta<CANON, MODE>);
-    const int64_t per = KMER_MAX_WINDOWS / SRCH_RUN;          // runs per launch: no 32-bit counter of a workgroup can wrap
-    for (int64_t g0 = 0; g0 < P.n_runs; g0 += per) {
-        const int64_t g1 = std::min(g0 + per, P.n_runs);
+    walk_runs(0, P.n_runs, [&](int64_t g0, int64_t g1) {
         const unsigned nb = (unsigned)std::min<int64_t>(nblocks(g1 - g0, BLOCK), MODE == 1 ? (int64_t)1 << 30 : resident);
         FX_LAUNCH(h, K_KMER_FASTA, (k_kmer_fasta<CANON, MODE>), dim3(nb), dim3(BLOCK), P, k, g0, g1, table, packed);
-    }
+    });
 }
 
 extern "C" int fx_fasta_kmers(fx_handle *h, int32_t k, int flags, const int64_t *ids, int64_t n_ids, int per_record, int64_t **counts,
                               int64_t *n_rows, int64_t *first_bad) {
     if (!h || !counts || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
     *counts = nullptr; *n_rows = 0; *first_bad = -1;
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
+    int rc = fasta_state(h, "windows", ids, n_ids);
+    if (rc) return rc;
     if (flags & ~FX_KMER_CANONICAL) return fail(FX_EINVAL, "unknown flag bits %d", flags);
     const int kmax = per_record ? KMER_LDS_K : KMER_MAX_K;
     if (k < 1 || k > kmax) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, kmax);
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, first_bad, kBadRecord);
-    if (rc) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    int64_t n_sel = 0;
+    if ((rc = fasta_enter(h, ids, n_ids, first_bad, &n_sel))) return rc;
     const int64_t rows = per_record ? n_sel : 1;
     KmerOut out(h);
     if (n_sel > 0) {
         Staged st(h);
         st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
         // 1. runs of every selected record -> run0
-        SearchPlan P;
-        P.masks = nullptr;
-        int64_t *d_tot = nullptr, n_runs = 0;
-        if ((rc = fasta_run_plan(h, st, K_KMER_SCAN, ids, n_ids, k, &P, &d_tot, &n_runs))) return rc;
-        if ((rc = out.prepare(h, k, rows, n_runs > 0))) return rc;
-        if (n_runs > 0) {
+        HitRuns R;
+        if ((rc = R.open(h, st, K_KMER_SCAN, nullptr, k, ids, n_ids, 1, nullptr)) || (rc = out.prepare(h, k, rows, R.P.n_runs > 0))) return rc;
+        if (R.P.n_runs > 0) {
             // 2. the count pass, the scan of the kept bytes, the windows past slen taken off again
-            ScratchBuf<uint32_t> packed;
-            ScratchBuf<int64_t> K;
-            if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
             const bool canon = flags & FX_KMER_CANONICAL;
             const int64_t stride = per_record ? (int64_t)1 << (2 * k) : 0;
             with_bool(canon, [&](auto C) {
-                with_int<2>(per_record ? 2 : k <= KMER_LDS_K ? 0 : 1, [&](auto M) { kmer_fasta_launch<C(), M()>(h, P, k, out.dev.p, packed.p); });
+                with_int<2>(per_record ? 2 : k <= KMER_LDS_K ? 0 : 1, [&](auto M) { kmer_fasta_launch<C(), M()>(h, R.P, k, out.dev.p, R.packed.p); });
             });
-            if ((rc = sscan<1>(h, st, K_KMER_SCAN, SrchLdKept{packed.p}, n_runs, K.p, d_tot))) return rc;
+            if ((rc = sscan<1>(h, st, K_KMER_SCAN, SrchLdKept{R.packed.p}, R.P.n_runs, R.pref.p, R.d_tot))) return rc;
             with_bool(canon, [&](auto C) {
-                FX_LAUNCH(h, K_KMER_FIX, k_kmer_fix<C()>, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), P, (int)k, (const int64_t *)K.p, stride, out.dev.p);
+                FX_LAUNCH(h, K_KMER_FIX, k_kmer_fix<C()>, dim3(nblocks(n_sel, BLOCK)), dim3(BLOCK), R.P, (int)k, (const int64_t *)R.pref.p, stride, out.dev.p);
             });
             if ((rc = out.home(h))) return rc;
         }
@@ -5128,30 +5170,23 @@ extern "C" int fx_fastq_kmers(fx_handle *h, int32_t k, int flags, const int64_t 
     if (!h || !counts || !first_bad) return fail(FX_EINVAL, "null argument");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     *counts = nullptr; *first_bad = -1;
-    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
-    FqLaunch q;
-    int rc = fq_prepare(h, 0, 0, &q);                          // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
+    FqBatch b{ids, n_ids, start, end};
+    int rc = b.enter(h);
     if (rc) return rc;
     if (flags & ~FX_KMER_CANONICAL) return fail(FX_EINVAL, "unknown flag bits %d", flags);
     if (k < 1 || k > KMER_MAX_K) return fail(FX_EINVAL, "k %d outside 1..%d", (int)k, KMER_MAX_K);
-    const int64_t n = ids ? n_ids : h->n_reads;
-    if ((rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead))) return rc;
+    if ((rc = b.check(h, first_bad))) return rc;
     KmerOut out(h);
-    if (n > 0) {
+    if (b.n > 0) {
         Staged st(h);
-        FqQueries Q;
-        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &Q))) return rc;
-        const FqView v = fq_view(h);
-        if ((rc = out.prepare(h, k, 1, true))) return rc;
-        // queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
-        const int64_t per = std::max<int64_t>(KMER_MAX_WINDOWS / std::max<int64_t>((int64_t)h->fq_maxlen, 1), 1);
+        if ((rc = b.up(h, st, first_bad)) || (rc = out.prepare(h, k, 1, true))) return rc;
+        const FqView &v = b.v;
         with_bool(flags & FX_KMER_CANONICAL, [&](auto C) {
             with_bool(k <= KMER_LDS_K, [&](auto L) {
-                for (int64_t q0 = 0; q0 < n; q0 += per) {
-                    const int64_t q1 = std::min(q0 + per, n);
-                    FX_LAUNCH(h, K_KMER_FASTQ, (k_kmer_fastq<C(), L()>), dim3(lane_group_grid<k_kmer_fastq<C(), L()>>(h, q1 - q0, q.lpr)), dim3(BLOCK), v.data,
-                              v.base, v.n, v.rlen, v.soff, Q.ids, q0, q1, Q.start, Q.end, q.lpr, k, out.dev.p);
-                }
+                walk_queries(h, 0, b.n, [&](int64_t q0, int64_t q1) {
+                    FX_LAUNCH(h, K_KMER_FASTQ, (k_kmer_fastq<C(), L()>), dim3(lane_group_grid<k_kmer_fastq<C(), L()>>(h, q1 - q0, b.q.lpr)), dim3(BLOCK), v.data,
+                              v.base, v.n, v.rlen, v.soff, b.Q.ids, q0, q1, b.Q.start, b.Q.end, b.q.lpr, k, out.dev.p);
+                });
             });
         });
         if ((rc = out.home(h))) return rc;
@@ -5374,45 +5409,31 @@ extern "C" int fx_fasta_kmer_table(fx_handle *h, int32_t k, int flags, const int
                                    int64_t **codes, int64_t **counts, int64_t *n_distinct, int64_t *n_windows, int64_t *n_parts, int64_t *first_bad) {
     if (!h || !codes || !counts || !n_distinct || !n_windows || !n_parts || !first_bad) return fail(FX_EINVAL, "null argument");
     *codes = *counts = nullptr; *n_distinct = *n_windows = *n_parts = 0; *first_bad = -1;
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
-    int rc = kmer_table_args(k, flags, min_count, &max_bytes);
-    if (rc) return rc;
-    rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, first_bad, kBadRecord);
-    if (rc) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    int rc;
+    int64_t n_sel = 0;
+    if ((rc = fasta_state(h, "windows", ids, n_ids)) || (rc = kmer_table_args(k, flags, min_count, &max_bytes)) ||
+        (rc = fasta_enter(h, ids, n_ids, first_bad, &n_sel)))
+        return rc;
     KtOut out(h);
     if (n_sel > 0) {
         Staged st(h);
         st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
-        SearchPlan P;
-        P.masks = nullptr;
-        int64_t *d_tot = nullptr, n_runs = 0;
-        if ((rc = fasta_run_plan(h, st, K_KMER_SCAN, ids, n_ids, k, &P, &d_tot, &n_runs))) return rc;
-        if (n_runs > 0) {
-            // the kept bytes of every run and their scan: the cut at slen is known before the first window is produced
-            ScratchBuf<uint32_t> packed;
-            ScratchBuf<int64_t> K;
-            if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
-            FX_LAUNCH(h, K_KT_KEPT, k_kt_kept, dim3(nblocks(n_runs, BLOCK)), dim3(BLOCK), P, packed.p);
-            if ((rc = sscan<1>(h, st, K_KMER_SCAN, SrchLdKept{packed.p}, n_runs, K.p, d_tot))) return rc;
-            packed.release();
+        HitRuns R;
+        if ((rc = R.open(h, st, K_KMER_SCAN, nullptr, k, ids, n_ids, 1, nullptr))) return rc;
+        if (R.P.n_runs > 0) {
+            if ((rc = R.kept(h, st))) return rc;
+            R.packed.release();
             const bool canon = flags & FX_KMER_CANONICAL;
             KtSource src;
-            src.units = n_runs; src.per_unit = SRCH_RUN;
+            src.units = R.P.n_runs; src.per_unit = SRCH_RUN;
             src.walk = [&](bool emit, const KtArgs &A, int64_t u0, int64_t u1) {
                 with_bool(canon, [&](auto C) {
                     with_bool(emit, [&](auto E) {
                         static const int64_t resident = resident_blocks(h, k_kt_fasta<C(), E()>);
-                        const int64_t per = KMER_MAX_WINDOWS / SRCH_RUN;          // runs per launch: no 32-bit counter of a workgroup can wrap
-                        for (int64_t g0 = u0; g0 < u1; g0 += per) {
-                            const int64_t g1 = std::min(g0 + per, u1);
+                        walk_runs(u0, u1, [&](int64_t g0, int64_t g1) {
                             FX_LAUNCH(h, E() ? K_KT_EMIT : K_KT_HIST, (k_kt_fasta<C(), E()>), dim3((unsigned)std::min<int64_t>(nblocks(g1 - g0, BLOCK), resident)), dim3(BLOCK),
-                                      P, (int)k, g0, g1, (const int64_t *)K.p, A);
-                        }
+                                      R.P, (int)k, g0, g1, (const int64_t *)R.pref.p, A);
+                        });
                     });
                 });
             };
@@ -5428,32 +5449,24 @@ extern "C" int fx_fastq_kmer_table(fx_handle *h, int32_t k, int flags, const int
     if (!h || !codes || !counts || !n_distinct || !n_windows || !n_parts || !first_bad) return fail(FX_EINVAL, "null argument");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     *codes = *counts = nullptr; *n_distinct = *n_windows = *n_parts = 0; *first_bad = -1;
-    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
-    FqLaunch q;
-    int rc = fq_prepare(h, 0, 0, &q);                          // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
-    if (rc) return rc;
-    if ((rc = kmer_table_args(k, flags, min_count, &max_bytes))) return rc;
-    const int64_t n = ids ? n_ids : h->n_reads;
-    if ((rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead))) return rc;
+    FqBatch b{ids, n_ids, start, end};
+    int rc;
+    if ((rc = b.enter(h)) || (rc = kmer_table_args(k, flags, min_count, &max_bytes)) || (rc = b.check(h, first_bad))) return rc;
     KtOut out(h);
-    if (n > 0) {
+    if (b.n > 0) {
         Staged st(h);
-        FqQueries Q;
-        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &Q))) return rc;
-        const FqView v = fq_view(h);
+        if ((rc = b.up(h, st, first_bad))) return rc;
+        const FqView &v = b.v;
         const bool canon = flags & FX_KMER_CANONICAL;
         KtSource src;
-        src.units = n; src.per_unit = std::max<int64_t>((int64_t)h->fq_maxlen, 1);
+        src.units = b.n; src.per_unit = std::max<int64_t>((int64_t)h->fq_maxlen, 1);
         src.walk = [&](bool emit, const KtArgs &A, int64_t u0, int64_t u1) {
-            // queries per launch: even if all their windows fell to one counter of one workgroup it would not wrap
-            const int64_t per = std::max<int64_t>(KMER_MAX_WINDOWS / src.per_unit, 1);
             with_bool(canon, [&](auto C) {
                 with_bool(emit, [&](auto E) {
-                    for (int64_t q0 = u0; q0 < u1; q0 += per) {
-                        const int64_t q1 = std::min(q0 + per, u1);
-                        FX_LAUNCH(h, E() ? K_KT_EMIT : K_KT_HIST, (k_kt_fastq<C(), E()>), dim3(lane_group_grid<k_kt_fastq<C(), E()>>(h, q1 - q0, q.lpr)), dim3(BLOCK),
-                                  v.data, v.base, v.n, v.rlen, v.soff, Q.ids, q0, q1, Q.start, Q.end, q.lpr, (int)k, A);
-                    }
+                    walk_queries(h, u0, u1, [&](int64_t q0, int64_t q1) {
+                        FX_LAUNCH(h, E() ? K_KT_EMIT : K_KT_HIST, (k_kt_fastq<C(), E()>), dim3(lane_group_grid<k_kt_fastq<C(), E()>>(h, q1 - q0, b.q.lpr)), dim3(BLOCK),
+                                  v.data, v.base, v.n, v.rlen, v.soff, b.Q.ids, q0, q1, b.Q.start, b.Q.end, b.q.lpr, (int)k, A);
+                    });
                 });
             });
         };
@@ -5549,12 +5562,9 @@ template <class K> static unsigned ks_grid(fx_handle *h, K kern, size_t lds, int
     return (unsigned)std::min<int64_t>(want, (int64_t)per_cu * std::max(n_cu, 1));
 }
 
-// What the two FASTQ entries check, in the order of fx_fastq_kmer_table.
-static int ks_fastq_args(fx_handle *h, const fx_kmer_set *set, const int64_t *ids, int64_t n_ids, int64_t *first_bad, FqLaunch *q) {
-    int rc = fq_prepare(h, 0, 0, q);                           // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
-    if (rc) return rc;
+static int ks_same_device(fx_handle *h, const fx_kmer_set *set) {
     if (set->device != h->device) return fail(FX_EINVAL, "the k-mer set lives on device %d, the handle on device %d", set->device, h->device);
-    return check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
+    return FX_OK;
 }
 
 // n_windows / n_hits of n > 0 queries on the device: two int32 columns of one block, each from a 256-byte boundary.
@@ -5562,18 +5572,17 @@ struct KsCols {
     ScratchBuf<int32_t> dev;
     int32_t *nw = nullptr, *nh = nullptr;
 };
-static int ks_fastq_run(fx_handle *h, const fx_kmer_set *set, Staged &st, const FqLaunch &q, const int64_t *ids, int64_t n, const int64_t *start,
-                        const int64_t *end, int64_t *first_bad, KsCols &o) {
+static int ks_fastq_run(fx_handle *h, const fx_kmer_set *set, Staged &st, FqBatch &b, int64_t *first_bad, KsCols &o) {
     int rc;
-    FqQueries Q;
-    if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &Q))) return rc;
-    const FqView v = fq_view(h);
-    const int64_t stride = (n + 63) & ~(int64_t)63;
+    if ((rc = b.up(h, st, first_bad))) return rc;
+    const FqView &v = b.v;
+    const FqQueries &Q = b.Q;
+    const int64_t n = b.n, stride = (n + 63) & ~(int64_t)63;
     if ((rc = o.dev.alloc(h->device, 2 * stride, h->stream))) return rc;
     o.nw = o.dev.p; o.nh = o.dev.p + stride;
     const KsView S = set->view();
     const size_t lds = set->lds_bytes();
-    const int k = set->k, lpr = q.lpr;
+    const int k = set->k, lpr = b.q.lpr;
     with_bool(set->flags & FX_KMER_CANONICAL, [&](auto C) {
         with_bool(set->in_lds(), [&](auto L) {
             auto kern = k_ks_fastq<C(), L()>;
@@ -5590,17 +5599,16 @@ extern "C" int fx_fastq_kmer_hits(fx_handle *h, const fx_kmer_set *set, const in
     if (!h || !set || !n_windows || !n_hits || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     *n_windows = *n_hits = nullptr; *n_rows = 0; *first_bad = -1;
-    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
-    FqLaunch q;
-    int rc = ks_fastq_args(h, set, ids, n_ids, first_bad, &q);
-    if (rc) return rc;
-    const int64_t n = ids ? n_ids : h->n_reads;
+    FqBatch b{ids, n_ids, start, end};
+    int rc;
+    if ((rc = b.enter(h)) || (rc = ks_same_device(h, set)) || (rc = b.check(h, first_bad))) return rc;
+    const int64_t n = b.n;
     PinnedOut<2> out(h);
     auto pinned = [&] { return out.alloc(0, std::max<int64_t>(n, 1) * 4) && out.alloc(1, std::max<int64_t>(n, 1) * 4); };
     if (n > 0) {
         Staged st(h);
         KsCols o;
-        if ((rc = ks_fastq_run(h, set, st, q, ids, n, start, end, first_bad, o))) return rc;
+        if ((rc = ks_fastq_run(h, set, st, b, first_bad, o))) return rc;
         if (!pinned()) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n);
         if ((rc = home(h, "k-mer hits", {{out.p[0], o.nw, n * 4}, {out.p[1], o.nh, n * 4}}))) return rc;
     } else if (!pinned()) return fail(FX_ENOMEM, "pinned blocks");
@@ -5614,14 +5622,14 @@ extern "C" int fx_fastq_kmer_screen(fx_handle *h, const fx_kmer_set *set, const 
     if (!h || !set || !pos || !n_pos || !first_bad) return fail(FX_EINVAL, "null argument");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     *pos = nullptr; *n_pos = 0; *first_bad = -1;
-    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
+    FqBatch b{ids, n_ids, start, end};
+    int rc = b.args();                                     // (the numbers are looked at before the handle: enter in its two parts)
+    if (rc) return rc;
     const int64_t lim = 1000000000ll;
     if (min_hits < 0) return fail(FX_EINVAL, "min_hits %lld below 0", (long long)min_hits);
     if (frac_num < 0 || frac_num > lim || frac_den < 0 || frac_den > lim) return fail(FX_EINVAL, "a ratio outside 0..10^9");
-    FqLaunch q;
-    int rc = ks_fastq_args(h, set, ids, n_ids, first_bad, &q);
-    if (rc) return rc;
-    const int64_t n = ids ? n_ids : h->n_reads;
+    if ((rc = b.prepare(h)) || (rc = ks_same_device(h, set)) || (rc = b.check(h, first_bad))) return rc;
+    const int64_t n = b.n;
     int64_t total = 0;
     PinnedOut<1> out(h);
     if (n > 0) {
@@ -5629,7 +5637,7 @@ extern "C" int fx_fastq_kmer_screen(fx_handle *h, const fx_kmer_set *set, const 
         KsCols o;
         ScratchBuf<uint8_t> pass;
         int64_t *d_tot = nullptr;
-        if ((rc = ks_fastq_run(h, set, st, q, ids, n, start, end, first_bad, o))) return rc;
+        if ((rc = ks_fastq_run(h, set, st, b, first_bad, o))) return rc;
         if ((rc = pass.alloc(h->device, n, h->stream)) || (rc = st.scratch<int64_t>(1, &d_tot))) return rc;
         FX_LAUNCH(h, K_KS_SCREEN, k_ks_pass, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int32_t *)o.nw, (const int32_t *)o.nh, n, min_hits, frac_num, frac_den,
                   invert, pass.p);
@@ -5644,41 +5652,30 @@ extern "C" int fx_fasta_kmer_hits(fx_handle *h, const fx_kmer_set *set, const in
                                   int64_t *n_rows, int64_t *first_bad) {
     if (!h || !set || !n_windows || !n_hits || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
     *n_windows = *n_hits = nullptr; *n_rows = 0; *first_bad = -1;
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
-    if (set->device != h->device) return fail(FX_EINVAL, "the k-mer set lives on device %d, the handle on device %d", set->device, h->device);
-    int rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, first_bad, kBadRecord);
-    if (rc) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    int rc;
+    int64_t n_sel = 0;
+    if ((rc = fasta_state(h, "windows", ids, n_ids)) || (rc = ks_same_device(h, set)) || (rc = fasta_enter(h, ids, n_ids, first_bad, &n_sel))) return rc;
     PinnedOut<2> out(h);
     if (!out.alloc(0, std::max<int64_t>(n_sel, 1) * 8) || !out.alloc(1, std::max<int64_t>(n_sel, 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n_sel);
     if (n_sel > 0) {
         Staged st(h);
         st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
         const int k = set->k;
-        SearchPlan P;
-        P.masks = nullptr;
-        int64_t *d_tot = nullptr, n_runs = 0;
-        if ((rc = fasta_run_plan(h, st, K_KMER_SCAN, ids, n_ids, k, &P, &d_tot, &n_runs))) return rc;
+        HitRuns R;
+        if ((rc = R.open(h, st, K_KMER_SCAN, nullptr, k, ids, n_ids, 1, nullptr))) return rc;
         ScratchBuf<unsigned long long> acc;                  // a (windows, hits) pair per row
-        ScratchBuf<int64_t> cols, K;
-        ScratchBuf<uint32_t> packed;
+        ScratchBuf<int64_t> cols;
         if ((rc = acc.alloc(h->device, 2 * n_sel, h->stream)) || (rc = cols.alloc(h->device, 2 * n_sel, h->stream))) return rc;
         HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)n_sel * 16, h->stream));
-        if (n_runs > 0) {
-            // the kept bytes of every run and their scan: the cut at slen is known before the first window is looked up
-            if ((rc = packed.alloc(h->device, n_runs, h->stream)) || (rc = K.alloc(h->device, n_runs + 1, h->stream))) return rc;
-            FX_LAUNCH(h, K_KT_KEPT, k_kt_kept, dim3(nblocks(n_runs, BLOCK)), dim3(BLOCK), P, packed.p);
-            if ((rc = sscan<1>(h, st, K_KMER_SCAN, SrchLdKept{packed.p}, n_runs, K.p, d_tot))) return rc;
+        if (R.P.n_runs > 0) {
+            if ((rc = R.kept(h, st))) return rc;
             const KsView S = set->view();
             const size_t lds = set->lds_bytes();
             with_bool(set->flags & FX_KMER_CANONICAL, [&](auto C) {
                 with_bool(set->in_lds(), [&](auto L) {
                     auto kern = k_ks_fasta<C(), L()>;
-                    FX_LAUNCH_LDS(h, K_KS_FASTA, kern, dim3(ks_grid(h, kern, lds, nblocks(n_runs, BLOCK))), dim3(BLOCK), lds, P, k, (const int64_t *)K.p, S, acc.p);
+                    FX_LAUNCH_LDS(h, K_KS_FASTA, kern, dim3(ks_grid(h, kern, lds, nblocks(R.P.n_runs, BLOCK))), dim3(BLOCK), lds, R.P, k, (const int64_t *)R.pref.p, S,
+                                  acc.p);
                 });
             });
         }
@@ -5950,14 +5947,8 @@ extern "C" int fx_fasta_sketch(fx_handle *h, int32_t k, int flags, const int64_t
     if (!rc) rc = sketch_oversample(oversample);
     if (rc) return rc;
     if (!h || !sk || !n_rounds) return fail(FX_EINVAL, "null argument");
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    if (!h->fasta_built) return fail(FX_ESTATE, "fx_fasta_build has not run");
-    if (h->base != 0 || h->halo != 0) return fail(FX_EINVAL, "a byte-range shard carries no halo for windows across its cuts");
-    rc = use_device(h);
-    if (!rc) rc = finish_build(h);
-    if (!rc) rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord);
-    if (rc) return rc;
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    int64_t n_sel = 0;
+    if ((rc = fasta_state(h, "windows", ids, n_ids)) || (rc = fasta_enter(h, ids, n_ids, nullptr, &n_sel))) return rc;
     const int pooled = (flags & FX_SK_POOLED) ? 1 : 0;
     const SkShape p{(int)k, flags, max_key, size, oversample ? (int)oversample : 4, pooled ? 1 : n_sel};
     if (n_sel == 0) return sketch_empty(h, k, flags, max_key, size, p.n_sets, sk, n_rounds);
@@ -5965,7 +5956,7 @@ extern "C" int fx_fasta_sketch(fx_handle *h, int32_t k, int flags, const int64_t
     Staged st(h);
     st.reserve_pin((ids ? n_ids : 0) * 8 + 512);
     HitRuns R;
-    if ((rc = R.open(h, st, nullptr, k, ids, n_ids, 2, nullptr))) return rc;
+    if ((rc = R.open(h, st, K_SEARCH_SCAN, nullptr, k, ids, n_ids, 2, nullptr))) return rc;
     if (R.P.n_runs == 0) return sketch_empty(h, k, flags, max_key, size, p.n_sets, sk, n_rounds);
     SkState S;
     if ((rc = S.alloc(h, p.n_sets))) return rc;
@@ -6012,17 +6003,16 @@ extern "C" int fx_fastq_sketch(fx_handle *h, int32_t k, int flags, const int64_t
     if (rc) return rc;
     if (!h || !sk || !n_rounds || !first_bad) return fail(FX_EINVAL, "null argument");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
-    FqLaunch q;
-    if ((rc = fq_prepare(h, 0, 0, &q))) return rc;             // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
-    const int64_t n = ids ? n_ids : h->n_reads;
-    if ((rc = check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead))) return rc;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");      // (stricter than FqBatch::args: a count needs its array)
+    FqBatch b{ids, n_ids, start, end};
+    if ((rc = b.prepare(h)) || (rc = b.check(h, first_bad))) return rc;
+    const int64_t n = b.n;
     const SkShape p{(int)k, flags | FX_SK_POOLED, max_key, size, oversample ? (int)oversample : 4, 1};
     if (n == 0) return sketch_empty(h, k, p.flags, max_key, size, 1, sk, n_rounds);
     Staged st(h);
     SkState S;
-    SkFastqSrc src{h, S, fq_view(h), {}, n, q.lpr, (int)k, (flags & FX_SK_CANONICAL) != 0, nullptr};
-    if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &src.Q))) return rc;
+    if ((rc = b.up(h, st, first_bad))) return rc;
+    SkFastqSrc src{h, S, b.v, b.Q, n, b.q.lpr, (int)k, (flags & FX_SK_CANONICAL) != 0, nullptr};
     int64_t *d_tot = nullptr;
     if ((rc = S.alloc(h, 1)) || (rc = st.scratch<int64_t>(8, &d_tot)) || (rc = st.scratch<unsigned long long>(1, &src.cursor))) return rc;
     FX_LAUNCH(h, K_SK_SCAN, k_sk_letters_fq, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)h->fq_rlen.p, src.Q.ids, n, src.Q.start, src.Q.end, S.W.p);
@@ -6164,25 +6154,20 @@ struct DdWork {
     }
 };
 
-// What the two entries check before anything is allocated, in the order of the screening entries; then the queries on the device.
-struct DdArgs { FqLaunch q; int64_t n; FqQueries Q; };
-static int dd_check(fx_handle *h, const int64_t *ids, int64_t n_ids, int flags, int hash_bits, int64_t min_copies, int64_t *first_bad, DdArgs *a) {
-    if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
-    int rc = fq_prepare(h, 0, 0, &a->q);                       // FX_ESTATE before the build, FX_EINVAL on a shard, FX_EDEVICE without a device
-    if (rc) return rc;
+// What the numbers of the two entries decide, between the batch's enter and check (n: its queries).
+static int dd_args(int flags, int hash_bits, int64_t min_copies, int64_t n) {
     if (flags & ~FX_DUP_REVCOMP) return fail(FX_EINVAL, "unknown flag bits %d", flags);
     if (hash_bits < 0 || hash_bits > 64) return fail(FX_EINVAL, "hash_bits %d outside 0..64", hash_bits);
     if (min_copies < 1) return fail(FX_EINVAL, "min_copies %lld below 1", (long long)min_copies);
-    a->n = ids ? n_ids : h->n_reads;
-    if (a->n > DD_MAX_QUERIES) return fail(FX_EINVAL, "%lld queries, more than the 2^31 the sort carries positions for", (long long)a->n);
-    return check_ids(ids, n_ids, h->n_reads, first_bad, kBadRead);
+    if (n > DD_MAX_QUERIES) return fail(FX_EINVAL, "%lld queries, more than the 2^31 the sort carries positions for", (long long)n);
+    return FX_OK;
 }
 
 // first (and copies) of a.n > 0 queries on the device: the rounds of fx_fastq_dedup.hpp.  Nothing waits in here but the sort's
 // passes and the two totals of a round.
-static int dd_run(fx_handle *h, const DdArgs &a, int flags, int hash_bits, bool want_copies, DdWork &w, int64_t *n_groups, int64_t *n_rounds) {
+static int dd_run(fx_handle *h, const FqBatch &a, int flags, int hash_bits, bool want_copies, DdWork &w, int64_t *n_groups, int64_t *n_rounds) {
     int rc;
-    const FqView v = fq_view(h);
+    const FqView &v = a.v;
     const int lpr = a.q.lpr, bits = hash_bits ? hash_bits : 64;
     const uint64_t mask = bits == 64 ? ~0ull : (1ull << bits) - 1ull;
     const bool revcomp = flags & FX_DUP_REVCOMP;
@@ -6239,15 +6224,15 @@ extern "C" int fx_fastq_dup_first(fx_handle *h, const int64_t *ids, int64_t n_id
     if (!h || !first || !n_rows || !n_groups || !n_rounds || !first_bad) return fail(FX_EINVAL, "null argument");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     *first = nullptr; *n_rows = *n_groups = *n_rounds = 0; *first_bad = -1;
-    DdArgs a;
-    int rc = dd_check(h, ids, n_ids, flags, hash_bits, 1, first_bad, &a);
-    if (rc) return rc;
+    FqBatch a{ids, n_ids, start, end};
+    int rc;
+    if ((rc = a.enter(h)) || (rc = dd_args(flags, hash_bits, 1, a.n)) || (rc = a.check(h, first_bad))) return rc;
     const int64_t n = a.n;
     PinnedOut<1> out(h);
     if (n > 0) {
         Staged st(h);
         DdWork w;
-        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &a.Q)) || (rc = w.alloc(h, st, n, false))) return rc;
+        if ((rc = a.up(h, st, first_bad)) || (rc = w.alloc(h, st, n, false))) return rc;
         if (!out.alloc(0, n * 8)) return fail(FX_ENOMEM, "pinned block for %lld rows", (long long)n);
         if ((rc = dd_run(h, a, flags, hash_bits, false, w, n_groups, n_rounds)) || (rc = home(h, "duplicates", {{out.p[0], w.first.p, n * 8}}))) {
             *n_groups = *n_rounds = 0;
@@ -6266,9 +6251,9 @@ extern "C" int fx_fastq_dedup(fx_handle *h, const int64_t *ids, int64_t n_ids, c
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     *pos = nullptr; *n_pos = *n_groups = *n_rounds = 0; *first_bad = -1;
     if (copies) *copies = nullptr;
-    DdArgs a;
-    int rc = dd_check(h, ids, n_ids, flags, hash_bits, min_copies, first_bad, &a);
-    if (rc) return rc;
+    FqBatch a{ids, n_ids, start, end};
+    int rc;
+    if ((rc = a.enter(h)) || (rc = dd_args(flags, hash_bits, min_copies, a.n)) || (rc = a.check(h, first_bad))) return rc;
     const int64_t n = a.n;
     int64_t total = 0;
     PinnedOut<2> out(h);
@@ -6277,7 +6262,7 @@ extern "C" int fx_fastq_dedup(fx_handle *h, const int64_t *ids, int64_t n_ids, c
         DdWork w;
         ScratchBuf<uint8_t> pass;
         int64_t groups = 0, rounds = 0;
-        if ((rc = fq_queries(h, st, ids, n, start, end, first_bad, &a.Q)) || (rc = w.alloc(h, st, n, true)) ||
+        if ((rc = a.up(h, st, first_bad)) || (rc = w.alloc(h, st, n, true)) ||
             (rc = pass.alloc(h->device, n, h->stream)) || (rc = dd_run(h, a, flags, hash_bits, true, w, &groups, &rounds)))
             return rc;
         FX_LAUNCH(h, K_DD_SELECT, k_dd_pass, dim3(nblocks(n, BLOCK)), dim3(BLOCK), (const int64_t *)w.first.p, (const uint32_t *)w.copies.p, n, min_copies,
