@@ -49,15 +49,162 @@ class ShardSummary(C.Structure):
         "tail_elen", "tail_dlen", "tail_name_len", "lead_prev_nl", "second_last_nl")]
 
 
-SYMBOLS = [
-    "fx_last_error", "fx_version", "fx_device_count", "fx_open_file", "fx_open_laps", "fx_build_laps", "fx_open_file_indexed", "fx_gz_checkpoints", "fx_stream_size", "fx_open_file_range", "fx_open_host", "fx_open_device",
-    "fx_set_shard", "fx_close", "fx_release_scratch", "fx_pinned_alloc", "fx_pinned_free", "fx_pinned_holds", "fx_pinned_trim", "fx_size", "fx_device_memory", "fx_is_gzip", "fx_device_ptr", "fx_read_bytes", "fx_first_byte",
-    "fx_fasta_build", "fx_fasta_build_begin", "fx_fasta_build_end", "fx_fasta_table", "fx_fasta_set_table", "fx_fasta_line_regular", "fx_fasta_len_stats", "fx_fasta_comp", "fx_fasta_comp_shard", "fx_fasta_comp_sparse", "fx_fastq_build", "fx_fastq_build_comp", "fx_fastq_comp_info", "fx_set_halo", "fx_fastq_scan", "fx_fastq_build_ctx", "fx_fastq_table", "fx_fastq_comp",
-    "fx_fetch_ranges", "fx_fetch_slices", "fx_fetch_one", "fx_fasta_fetch", "fx_fasta_fetch_alloc", "fx_fasta_search", "fx_fasta_search_approx", "fx_fasta_pwm_scan", "fx_fasta_pwm_best", "fx_fasta_minimizers", "fx_fasta_rank_build", "fx_fasta_rank_free", "fx_fasta_region_counts", "fx_fasta_window_counts", "fx_fasta_class_runs", "fx_fasta_tandem_repeats", "fx_fasta_orfs", "fx_fasta_translate_alloc", "fx_fetch_phases", "fx_fastq_fetch", "fx_fastq_fetch_alloc", "fx_fastq_read_stats", "fx_fastq_cycle_hist", "fx_fastq_select", "fx_fastq_trim", "fx_fastq_format_alloc", "fx_fastq_demux", "fx_fastq_pair_overlap", "fx_fastq_pair_merge_alloc", "fx_fasta_kmers", "fx_fastq_kmers", "fx_fasta_kmer_table", "fx_fastq_kmer_table", "fx_kmer_set_create", "fx_kmer_set_free", "fx_kmer_set_contains", "fx_fastq_kmer_hits", "fx_fastq_kmer_screen", "fx_fasta_kmer_hits", "fx_fasta_sketch", "fx_fastq_sketch", "fx_sketch_info", "fx_sketch_read", "fx_sketch_from_host", "fx_sketch_compare", "fx_sketch_free", "fx_fastq_dup_first", "fx_fastq_dedup", "fx_names_build", "fx_names_lookup", "fx_names_sort", "fx_names_pack", "fx_revcomp", "fx_shard_summary_get",
-    "fx_fasta_set_row", "fx_shard_route", "fx_shard_summary_dev", "fx_fasta_stitch_dev", "fx_stream", "fx_read_fetch", "fx_gz_points", "fx_fxi_bulk_rows", "fx_fxi_bulk_index", "fx_fxi_bulk_index_int", "fx_fxi_dev_sort", "fx_fxi_dev_write", "fx_fxi_dev_build", "fx_fxi_presize_begin", "fx_fxi_presize_end", "fx_fxi_part_shape", "fx_fxi_part_firsts", "fx_fxi_part_names", "fx_fxi_part_leaves", "fx_fxi_join_grow", "fx_fxi_join_begin", "fx_fxi_join_write", "fx_fxi_join_end", "fx_scratch_policy", "fx_open_file_async", "fx_stage_wait", "fx_sync", "fx_prof_default", "fx_prof_enable", "fx_prof_reset", "fx_prof_count", "fx_prof_name", "fx_prof_read",
-    "fx_comm_unique_id", "fx_comm_init", "fx_comm_destroy", "fx_comm_rank", "fx_comm_world", "fx_comm_allgather", "fx_fasta_build_sharded_begin",
-    "fx_fasta_build_sharded", "fx_comm_summaries", "fx_fastq_build_sharded", "fx_bgzf_counts", "fx_sort_packed_names", "fx_gunzip_parallel", "fx_gz_open_mode", "fx_kseq_scan", "fx_kseq_records", "fx_kseq_fetch", "fx_kseq_prefix_lines",
-]
+vp, cs, i32, i64, u8, u64, f64, P = C.c_void_p, C.c_char_p, C.c_int, C.c_int64, C.c_uint8, C.c_uint64, C.c_double, C.POINTER
+pvp, pi32, pi64, pf64 = P(vp), P(i32), P(i64), P(f64)
+
+# Every entry of include/fxgpu.h: name -> (return type, argument types).  The one place a new entry is declared: lib() sets
+# these on the loaded library, SYMBOLS is its keys, and tests/test_cabi.py holds every line against the header's prototype.
+PROTOTYPES = {
+    "fx_last_error": (cs, []),
+    "fx_version": (cs, []),
+    "fx_device_count": (i32, []),
+    "fx_open_file": (i32, [cs, i32, pvp]),
+    "fx_open_laps": (i32, [pf64, pf64]),
+    "fx_build_laps": (i32, [pf64]),
+    "fx_open_file_indexed": (i32, [cs, i32, i64, vp, vp, vp, vp, vp, i64, pvp]),
+    "fx_gz_checkpoints": (i32, [vp, i64, vp, vp, vp, vp, vp, pi64, pi64]),
+    "fx_stream_size": (i32, [cs, pi64, pi32]),
+    "fx_open_file_range": (i32, [cs, i64, i64, i64, i32, pvp]),
+    "fx_open_host": (i32, [vp, i64, i32, pvp]),
+    "fx_open_device": (i32, [vp, i64, i32, pvp]),
+    "fx_set_shard": (i32, [vp, i64, i32, i32]),
+    "fx_close": (i32, [vp]),
+    "fx_release_scratch": (i32, []),
+    "fx_pinned_alloc": (vp, [i64]),
+    "fx_pinned_free": (None, [vp]),
+    "fx_pinned_holds": (i32, [vp, i64]),
+    "fx_pinned_trim": (i32, []),
+    "fx_size": (i64, [vp]),
+    "fx_device_memory": (i32, [i32, pi64, pi64]),
+    "fx_is_gzip": (i32, [vp]),
+    "fx_device_ptr": (vp, [vp]),
+    "fx_read_bytes": (i32, [vp, i64, i64, vp]),
+    "fx_first_byte": (i32, [vp, pi32]),
+    "fx_fasta_build": (i32, [vp, i32, P(FastaSummary)]),
+    "fx_fasta_build_begin": (i32, [vp, i32]),
+    "fx_fasta_build_end": (i32, [vp, P(FastaSummary)]),
+    "fx_fasta_table": (i32, [vp, i32] + [vp] * 9),
+    "fx_fasta_set_table": (i32, [vp, i64] + [vp] * 6),
+    "fx_fasta_line_regular": (i32, [vp, i32, vp]),
+    "fx_fasta_len_stats": (i32, [vp, i64, f64, P(LenStats)]),
+    "fx_fasta_comp": (i32, [vp, i32, vp]),
+    "fx_fasta_comp_shard": (i32, [vp, i32, vp, i64, vp]),
+    "fx_fasta_comp_sparse": (i32, [vp, i32, i64, vp, vp, vp, pi64, vp]),
+    "fx_fastq_build": (i32, [vp, P(FastqSummary)]),
+    "fx_fastq_build_comp": (i32, [vp, P(FastqSummary)]),
+    "fx_fastq_comp_info": (i32, [vp, pi64, pi64, pi32]),
+    "fx_set_halo": (i32, [vp, i64]),
+    "fx_fastq_scan": (i32, [vp, pi64, pi64]),
+    "fx_fastq_build_ctx": (i32, [vp, i64, i64, P(FastqSummary)]),
+    "fx_fastq_table": (i32, [vp, i32] + [vp] * 6),
+    "fx_fastq_comp": (i32, [vp, vp, vp]),
+    "fx_fetch_ranges": (i32, [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "fx_fetch_slices": (i32, [vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "fx_fetch_one": (i32, [vp, i64, i64, i64, i64, i32, vp, pi64]),
+    "fx_fasta_fetch": (i32, [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "fx_fasta_fetch_alloc": (i32, [vp, i64, vp, vp, vp, i32, vp, pvp, pvp, pi64]),
+    "fx_fasta_search": (i32, [vp, vp, vp, i32, i32, vp, i64, i64, pvp, pvp, pvp, pi64, vp]),
+    "fx_fasta_search_approx": (i32, [vp, vp, vp, i32, i32, i32, u64, vp, i64, i64, pvp, pvp, pvp, pvp, pi64, vp]),
+    "fx_fasta_pwm_scan": (i32, [vp, vp, i32, i32, i32, vp, i64, i64, pvp, pvp, pvp, pvp, pi64, vp]),
+    "fx_fasta_pwm_best": (i32, [vp, vp, i32, i32, vp, i64, vp, vp]),
+    "fx_fasta_minimizers": (i32, [vp, i32, i32, i32, vp, i64, i64, pvp, pvp, pvp, pvp, pi64, vp]),
+    "fx_fasta_rank_build": (i32, [vp]),
+    "fx_fasta_rank_free": (i32, [vp]),
+    "fx_fasta_region_counts": (i32, [vp, i32, i64, vp, vp, vp, vp, pi64]),
+    "fx_fasta_window_counts": (i32, [vp, vp, i64, i64, i64, i32, i64] + [pvp] * 4 + [pi64]),
+    "fx_fasta_class_runs": (i32, [vp, vp, i64, vp, i64, i64] + [pvp] * 3 + [pi64] * 2),
+    "fx_fasta_tandem_repeats": (i32, [vp, vp, i32, i64, vp, i64, i64] + [pvp] * 5 + [pi64] * 2),
+    "fx_fasta_orfs": (i32, [vp, u64, u64, i32, i32, i64, vp, i64, i64] + [pvp] * 5 + [pi64] * 2),
+    "fx_fasta_translate_alloc": (i32, [vp, i64, vp, vp, vp, vp, vp, u8, pvp, pvp, pi64]),
+    "fx_fetch_phases": (i32, [pf64, i32]),
+    "fx_fastq_fetch": (i32, [vp, i32, i64, vp, i32, i32, vp, vp, vp, vp]),
+    "fx_fastq_fetch_alloc": (i32, [vp, i64, vp, i32, i32, i32, pvp, pvp, pvp, pvp, pi64]),
+    "fx_fastq_read_stats": (i32, [vp, vp, i64, i32, i32] + [pvp] * 7 + [pi64, pi64]),
+    "fx_fastq_cycle_hist": (i32, [vp, i32, pvp, pvp, pvp]),
+    "fx_fastq_select": (i32, [vp, i32, i32, i64, i64, i64, i64, i64, i64, i64, pvp, pi64]),
+    "fx_fastq_trim": (i32, [vp, vp, i64, i32, i64, i64, vp, i32, i32, i64, i64, i32, i32, i64, i64, i32, pvp, pvp, pi64, pi64]),
+    "fx_fastq_format_alloc": (i32, [vp, vp, i64, vp, vp, i64, pvp, pvp, pi64, pi64, pi64]),
+    "fx_fastq_demux": (i32, [vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, i32] + [pvp] * 6 + [pi64, pi64]),
+    "fx_fastq_pair_overlap": (i32, [vp, vp, vp, i64, i32, i32, i64, i64, pvp, pvp, pvp, pvp, pvp, pi64, pi64]),
+    "fx_fastq_pair_merge_alloc": (i32, [vp, vp, vp, i64, vp, i64, pvp, pvp, pi64, pi64, pi64]),
+    "fx_fasta_kmers": (i32, [vp, i32, i32, vp, i64, i32, pvp, pi64, pi64]),
+    "fx_fastq_kmers": (i32, [vp, i32, i32, vp, i64, vp, vp, pvp, pi64]),
+    "fx_fasta_kmer_table": (i32, [vp, i32, i32, vp, i64, i64, i64] + [pvp] * 2 + [pi64] * 4),
+    "fx_fastq_kmer_table": (i32, [vp, i32, i32, vp, i64, vp, vp, i64, i64] + [pvp] * 2 + [pi64] * 4),
+    "fx_kmer_set_create": (i32, [vp, i32, i32, vp, i64, pvp]),
+    "fx_kmer_set_free": (i32, [vp]),
+    "fx_kmer_set_contains": (i32, [vp, vp, i64, vp]),
+    "fx_fastq_kmer_hits": (i32, [vp, vp, vp, i64, vp, vp, pvp, pvp, pi64, pi64]),
+    "fx_fastq_kmer_screen": (i32, [vp, vp, vp, i64, vp, vp, i64, i64, i64, i32, pvp, pi64, pi64]),
+    "fx_fasta_kmer_hits": (i32, [vp, vp, vp, i64, pvp, pvp, pi64, pi64]),
+    "fx_fasta_sketch": (i32, [vp, i32, i32, vp, i64, u64, i64, i32, pvp, pi32]),
+    "fx_fastq_sketch": (i32, [vp, i32, i32, vp, i64, vp, vp, u64, i64, i32, pvp, pi32, pi64]),
+    "fx_sketch_info": (i32, [vp, pi32, pi32, P(u64), pi64, pi64, pi64]),
+    "fx_sketch_read": (i32, [vp, pvp, pvp]),
+    "fx_sketch_from_host": (i32, [i32, i32, i32, u64, i64, i64, vp, vp, pvp]),
+    "fx_sketch_compare": (i32, [vp, vp, vp, i64, vp, i64, i64, u64, i64, pvp, pvp]),
+    "fx_sketch_free": (i32, [vp]),
+    "fx_fastq_dup_first": (i32, [vp, vp, i64, vp, vp, i32, i32, pvp, pi64, pi64, pi64, pi64]),
+    "fx_fastq_dedup": (i32, [vp, vp, i64, vp, vp, i32, i32, i64, i64, pvp, pvp, pi64, pi64, pi64, pi64]),
+    "fx_names_build": (i32, [vp, i32]),
+    "fx_names_lookup": (i32, [vp, i32, i64, vp, vp, vp]),
+    "fx_names_sort": (i32, [vp, i32, i32, vp, pi64]),
+    "fx_names_pack": (i32, [vp, i32, vp, i64, vp, pi64]),
+    "fx_revcomp": (i32, [i32, i32, vp, i64, i32]),
+    "fx_shard_summary_get": (i32, [vp, P(ShardSummary)]),
+    "fx_fasta_set_row": (i32, [vp, i64, i64, i64, i64, i64, i32, i32, i32, i32]),
+    "fx_shard_route": (i32, [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp] + [vp] * 8),
+    "fx_shard_summary_dev": (i32, [vp, vp]),
+    "fx_fasta_stitch_dev": (i32, [vp, vp, i32, i32, i32]),
+    "fx_stream": (vp, [vp]),
+    "fx_read_fetch": (i32, [vp, i32, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "fx_gz_points": (i32, [vp, i64, vp, vp, i64, pi64, pi64]),
+    "fx_fxi_bulk_rows": (i32, [cs, i32, i64, vp, vp, i32, vp]),
+    "fx_fxi_bulk_index": (i32, [cs, i32, i64, vp, vp, vp]),
+    "fx_fxi_bulk_index_int": (i32, [cs, i32, i64, vp, vp]),
+    "fx_fxi_dev_sort": (i32, [vp, i32, pi64]),
+    "fx_fxi_dev_write": (i32, [vp, i32, cs, i32, i32, pf64]),
+    "fx_fxi_dev_build": (i32, [vp, i32, cs, i32, i32, pi64, pf64]),
+    "fx_fxi_presize_begin": (i32, [cs, i64, i32, pvp]),
+    "fx_fxi_presize_end": (i32, [vp, i32]),
+    "fx_fxi_part_shape": (i32, [vp, i32, i64, pi64]),
+    "fx_fxi_part_firsts": (i32, [vp, vp]),
+    "fx_fxi_part_names": (i32, [vp, i32, vp, vp]),
+    "fx_fxi_part_leaves": (i32, [vp, i32, cs, i64, i64, pf64]),
+    "fx_fxi_join_grow": (i32, [cs, i32, i64, i64, i32, pi64]),
+    "fx_fxi_join_begin": (i32, [i32, vp, vp, i64, pvp, pi64]),
+    "fx_fxi_join_write": (i32, [vp, cs, i32, i32, i64, i64, vp, i64, pf64]),
+    "fx_fxi_join_end": (None, [vp]),
+    "fx_scratch_policy": (i32, [vp, i32, i64, i64, vp]),
+    "fx_open_file_async": (i32, [cs, i32, pvp]),
+    "fx_stage_wait": (i32, [vp, i64]),
+    "fx_sync": (i32, [vp]),
+    "fx_prof_default": (i32, [i32]),
+    "fx_prof_enable": (i32, [vp, i32]),
+    "fx_prof_reset": (i32, [vp]),
+    "fx_prof_count": (i32, []),
+    "fx_prof_name": (cs, [i32]),
+    "fx_prof_read": (i32, [vp, i32, pf64, pi64]),
+    "fx_comm_unique_id": (i32, [vp]),
+    "fx_comm_init": (i32, [i32, i32, vp, i32, pvp]),
+    "fx_comm_destroy": (i32, [vp]),
+    "fx_comm_rank": (i32, [vp]),
+    "fx_comm_world": (i32, [vp]),
+    "fx_comm_allgather": (i32, [vp, vp, vp, i64]),
+    "fx_fasta_build_sharded_begin": (i32, [vp, vp, i32]),
+    "fx_fasta_build_sharded": (i32, [vp, vp, i32, vp]),
+    "fx_comm_summaries": (i32, [vp, vp, vp]),
+    "fx_fastq_build_sharded": (i32, [vp, vp, vp]),
+    "fx_bgzf_counts": (i32, [vp, vp]),
+    "fx_sort_packed_names": (i32, [i32, vp, vp, i64, vp, pi64]),
+    "fx_gunzip_parallel": (i32, [vp, i64, i32, vp, i64, pi64, pi64]),
+    "fx_gz_open_mode": (i32, [vp]),
+    "fx_kseq_scan": (i32, [vp, vp, vp, vp, vp]),
+    "fx_kseq_records": (i32, [vp, i64, i64, vp]),
+    "fx_kseq_fetch": (i32, [vp, i32, i64, i64, i32, vp, vp, vp]),
+    "fx_kseq_prefix_lines": (i64, [vp]),
+}
+SYMBOLS = list(PROTOTYPES)
 
 
 def so_path():
@@ -176,170 +323,11 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(_SO, mode=C.RTLD_GLOBAL)
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-    L.fx_last_error.restype = C.c_char_p
-    L.fx_version.restype = C.c_char_p
-    L.fx_device_count.restype = i32
-    L.fx_open_file.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
-    L.fx_open_host.argtypes = [vp, i64, i32, C.POINTER(vp)]
-    L.fx_stream_size.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i32)]
-    L.fx_open_file_indexed.argtypes = [C.c_char_p, i32, i64, vp, vp, vp, vp, vp, i64, C.POINTER(vp)]
-    L.fx_gz_checkpoints.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]
-    L.fx_open_file_range.argtypes = [C.c_char_p, i64, i64, i64, i32, C.POINTER(vp)]
-    L.fx_open_device.argtypes = [vp, i64, i32, C.POINTER(vp)]
-    L.fx_shard_route.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp] + [vp] * 8
-    L.fx_set_shard.argtypes = [vp, i64, i32, i32]
-    L.fx_close.argtypes = [vp]
-    L.fx_size.restype = i64
-    L.fx_size.argtypes = [vp]
-    L.fx_is_gzip.argtypes = [vp]
-    L.fx_device_memory.argtypes = [i32, C.POINTER(i64), C.POINTER(i64)]
-    L.fx_device_ptr.restype = vp
-    L.fx_device_ptr.argtypes = [vp]
-    L.fx_read_bytes.argtypes = [vp, i64, i64, vp]
-    L.fx_first_byte.argtypes = [vp, C.POINTER(i32)]
-    L.fx_fasta_build.argtypes = [vp, i32, C.POINTER(FastaSummary)]
-    L.fx_fasta_build_begin.argtypes = [vp, i32]
-    L.fx_fasta_build_end.argtypes = [vp, C.POINTER(FastaSummary)]
-    L.fx_fasta_table.argtypes = [vp, i32] + [vp] * 9
-    L.fx_fasta_set_table.argtypes = [vp, i64] + [vp] * 6
-    L.fx_fasta_line_regular.argtypes = [vp, i32, vp]
-    L.fx_fasta_len_stats.argtypes = [vp, i64, C.c_double, C.POINTER(LenStats)]
-    L.fx_fasta_comp.argtypes = [vp, i32, vp]
-    L.fx_fasta_comp_shard.argtypes = [vp, i32, vp, i64, vp]
-    L.fx_fasta_comp_sparse.argtypes = [vp, i32, i64, vp, vp, vp, C.POINTER(i64), vp]
-    L.fx_fastq_build.argtypes = [vp, C.POINTER(FastqSummary)]
-    L.fx_fastq_build_comp.argtypes = [vp, C.POINTER(FastqSummary)]
-    L.fx_fastq_table.argtypes = [vp, i32] + [vp] * 6
-    L.fx_set_halo.argtypes = [vp, i64]
-    L.fx_fastq_scan.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_build_ctx.argtypes = [vp, i64, i64, C.POINTER(FastqSummary)]
-    L.fx_fastq_comp.argtypes = [vp, vp, vp]
-    L.fx_fetch_one.argtypes = [vp, i64, i64, i64, i64, i32, vp, C.POINTER(i64)]
-    L.fx_fetch_ranges.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.fx_fasta_fetch.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.fx_fetch_slices.argtypes = [vp, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.fx_fastq_fetch.argtypes = [vp, i32, i64, vp, i32, i32, vp, vp, vp, vp]
-    L.fx_pinned_alloc.restype = vp
-    L.fx_pinned_alloc.argtypes = [i64]
-    L.fx_pinned_free.restype = None
-    L.fx_pinned_free.argtypes = [vp]
-    L.fx_pinned_holds.argtypes = [vp, i64]
-    L.fx_fasta_fetch_alloc.argtypes = [vp, i64, vp, vp, vp, i32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
-    L.fx_fasta_search.argtypes = [vp, vp, vp, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp]
-    L.fx_fasta_search_approx.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                         C.POINTER(vp), C.POINTER(i64), vp]
-    L.fx_fasta_pwm_scan.argtypes = [vp, vp, i32, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                    C.POINTER(i64), vp]
-    L.fx_fasta_pwm_best.argtypes = [vp, vp, i32, i32, vp, i64, vp, vp]
-    L.fx_fasta_minimizers.argtypes = [vp, i32, i32, i32, vp, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                      C.POINTER(i64), vp]
-    L.fx_fasta_rank_build.argtypes = [vp]
-    L.fx_fasta_rank_free.argtypes = [vp]
-    L.fx_fasta_region_counts.argtypes = [vp, i32, i64, vp, vp, vp, vp, C.POINTER(i64)]
-    L.fx_fasta_window_counts.argtypes = [vp, vp, i64, i64, i64, i32, i64] + [C.POINTER(vp)] * 4 + [C.POINTER(i64)]
-    L.fx_fasta_class_runs.argtypes = [vp, vp, i64, vp, i64, i64] + [C.POINTER(vp)] * 3 + [C.POINTER(i64)] * 2
-    L.fx_fasta_tandem_repeats.argtypes = [vp, vp, C.c_int32, i64, vp, i64, i64] + [C.POINTER(vp)] * 5 + [C.POINTER(i64)] * 2
-    L.fx_fasta_orfs.argtypes = [vp, C.c_uint64, C.c_uint64, i32, i32, i64, vp, i64, i64] + [C.POINTER(vp)] * 5 + [C.POINTER(i64)] * 2
-    L.fx_fasta_translate_alloc.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.c_uint8, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
-    L.fx_fastq_fetch_alloc.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
-    L.fx_fetch_phases.argtypes = [C.POINTER(C.c_double), i32]
-    L.fx_fastq_read_stats.argtypes = [vp, vp, i64, i32, i32] + [C.POINTER(vp)] * 7 + [C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_cycle_hist.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
-    L.fx_fastq_select.argtypes = [vp, i32, i32, i64, i64, i64, i64, i64, i64, i64, C.POINTER(vp), C.POINTER(i64)]
-    L.fx_fastq_trim.argtypes = [vp, vp, i64, i32, i64, i64, vp, i32, i32, i64, i64, i32, i32, i64, i64, i32,
-                                C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_format_alloc.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_demux.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, i32] + [C.POINTER(vp)] * 6 + [C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_pair_overlap.argtypes = [vp, vp, vp, i64, i32, i32, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                        C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_pair_merge_alloc.argtypes = [vp, vp, vp, i64, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fasta_kmers.argtypes = [vp, i32, i32, vp, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_kmers.argtypes = [vp, i32, i32, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(i64)]
-    L.fx_fasta_kmer_table.argtypes = [vp, i32, i32, vp, i64, i64, i64] + [C.POINTER(vp)] * 2 + [C.POINTER(i64)] * 4
-    L.fx_fastq_kmer_table.argtypes = [vp, i32, i32, vp, i64, vp, vp, i64, i64] + [C.POINTER(vp)] * 2 + [C.POINTER(i64)] * 4
-    L.fx_kmer_set_create.argtypes = [vp, i32, i32, vp, i64, C.POINTER(vp)]
-    L.fx_kmer_set_free.argtypes = [vp]
-    L.fx_kmer_set_contains.argtypes = [vp, vp, i64, vp]
-    u64 = C.c_uint64
-    L.fx_fasta_sketch.argtypes = [vp, i32, i32, vp, i64, u64, i64, i32, C.POINTER(vp), C.POINTER(i32)]
-    L.fx_fastq_sketch.argtypes = [vp, i32, i32, vp, i64, vp, vp, u64, i64, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64)]
-    L.fx_sketch_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_sketch_read.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
-    L.fx_sketch_from_host.argtypes = [i32, i32, i32, u64, i64, i64, vp, vp, C.POINTER(vp)]
-    L.fx_sketch_compare.argtypes = [vp, vp, vp, i64, vp, i64, i64, u64, i64, C.POINTER(vp), C.POINTER(vp)]
-    L.fx_sketch_free.argtypes = [vp]
-    L.fx_fastq_kmer_hits.argtypes = [vp, vp, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_kmer_screen.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fasta_kmer_hits.argtypes = [vp, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_dup_first.argtypes = [vp, vp, i64, vp, vp, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
-    L.fx_fastq_dedup.argtypes = [vp, vp, i64, vp, vp, i32, i32, i64, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
-                                 C.POINTER(i64)]
-    L.fx_names_build.argtypes = [vp, i32]
-    L.fx_names_lookup.argtypes = [vp, i32, i64, vp, vp, vp]
-    L.fx_revcomp.argtypes = [i32, i32, vp, i64, i32]
-    L.fx_read_fetch.argtypes = [vp, i32, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.fx_shard_summary_get.argtypes = [vp, C.POINTER(ShardSummary)]
-    L.fx_fasta_set_row.argtypes = [vp, i64, i64, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    L.fx_shard_summary_dev.argtypes = [vp, vp]
-    L.fx_fasta_stitch_dev.argtypes = [vp, vp, i32, i32, i32]
-    L.fx_stream.restype = vp
-    L.fx_stream.argtypes = [vp]
-    L.fx_gz_points.argtypes = [vp, i64, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-    L.fx_names_sort.argtypes = [vp, i32, i32, vp, C.POINTER(i64)]
-    L.fx_names_pack.argtypes = [vp, i32, vp, i64, vp, C.POINTER(i64)]
-    L.fx_fxi_bulk_rows.argtypes = [C.c_char_p, i32, i64, vp, vp, i32, vp]
-    L.fx_fxi_bulk_index.argtypes = [C.c_char_p, i32, i64, vp, vp, vp]
-    L.fx_fxi_bulk_index_int.argtypes = [C.c_char_p, i32, i64, vp, vp]
-    L.fx_open_laps.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.fx_build_laps.argtypes = [C.POINTER(C.c_double)]
-    L.fx_fastq_comp_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
-    L.fx_fxi_dev_sort.argtypes = [vp, i32, C.POINTER(C.c_int64)]
-    L.fx_fxi_dev_write.argtypes = [vp, i32, C.c_char_p, i32, i32, C.POINTER(C.c_double)]
-    L.fx_fxi_dev_build.argtypes = [vp, i32, C.c_char_p, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-    L.fx_fxi_presize_begin.argtypes = [C.c_char_p, i64, i32, C.POINTER(vp)]
-    L.fx_fxi_presize_end.argtypes = [vp, i32]
-    L.fx_fxi_part_shape.argtypes = [vp, i32, i64, C.POINTER(C.c_int64)]
-    L.fx_fxi_part_firsts.argtypes = [vp, vp]
-    L.fx_fxi_part_names.argtypes = [vp, i32, vp, vp]
-    L.fx_fxi_part_leaves.argtypes = [vp, i32, C.c_char_p, i64, i64, C.POINTER(C.c_double)]
-    L.fx_fxi_join_grow.argtypes = [C.c_char_p, i32, i64, i64, i32, C.POINTER(C.c_int64)]
-    L.fx_fxi_join_begin.argtypes = [i32, vp, vp, i64, C.POINTER(vp), C.POINTER(C.c_int64)]
-    L.fx_fxi_join_write.argtypes = [vp, C.c_char_p, i32, i32, i64, i64, vp, i64, C.POINTER(C.c_double)]
-    L.fx_fxi_join_end.argtypes = [vp]
-    L.fx_fxi_join_end.restype = None
-    L.fx_scratch_policy.argtypes = [vp, i32, i64, i64, vp]
-    L.fx_open_file_async.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
-    L.fx_stage_wait.argtypes = [vp, i64]
-    L.fx_sync.argtypes = [vp]
-    L.fx_prof_enable.argtypes = [vp, i32]
-    L.fx_prof_default.argtypes = [i32]
-    L.fx_prof_reset.argtypes = [vp]
-    L.fx_prof_name.restype = C.c_char_p
-    L.fx_prof_name.argtypes = [i32]
-    L.fx_prof_read.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]
-    L.fx_comm_unique_id.argtypes = [vp]
-    L.fx_comm_init.argtypes = [i32, i32, vp, i32, C.POINTER(vp)]
-    L.fx_comm_destroy.argtypes = [vp]
-    L.fx_comm_rank.argtypes = [vp]
-    L.fx_comm_world.argtypes = [vp]
-    L.fx_comm_allgather.argtypes = [vp, vp, vp, i64]
-    L.fx_fasta_build_sharded_begin.argtypes = [vp, vp, i32]
-    L.fx_fasta_build_sharded.argtypes = [vp, vp, i32, vp]
-    L.fx_comm_summaries.argtypes = [vp, vp, vp]
-    L.fx_fastq_build_sharded.argtypes = [vp, vp, vp]
-    L.fx_bgzf_counts.argtypes = [vp, vp]
-    L.fx_gz_open_mode.argtypes = [vp]
-    L.fx_kseq_scan.argtypes = [vp, vp, vp, vp, vp]
-    L.fx_kseq_records.argtypes = [vp, i64, i64, vp]
-    L.fx_kseq_prefix_lines.argtypes = [vp]
-    L.fx_kseq_prefix_lines.restype = i64
-    L.fx_kseq_fetch.argtypes = [vp, i32, i64, i64, i32, vp, vp, vp]
-    L.fx_gunzip_parallel.argtypes = [vp, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-    L.fx_sort_packed_names.argtypes = [i32, vp, vp, i64, vp, C.POINTER(i64)]
-    for s in SYMBOLS:
-        if getattr(L, s).restype is C.c_int:
-            pass
+    for name, (res, args) in PROTOTYPES.items():
+        f = getattr(L, name)
+        f.restype = res
+        if args:                                               # an entry of no arguments keeps ctypes' unchecked call
+            f.argtypes = args
     _LIB = L
     return L
 
@@ -416,11 +404,6 @@ def pinned_array(ptr, count, dtype=np.uint8):
     return np.frombuffer(owner, dtype=dt, count=int(count))
 
 
-def _pinned_columns(ptrs, dtypes, t):
-    """The pinned blocks an entry handed out (c_void_p, at least one item each) -> the arrays over their first t items."""
-    return tuple(pinned_array(p.value, max(t, 1), dt)[:t] for p, dt in zip(ptrs, dtypes))
-
-
 def pinned_empty(count, dtype=np.uint8):
     """numpy array of `count` items in pinned host memory (fx_pinned_alloc): query arrays built in it go to the device
     without a staging copy, answers written into it arrive by DMA."""
@@ -453,6 +436,71 @@ def _raise(rc, **attrs):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def _sel(ids):
+    """A selection of records or reads as the entries take it -> (int64 array or None, count): None stays NULL (everything),
+    an empty selection still hands over a valid pointer, with count 0."""
+    if ids is None:
+        return None, 0
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    return (ids if ids.size else np.zeros(1, dtype=np.int64)), ids.size
+
+
+RAW = "raw"
+
+
+def _column(p, spec, n):
+    """One pinned block an entry handed out (c_void_p, at least one item) under its column spec (see _call)."""
+    if not p.value:
+        return None
+    if spec is RAW:
+        return p.value
+    dt, w = spec if isinstance(spec, tuple) else (spec, 1)
+    a = pinned_array(p.value, max(n * w, 1), dt)[:n * w]
+    return a if w == 1 else a.reshape(n, w)
+
+
+def _call(fn, head, cols=(), counters=(0,), err=None, tail=()):
+    """The call path of the entries that answer in pinned memory: fn(*head, one out-pointer per column, one int64 counter per
+    start value of `counters`, *tail) -> (tuple of columns, list of counter values).  numpy arrays in head and tail go over as
+    their addresses; this frame holds them until fn has returned, so a caller may pass temporaries.  cols: per out-pointer a
+    dtype (the array over the first n items, n = the first counter), (dtype, w) (the same as [n, w]), RAW (the address as
+    the library gave it) or None (NULL goes over: not wanted); a pointer the library left NULL comes back as None.  A status
+    other than 0 raises FxError with the attribute err = (name, index of the counter that feeds it)."""
+    def addr(a):
+        return a.ctypes.data if isinstance(a, np.ndarray) else a
+    ptrs = [None if c is None else C.c_void_p() for c in cols]
+    vals = [C.c_int64(v) for v in counters]
+    rc = fn(*map(addr, head), *[p if p is None else C.byref(p) for p in ptrs], *map(C.byref, vals), *map(addr, tail))
+    vals = [int(v.value) for v in vals]
+    if rc:
+        _raise(rc, **({err[0]: vals[err[1]]} if err else {}))
+    return tuple(None if p is None else _column(p, c, vals[0] if vals else 0) for p, c in zip(ptrs, cols)), vals
+
+
+def _ragged(dst, offs, n):
+    """The block pair of an fx_*_alloc entry (addresses; offs holds n + 2 items) -> (uint8 buffer cut to offsets[n],
+    int64 offsets[n + 1]), pinned."""
+    o = pinned_array(offs, n + 2, np.int64)[:n + 1]
+    return pinned_array(dst, max(int(o[n]), 1))[:int(o[n])], o
+
+
+def too_many(e, noun, arg, limit):
+    """The exception to raise for the FxError of a capped entry: FX_ERANGE with a true count (.n_hits / .n_rows) above the
+    caller's limit becomes the ValueError that names it, anything else is `e` itself."""
+    n = getattr(e, "n_hits", getattr(e, "n_rows", 0))
+    if e.code == FX_ERANGE and n > limit:
+        return ValueError("%d %s, more than %s=%d" % (n, noun, arg, limit))
+    return e
+
+
+def outside(e, what="interval", owner="read"):
+    """The exception to raise for the FxError of a query entry: FX_ERANGE that names a query (.first_bad >= 0) becomes the
+    ValueError that names it, anything else is `e` itself."""
+    if e.code == FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
+        return ValueError("the %s of query %d lies outside its %s" % (what, e.first_bad, owner))
+    return e
 
 
 class Comm:
@@ -549,14 +597,12 @@ class SketchObj:
 
     def compare(self, other, ia=None, ib=None, limit=0, max_key=0, max_pairs=10**8):
         """(shared, total), int64[n_a, n_b] in pinned memory (fx_sketch_compare); ia / ib: the sets that take part, None: all."""
-        ia = None if ia is None else np.ascontiguousarray(ia, dtype=np.int64)
-        ib = None if ib is None else np.ascontiguousarray(ib, dtype=np.int64)
-        na, nb = (self.n_sets if ia is None else ia.size), (other.n_sets if ib is None else ib.size)
-        keep = [np.zeros(1, dtype=np.int64) if a is not None and a.size == 0 else a for a in (ia, ib)]      # an empty selection still hands over a pointer
+        (ia, na), (ib, nb) = _sel(ia), _sel(ib)
+        na, nb = (self.n_sets if ia is None else na), (other.n_sets if ib is None else nb)
         ps, pt = C.c_void_p(), C.c_void_p()
-        check(lib().fx_sketch_compare(self._live(), other._live(), _ptr(keep[0]), na, _ptr(keep[1]), nb, int(limit), int(max_key), int(max_pairs),
+        check(lib().fx_sketch_compare(self._live(), other._live(), _ptr(ia), na, _ptr(ib), nb, int(limit), int(max_key), int(max_pairs),
                                       C.byref(ps), C.byref(pt)))
-        sh, tot = _pinned_columns((ps, pt), (np.int64, np.int64), na * nb)
+        sh, tot = (_column(p, np.int64, na * nb) for p in (ps, pt))
         return sh.reshape(na, nb), tot.reshape(na, nb)
 
     def close(self):
@@ -1150,23 +1196,22 @@ class Blob:
         counts int64[n_sel, 2] or None); more than `cap` hits raise FxError(FX_ERANGE) whose .n_hits is the true count.
         cap = 0 with counts: counts only.  (max_mismatch, anchor: how fasta_search_approx comes through here.)"""
         plen = len(pattern if pattern is not None else rpattern)
-        ids = None if ids is None else self._i64(ids)
-        cnt = np.zeros((self._n_selected(ids), 2), dtype=np.int64) if counts else None
         pat = None if pattern is None else np.frombuffer(bytes(pattern), dtype=np.uint8)
         rpat = None if rpattern is None else np.frombuffer(bytes(rpattern), dtype=np.uint8)
-        rec, st, sd, mm, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
         if max_mismatch is None:
-            rc = lib().fx_fasta_search(self._h, _ptr(pat), _ptr(rpat), plen, int(mode), _ptr(ids), 0 if ids is None else ids.size,
-                                       int(cap), C.byref(rec), C.byref(st), C.byref(sd), C.byref(n), _ptr(cnt))
+            fn, head, cols = lib().fx_fasta_search, (self._h, pat, rpat, plen, int(mode)), (np.int64, np.int64, np.uint8)
         else:
-            rc = lib().fx_fasta_search_approx(self._h, _ptr(pat), _ptr(rpat), plen, int(mode), int(max_mismatch), int(anchor), _ptr(ids),
-                                              0 if ids is None else ids.size, int(cap), C.byref(rec), C.byref(st), C.byref(sd),
-                                              C.byref(mm), C.byref(n), _ptr(cnt))
-        if rc:
-            _raise(rc, n_hits=int(n.value))
-        cols = (rec, st, sd) if max_mismatch is None else (rec, st, sd, mm)
-        hits = _pinned_columns(cols, (np.int64, np.int64, np.uint8, np.uint8), int(n.value)) if rec.value else None
-        return int(n.value), hits, cnt
+            fn, head = lib().fx_fasta_search_approx, (self._h, pat, rpat, plen, int(mode), int(max_mismatch), int(anchor))
+            cols = (np.int64, np.int64, np.uint8, np.uint8)
+        return self._hits(fn, head, ids, cap, counts, cols)
+
+    def _hits(self, fn, head, ids, cap, counts, cols):
+        """The tail the hit entries share: fn(*head, ids, n_ids, cap, the hit columns, n_hits, counts[n_sel, 2] or NULL) ->
+        (n_hits, the columns or None where the entry made none, counts or None)."""
+        ids, n_ids = _sel(ids)
+        cnt = np.zeros((self._n_selected(ids, n_ids), 2), dtype=np.int64) if counts else None
+        hits, (n,) = _call(fn, head + (ids, n_ids, int(cap)), cols, err=("n_hits", 0), tail=(cnt,))
+        return n, (None if hits[0] is None else hits), cnt
 
     def fasta_search_approx(self, pattern, rpattern, mode, max_mismatch, anchor=0, ids=None, cap=0, counts=False):
         """fasta_search with up to max_mismatch mismatching letters per hit, none of them at a position whose bit is set in
@@ -1174,9 +1219,9 @@ class Blob:
         arrays or None, counts or None)."""
         return self.fasta_search(pattern, rpattern, mode, ids, cap, counts, int(max_mismatch), anchor)
 
-    def _n_selected(self, ids):
+    def _n_selected(self, ids, n_ids):
         if ids is not None:
-            return ids.size
+            return n_ids
         n_sel = getattr(self, "_n_fasta", None)
         if n_sel is None:
             n_sel = int(self.fasta_build_end().n_seq)         # a build was only enqueued: wait for it, learn the count
@@ -1187,41 +1232,26 @@ class Blob:
         (rec, start, strand, score) pinned arrays or None, counts int64[n_sel, 2] or None); more than `cap` hits raise
         FxError(FX_ERANGE) whose .n_hits is the true count.  cap = 0 with counts: counts only."""
         mat = np.ascontiguousarray(mat, dtype=np.int32)
-        ids = None if ids is None else self._i64(ids)
-        cnt = np.zeros((self._n_selected(ids), 2), dtype=np.int64) if counts else None
-        rec, st, sd, sc, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
-        rc = lib().fx_fasta_pwm_scan(self._h, _ptr(mat), mat.shape[0], int(mode), int(min_score), _ptr(ids), 0 if ids is None else ids.size,
-                                     int(cap), C.byref(rec), C.byref(st), C.byref(sd), C.byref(sc), C.byref(n), _ptr(cnt))
-        if rc:
-            _raise(rc, n_hits=int(n.value))
-        hits = _pinned_columns((rec, st, sd, sc), (np.int64, np.int64, np.uint8, np.int32), int(n.value)) if rec.value else None
-        return int(n.value), hits, cnt
+        return self._hits(lib().fx_fasta_pwm_scan, (self._h, mat, mat.shape[0], int(mode), int(min_score)), ids, cap, counts,
+                          (np.int64, np.int64, np.uint8, np.int32))
 
     def fasta_pwm_best(self, mat, mode, ids=None):
         """The best-scoring window of every selected record and strand (fx_fasta_pwm_best) -> (scores int32[n_sel, 2],
         starts int64[n_sel, 2]); (INT32_MIN, -1) where there is none."""
         mat = np.ascontiguousarray(mat, dtype=np.int32)
-        ids = None if ids is None else self._i64(ids)
-        n_sel = self._n_selected(ids)
+        ids, n_ids = _sel(ids)
+        n_sel = self._n_selected(ids, n_ids)
         scores = np.full((n_sel, 2), np.iinfo(np.int32).min, dtype=np.int32)
         starts = np.full((n_sel, 2), -1, dtype=np.int64)
-        check(lib().fx_fasta_pwm_best(self._h, _ptr(mat), mat.shape[0], int(mode), _ptr(ids), 0 if ids is None else ids.size,
-                                      _ptr(scores), _ptr(starts)))
+        _call(lib().fx_fasta_pwm_best, (self._h, mat, mat.shape[0], int(mode), ids, n_ids, scores, starts), counters=())
         return scores, starts
 
     def fasta_minimizers(self, k, w, flags, ids=None, cap=0, counts=False):
         """The (w, k) minimizers of the selected records (fx_fasta_minimizers; flags: FX_MZ_CANONICAL | FX_MZ_LEX) -> (n_hits,
         (rec, start, strand, code) pinned arrays or None, counts int64[n_sel, 2] or None); more than `cap` rows raise
         FxError(FX_ERANGE) whose .n_hits is the true count.  cap = 0 with counts: counts only."""
-        ids = None if ids is None else self._i64(ids)
-        cnt = np.zeros((self._n_selected(ids), 2), dtype=np.int64) if counts else None
-        rec, st, sd, cd, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(0)
-        rc = lib().fx_fasta_minimizers(self._h, int(k), int(w), int(flags), _ptr(ids), 0 if ids is None else ids.size, int(cap), C.byref(rec),
-                                       C.byref(st), C.byref(sd), C.byref(cd), C.byref(n), _ptr(cnt))
-        if rc:
-            _raise(rc, n_hits=int(n.value))
-        rows = _pinned_columns((rec, st, sd, cd), (np.int64, np.int64, np.uint8, np.uint64), int(n.value)) if rec.value else None
-        return int(n.value), rows, cnt
+        return self._hits(lib().fx_fasta_minimizers, (self._h, int(k), int(w), int(flags)), ids, cap, counts,
+                          (np.int64, np.int64, np.uint8, np.uint64))
 
     def fasta_rank_build(self):
         """The rank index of the resident table (fx_fasta_rank_build); a second call does nothing."""
@@ -1248,59 +1278,34 @@ class Blob:
     def fasta_window_counts(self, window, step, partial=True, ids=None, cap=10**8):
         """The windows of the selected records and their class counts (fx_fasta_window_counts) -> (rec, start, stop, counts
         int64[n, 7]) pinned arrays; more than `cap` windows raise FxError(FX_ERANGE) whose .n_rows is the true count."""
-        ids = None if ids is None else self._i64(ids)
-        out = [C.c_void_p() for _ in range(4)]
-        n = C.c_int64(0)
-        rc = lib().fx_fasta_window_counts(self._h, _ptr(ids), 0 if ids is None else ids.size, int(window), int(step), int(bool(partial)),
-                                          int(cap), *[C.byref(p) for p in out], C.byref(n))
-        if rc:
-            _raise(rc, n_rows=int(n.value))
-        t = int(n.value)
-        return _pinned_columns(out[:3], [np.int64] * 3, t) + (pinned_array(out[3].value, max(t, 1) * 7, np.int64)[:t * 7].reshape(t, 7),)
+        return _call(lib().fx_fasta_window_counts, (self._h, *_sel(ids), int(window), int(step), int(bool(partial)), int(cap)),
+                     [np.int64] * 3 + [(np.int64, 7)], err=("n_rows", 0))[0]
 
     def fasta_class_runs(self, set32, min_len=1, ids=None, cap=10**8):
         """Every maximal interval of letters of the 256-bit set `set32` (32 bytes) of at least min_len letters
         (fx_fasta_class_runs) -> (rec, start, stop) pinned arrays; more than `cap` raise FxError(FX_ERANGE) whose .n_rows is
         the true count."""
-        ids = None if ids is None else self._i64(ids)
         bits = np.frombuffer(bytes(set32), dtype=np.uint8)
         if bits.size != 32:
             raise ValueError("a byte set is 32 bytes")
-        out = [C.c_void_p() for _ in range(3)]
-        n, tot = C.c_int64(0), C.c_int64(0)
-        rc = lib().fx_fasta_class_runs(self._h, _ptr(bits), int(min_len), _ptr(ids), 0 if ids is None else ids.size, int(cap),
-                                       *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
-        if rc:
-            _raise(rc, n_rows=int(tot.value))
-        return _pinned_columns(out, [np.int64] * 3, int(n.value))
+        return _call(lib().fx_fasta_class_runs, (self._h, bits, int(min_len), *_sel(ids), int(cap)), [np.int64] * 3,
+                     counters=(0, 0), err=("n_rows", 1))[0]
 
     def fasta_tandem_repeats(self, min_copies, min_len=0, ids=None, cap=10**8):
         """The perfect tandem repeats of period 1..len(min_copies) <= 8 (fx_fasta_tandem_repeats): min_copies[p - 1] copies at
         least of period p, 0 = not searched -> (rec, start, stop int64, period uint8, motif uint32) pinned arrays ordered by
         record, stop, period; more than `cap` raise FxError(FX_ERANGE) whose .n_rows is the true count."""
-        ids = None if ids is None else self._i64(ids)
         mc = np.ascontiguousarray(min_copies, dtype=np.int32)
-        out = [C.c_void_p() for _ in range(5)]
-        n, tot = C.c_int64(0), C.c_int64(0)
-        rc = lib().fx_fasta_tandem_repeats(self._h, _ptr(mc), int(mc.size), int(min_len), _ptr(ids), 0 if ids is None else ids.size,
-                                           int(cap), *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
-        if rc:
-            _raise(rc, n_rows=int(tot.value))
-        return _pinned_columns(out, (np.int64, np.int64, np.int64, np.uint8, np.uint32), int(n.value))
+        return _call(lib().fx_fasta_tandem_repeats, (self._h, mc, int(mc.size), int(min_len), *_sel(ids), int(cap)),
+                     (np.int64, np.int64, np.int64, np.uint8, np.uint32), counters=(0, 0), err=("n_rows", 1))[0]
 
     def fasta_orfs(self, stop_mask, start_mask, mode=1, strands=3, min_len=0, ids=None, cap=10**8):
         """The open reading frames of the six frames (fx_fasta_orfs): masks by codon index 16 c0 + 4 c1 + c2 in A C G T order,
         mode 0 stop to stop / 1 START to stop, strands 1 + / 2 - / 3 both -> (rec, start, stop int64, frame int8, flags uint8)
         pinned arrays in the order the header states; more than `cap` raise FxError(FX_ERANGE) whose .n_rows is the true
         count."""
-        ids = None if ids is None else self._i64(ids)
-        out = [C.c_void_p() for _ in range(5)]
-        n, tot = C.c_int64(0), C.c_int64(0)
-        rc = lib().fx_fasta_orfs(self._h, int(stop_mask), int(start_mask), int(mode), int(strands), int(min_len), _ptr(ids),
-                                 0 if ids is None else ids.size, int(cap), *[C.byref(p) for p in out], C.byref(n), C.byref(tot))
-        if rc:
-            _raise(rc, n_rows=int(tot.value))
-        return _pinned_columns(out, (np.int64, np.int64, np.int64, np.int8, np.uint8), int(n.value))
+        return _call(lib().fx_fasta_orfs, (self._h, int(stop_mask), int(start_mask), int(mode), int(strands), int(min_len), *_sel(ids), int(cap)),
+                     (np.int64, np.int64, np.int64, np.int8, np.uint8), counters=(0, 0), err=("n_rows", 1))[0]
 
     def fasta_translate_alloc(self, seq_id, start, stop, aa64, strand=None, unknown=ord("X")):
         """(record id, start, stop) batches translated by the 64-byte table aa64 (fx_fasta_translate_alloc; strand: None or one
@@ -1314,13 +1319,9 @@ class Blob:
         tab = np.frombuffer(bytes(aa64), dtype=np.uint8)
         if tab.size != 64:
             raise ValueError("the amino-acid table has %d entries, not 64" % tab.size)
-        dst, offs, bad = C.c_void_p(), C.c_void_p(), C.c_int64(-1)
-        rc = lib().fx_fasta_translate_alloc(self._h, n, _ptr(seq_id), _ptr(start), _ptr(stop), _ptr(sd), _ptr(tab), int(unknown),
-                                            C.byref(dst), C.byref(offs), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        o = pinned_array(offs.value, n + 2, np.int64)[:n + 1]
-        return pinned_array(dst.value, max(int(o[n]), 1))[:int(o[n])], o
+        (dst, offs), _ = _call(lib().fx_fasta_translate_alloc, (self._h, n, seq_id, start, stop, sd, tab, int(unknown)), (RAW, RAW),
+                               counters=(-1,), err=("first_bad", 0))
+        return _ragged(dst, offs, n)
 
     def fastq_fetch_alloc(self, read_id, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         """Reads by id with the layout left to the library (fx_fastq_fetch_alloc) -> (seq, qual, quali, offsets), pinned."""
@@ -1342,15 +1343,9 @@ class Blob:
     def fastq_read_stats(self, ids=None, phred=0, low_qual=20):
         """Per-read quality statistics (fx_fastq_read_stats) -> dict of pinned columns length, qsum, qmin, qmax, n_low, n_gc,
         n_other in the order of ids (None: every read); an id outside the table raises FxError(FX_ERANGE) with .first_bad."""
-        ids = None if ids is None else self._i64(ids)
-        cols = [C.c_void_p() for _ in range(7)]
-        n, bad = C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_read_stats(self._h, _ptr(ids), 0 if ids is None else ids.size, int(phred), int(low_qual),
-                                       *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        names = ("length", "qsum", "qmin", "qmax", "n_low", "n_gc", "n_other")
-        return dict(zip(names, _pinned_columns(cols, [np.int64] * 2 + [np.int16] * 2 + [np.int32] * 3, int(n.value))))
+        cols, _ = _call(lib().fx_fastq_read_stats, (self._h, *_sel(ids), int(phred), int(low_qual)),
+                        [np.int64] * 2 + [np.int16] * 2 + [np.int32] * 3, counters=(0, -1), err=("first_bad", 1))
+        return dict(zip(("length", "qsum", "qmin", "qmax", "n_low", "n_gc", "n_other"), cols))
 
     def fastq_cycle_hist(self, cycles):
         """Per-cycle histograms (fx_fastq_cycle_hist) -> (qual int64[cycles, 256], base int64[cycles, 5], depth int64[cycles]), pinned."""
@@ -1363,154 +1358,97 @@ class Blob:
     def fastq_select(self, phred=0, low_qual=20, min_len=-1, max_len=-1, mean_qual=(0, 0), low_frac=(0, 0), max_other=-1):
         """Ascending ids of the reads that pass (fx_fastq_select); mean_qual / low_frac are (numerator, denominator) pairs, a
         denominator of 0 and a bound of -1 mean "not asked" -> int64 array in pinned memory."""
-        p, n = C.c_void_p(), C.c_int64(0)
-        check(lib().fx_fastq_select(self._h, int(phred), int(low_qual), int(min_len), int(max_len), int(mean_qual[0]), int(mean_qual[1]),
-                                    int(low_frac[0]), int(low_frac[1]), int(max_other), C.byref(p), C.byref(n)))
-        return _pinned_columns([p], [np.int64], int(n.value))[0]
+        return _call(lib().fx_fastq_select, (self._h, int(phred), int(low_qual), int(min_len), int(max_len), int(mean_qual[0]), int(mean_qual[1]),
+                                             int(low_frac[0]), int(low_frac[1]), int(max_other)), [np.int64])[0][0]
 
     def fastq_trim(self, ids=None, phred=0, clip_front=0, clip_tail=0, adapter=None, min_overlap=1, err=(0, 1), front_qual=None,
                    window=None, tail_qual=None):
         """Per-read surviving interval (fx_fastq_trim) -> (start, end), int64 in pinned memory, in the order of ids (None:
         every read).  adapter: upper-case bytes of A C G T N or None; err = (num, den); window = (length, num, den) or None;
         a threshold None is a step not asked for.  An id outside the table raises FxError(FX_ERANGE) with .first_bad."""
-        ids = None if ids is None else self._i64(ids)
         ad = None if adapter is None else bytes(adapter)
         w = (0, 0, 1) if window is None else window
-        ps, pe, n, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_trim(self._h, _ptr(ids), 0 if ids is None else ids.size, int(phred), int(clip_front), int(clip_tail),
-                                 ad, 0 if ad is None else len(ad), int(min_overlap), int(err[0]), int(err[1]),
-                                 -1 if front_qual is None else int(front_qual), int(w[0]), int(w[1]), int(w[2]),
-                                 -1 if tail_qual is None else int(tail_qual), C.byref(ps), C.byref(pe), C.byref(n), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        return _pinned_columns((ps, pe), [np.int64] * 2, int(n.value))
+        head = (self._h, *_sel(ids), int(phred), int(clip_front), int(clip_tail), ad, 0 if ad is None else len(ad), int(min_overlap),
+                int(err[0]), int(err[1]), -1 if front_qual is None else int(front_qual), int(w[0]), int(w[1]), int(w[2]),
+                -1 if tail_qual is None else int(tail_qual))
+        return _call(lib().fx_fastq_trim, head, [np.int64] * 2, counters=(0, -1), err=("first_bad", 1))[0]
 
     def fastq_format_alloc(self, ids=None, start=None, end=None, min_len=0):
         """Four-line records of the queries cut to [start, end) (fx_fastq_format_alloc; start = end = None: whole reads) ->
         (uint8 buffer, int64 offsets[n + 1], records kept), pinned.  A bad id or interval raises FxError(FX_ERANGE) with
         .first_bad."""
-        ids = None if ids is None else self._i64(ids)
-        start = None if start is None else self._i64(start)
-        end = None if end is None else self._i64(end)
-        pd, po, n, kept, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_format_alloc(self._h, _ptr(ids), 0 if ids is None else ids.size, _ptr(start), _ptr(end), int(min_len),
-                                         C.byref(pd), C.byref(po), C.byref(n), C.byref(kept), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
-        tot = int(o[m])
-        return pinned_array(pd.value, max(tot, 1))[:tot], o, int(kept.value)
+        (dst, offs), (n, kept, _) = _call(lib().fx_fastq_format_alloc, (self._h, *self._fastq_queries(ids, start, end), int(min_len)),
+                                          (RAW, RAW), counters=(0, 0, -1), err=("first_bad", 2))
+        return _ragged(dst, offs, n) + (kept,)
 
     def fastq_demux(self, barcodes, src, off, length, mm, margin=1, ids=None, want_order=True):
         """Barcode demultiplexing (fx_fastq_demux) -> dict of pinned columns sample, dist, second (int32, one row per query in
         the order of ids; None: every read), counts (int64[n_samples + 2]) and, with want_order, order (int64[n]) and
         bin_off (int64[n_samples + 3]).  barcodes: uint8[n_samples, sum(length)], upper-case A C G T N; src / off / length /
         mm: one entry per segment (1 or 2).  An id outside the table raises FxError(FX_ERANGE) with .first_bad."""
-        ids = None if ids is None else self._i64(ids)
         bc = np.ascontiguousarray(barcodes, dtype=np.uint8)
         seg = [np.ascontiguousarray(a, dtype=np.int32) for a in (src, off, length, mm)]
         n_seg = int(seg[0].size)
         if bc.ndim != 2 or any(a.ndim != 1 or a.size != n_seg for a in seg) or n_seg not in (1, 2) or bc.shape[1] != int(seg[2].sum()):
             raise ValueError("barcodes must be n_samples rows of sum(length) letters, with one src / off / length / mm per segment")
         n_samples = int(bc.shape[0])
-        cols = [C.c_void_p() for _ in range(6)]
-        n, bad = C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_demux(self._h, _ptr(ids), 0 if ids is None else ids.size, n_seg, *[_ptr(a) for a in seg], _ptr(bc), n_samples,
-                                  int(margin), 1 if want_order else 0, *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        out = dict(zip(("sample", "dist", "second"), _pinned_columns(cols[:3], [np.int32] * 3, m)))
-        out["counts"] = pinned_array(cols[3].value, n_samples + 2, np.int64)
+        cols, _ = _call(lib().fx_fastq_demux, (self._h, *_sel(ids), n_seg, *seg, bc, n_samples, int(margin), 1 if want_order else 0),
+                        [np.int32] * 3 + [RAW, np.int64, RAW], counters=(0, -1), err=("first_bad", 1))
+        out = dict(zip(("sample", "dist", "second"), cols[:3]))
+        out["counts"] = pinned_array(cols[3], n_samples + 2, np.int64)
         if want_order:
-            out["order"] = _pinned_columns(cols[4:5], [np.int64], m)[0]
-            out["bin_off"] = pinned_array(cols[5].value, n_samples + 3, np.int64)
+            out["order"] = cols[4]
+            out["bin_off"] = pinned_array(cols[5], n_samples + 3, np.int64)
         return out
 
     def fastq_pair_overlap(self, mate, ids=None, min_overlap=30, max_diff=5, err=(1, 5)):
         """The overlap of every pair (this blob: read 1, `mate`: read 2; fx_fastq_pair_overlap) -> dict of pinned columns diag,
         overlap, mismatches (int32), end1, end2 (int64) in the order of ids (None: every pair); diag is FX_PAIR_NONE where no
         diagonal is accepted.  err = (num, den).  An id outside the table raises FxError(FX_ERANGE) with .first_bad."""
-        ids = None if ids is None else self._i64(ids)
-        cols = [C.c_void_p() for _ in range(5)]
-        n, bad = C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_pair_overlap(self._h, mate._h, _ptr(ids), 0 if ids is None else ids.size, int(min_overlap), int(max_diff),
-                                         int(err[0]), int(err[1]), *[C.byref(c) for c in cols], C.byref(n), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        names = ("diag", "overlap", "mismatches", "end1", "end2")
-        return dict(zip(names, _pinned_columns(cols, [np.int32] * 3 + [np.int64] * 2, int(n.value))))
+        cols, _ = _call(lib().fx_fastq_pair_overlap, (self._h, mate._h, *_sel(ids), int(min_overlap), int(max_diff), int(err[0]), int(err[1])),
+                        [np.int32] * 3 + [np.int64] * 2, counters=(0, -1), err=("first_bad", 1))
+        return dict(zip(("diag", "overlap", "mismatches", "end1", "end2"), cols))
 
     def fastq_pair_merge_alloc(self, mate, diag, ids=None, min_len=0):
         """The merged records of the pairs (fx_fastq_pair_merge_alloc; diag: what fastq_pair_overlap returned for the same
         ids) -> (uint8 buffer, int64 offsets[n + 1], records merged), pinned.  A bad id or diagonal raises
         FxError(FX_ERANGE) with .first_bad."""
-        ids = None if ids is None else self._i64(ids)
         diag = np.ascontiguousarray(diag, dtype=np.int32)
-        pd, po, n, merged, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_pair_merge_alloc(self._h, mate._h, _ptr(ids), 0 if ids is None else ids.size, _ptr(diag) if diag.size else None,
-                                             int(min_len), C.byref(pd), C.byref(po), C.byref(n), C.byref(merged), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        m = int(n.value)
-        o = pinned_array(po.value, m + 2, np.int64)[:m + 1]
-        tot = int(o[m])
-        return pinned_array(pd.value, max(tot, 1))[:tot], o, int(merged.value)
-
-    @staticmethod
-    def _kmer_ids(ids):
-        """ids for the k-mer entries: None stays NULL (everything); an empty selection still hands over a valid pointer."""
-        if ids is None:
-            return None, 0, None
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        return (ids if ids.size else np.zeros(1, dtype=np.int64)), ids.size, ids
+        (dst, offs), (n, merged, _) = _call(lib().fx_fastq_pair_merge_alloc, (self._h, mate._h, *_sel(ids), diag if diag.size else None, int(min_len)),
+                                            (RAW, RAW), counters=(0, 0, -1), err=("first_bad", 2))
+        return _ragged(dst, offs, n) + (merged,)
 
     def fasta_kmers(self, k, canonical=False, ids=None, per_record=False):
         """k-mer spectrum of the resident FASTA table (fx_fasta_kmers) -> int64[4**k], or int64[n_sel, 4**k] with per_record
         (k <= 6), in pinned memory.  ids: 0-based record ids, any order, repeats count again; None: every record.  An id
         outside the table raises FxError(FX_ERANGE) with .first_bad."""
-        buf, n_ids, _ = self._kmer_ids(ids)
-        p, rows, bad = C.c_void_p(), C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fasta_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids, 1 if per_record else 0,
-                                  C.byref(p), C.byref(rows), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        m, w = int(rows.value), 4 ** int(k)
-        a = pinned_array(p.value, max(m * w, 1), np.int64)[:m * w]
-        return a.reshape(m, w) if per_record else a
+        (a,), _ = _call(lib().fx_fasta_kmers, (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, *_sel(ids), 1 if per_record else 0),
+                        [(np.int64, 4 ** int(k))], counters=(0, -1), err=("first_bad", 1))
+        return a if per_record else a.reshape(-1)
 
     def fastq_kmers(self, k, canonical=False, ids=None, start=None, end=None):
         """k-mer spectrum of the reads `ids` (None: every read) cut to [start, end) (both None: whole reads) of the resident
         FASTQ table (fx_fastq_kmers) -> int64[4**k] in pinned memory.  A bad id or interval raises FxError(FX_ERANGE) with
         .first_bad."""
-        q, keep = self._fastq_queries(ids, start, end)
-        p, bad = C.c_void_p(), C.c_int64(-1)
-        rc = lib().fx_fastq_kmers(self._h, int(k), FX_KMER_CANONICAL if canonical else 0, *q, C.byref(p), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        return pinned_array(p.value, 4 ** int(k), np.int64)
+        (p,), _ = _call(lib().fx_fastq_kmers, (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, *self._fastq_queries(ids, start, end)),
+                        [RAW], counters=(-1,), err=("first_bad", 0))
+        return pinned_array(p, 4 ** int(k), np.int64)
 
     def _kmer_table(self, call, head, min_count, max_bytes):
-        pc, pn = C.c_void_p(), C.c_void_p()
-        nd, nw, parts, bad = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
-        rc = call(*head, int(min_count), int(max_bytes), C.byref(pc), C.byref(pn), C.byref(nd), C.byref(nw), C.byref(parts), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        return _pinned_columns((pc, pn), [np.int64] * 2, int(nd.value)) + (int(nw.value), int(parts.value))
+        cols, (_, nw, parts, _) = _call(call, head + (int(min_count), int(max_bytes)), [np.int64] * 2, counters=(0, 0, 0, -1), err=("first_bad", 3))
+        return cols + (nw, parts)
 
     def fasta_kmer_table(self, k, canonical=False, ids=None, min_count=1, max_bytes=0):
         """Sparse k-mer table of the resident FASTA table (fx_fasta_kmer_table), 1 <= k <= 31 -> (codes int64[n] ascending,
         counts int64[n], n_windows, n_parts), the arrays in pinned memory.  ids as for fasta_kmers; max_bytes = 0: the
         library's default budget of device working memory."""
-        buf, n_ids, _ = self._kmer_ids(ids)
-        head = (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, _ptr(buf), n_ids)
+        head = (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, *_sel(ids))
         return self._kmer_table(lib().fx_fasta_kmer_table, head, min_count, max_bytes)
 
     def fastq_kmer_table(self, k, canonical=False, ids=None, start=None, end=None, min_count=1, max_bytes=0):
         """Sparse k-mer table of the reads `ids` cut to [start, end) (fx_fastq_kmer_table) -> what fasta_kmer_table returns."""
-        q, keep = self._fastq_queries(ids, start, end)
-        return self._kmer_table(lib().fx_fastq_kmer_table, (self._h, int(k), FX_KMER_CANONICAL if canonical else 0) + q, min_count, max_bytes)
+        head = (self._h, int(k), FX_KMER_CANONICAL if canonical else 0, *self._fastq_queries(ids, start, end))
+        return self._kmer_table(lib().fx_fastq_kmer_table, head, min_count, max_bytes)
 
     def kmer_set(self, k, canonical, codes):
         """A device k-mer set of `codes` on this blob's device (fx_kmer_set_create) -> KmerSet; any blob of the device may use it."""
@@ -1519,81 +1457,64 @@ class Blob:
     def fasta_sketch(self, k, flags, ids=None, max_key=1, size=0, oversample=0):
         """Sketches of the selected records (fx_fasta_sketch; flags: FX_SK_CANONICAL | FX_SK_POOLED; ids: distinct ascending
         record ids, None: every record) -> (SketchObj, n_rounds)."""
-        buf, n_ids, _ = self._kmer_ids(ids)
+        ids, n_ids = _sel(ids)
         s, nr = C.c_void_p(), C.c_int(0)
-        check(lib().fx_fasta_sketch(self._h, int(k), int(flags), _ptr(buf), n_ids, int(max_key), int(size), int(oversample), C.byref(s), C.byref(nr)))
+        check(lib().fx_fasta_sketch(self._h, int(k), int(flags), _ptr(ids), n_ids, int(max_key), int(size), int(oversample), C.byref(s), C.byref(nr)))
         return SketchObj(s), int(nr.value)
 
     def fastq_sketch(self, k, flags, ids=None, start=None, end=None, max_key=1, size=0, oversample=0):
         """The pooled sketch of the reads `ids` cut to [start, end) (fx_fastq_sketch) -> (SketchObj, n_rounds); a bad id or
         interval raises FxError(FX_ERANGE) with .first_bad."""
-        q, keep = self._fastq_queries(ids, start, end)
+        ids, n_ids, start, end = self._fastq_queries(ids, start, end)
         s, nr, bad = C.c_void_p(), C.c_int(0), C.c_int64(-1)
-        rc = lib().fx_fastq_sketch(self._h, int(k), int(flags), *q, int(max_key), int(size), int(oversample), C.byref(s), C.byref(nr), C.byref(bad))
+        rc = lib().fx_fastq_sketch(self._h, int(k), int(flags), _ptr(ids), n_ids, _ptr(start), _ptr(end), int(max_key), int(size), int(oversample),
+                                   C.byref(s), C.byref(nr), C.byref(bad))
         if rc:
             _raise(rc, first_bad=int(bad.value))
         return SketchObj(s), int(nr.value)
 
-    def _kmer_hits(self, call, head, dtype):
-        pw, ph, n, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(-1)
-        rc = call(*head, C.byref(pw), C.byref(ph), C.byref(n), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        return _pinned_columns((pw, ph), [dtype] * 2, int(n.value))
+    @staticmethod
+    def _kmer_hits(call, head, dtype):
+        return _call(call, head, [dtype] * 2, counters=(0, -1), err=("first_bad", 1))[0]
 
     def _fastq_queries(self, ids, start, end):
-        buf, n_ids, _ = self._kmer_ids(ids)
+        """The query batch of the FASTQ interval entries -> (ids, n_ids, start, end) as they go into _call."""
         start = None if start is None else self._i64(start)
         end = None if end is None else self._i64(end)
         if start is not None and start.size == 0:
             start = end = None                                 # no query, no interval
-        return (_ptr(buf), n_ids, _ptr(start), _ptr(end)), (buf, start, end)
+        return (*_sel(ids), start, end)
 
     def fastq_kmer_hits(self, kset, ids=None, start=None, end=None):
         """Per query the valid windows of seq[start:end] and how many of them are in `kset` (fx_fastq_kmer_hits) ->
         (n_windows, n_hits), int32 in pinned memory.  A bad id or interval raises FxError(FX_ERANGE) with .first_bad."""
-        q, keep = self._fastq_queries(ids, start, end)
-        return self._kmer_hits(lib().fx_fastq_kmer_hits, (self._h, kset._s) + q, np.int32)
+        return self._kmer_hits(lib().fx_fastq_kmer_hits, (self._h, kset._s, *self._fastq_queries(ids, start, end)), np.int32)
 
     def fastq_kmer_screen(self, kset, ids=None, start=None, end=None, min_hits=1, frac=(0, 0), invert=False):
         """The ascending positions of the queries whose hits pass min_hits and the ratio frac = (num, den) (fx_fastq_kmer_screen;
         den 0: not asked) -> int64 in pinned memory."""
-        q, keep = self._fastq_queries(ids, start, end)
-        p, n, bad = C.c_void_p(), C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_kmer_screen(self._h, kset._s, *q, int(min_hits), int(frac[0]), int(frac[1]), 1 if invert else 0,
-                                        C.byref(p), C.byref(n), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        return _pinned_columns([p], [np.int64], int(n.value))[0]
+        head = (self._h, kset._s, *self._fastq_queries(ids, start, end), int(min_hits), int(frac[0]), int(frac[1]), 1 if invert else 0)
+        return _call(lib().fx_fastq_kmer_screen, head, [np.int64], counters=(0, -1), err=("first_bad", 1))[0][0]
 
     def fasta_kmer_hits(self, kset, ids=None):
         """Per selected record the valid windows and the hits in `kset` (fx_fasta_kmer_hits) -> (n_windows, n_hits), int64."""
-        buf, n_ids, _ = self._kmer_ids(ids)
-        return self._kmer_hits(lib().fx_fasta_kmer_hits, (self._h, kset._s, _ptr(buf), n_ids), np.int64)
+        return self._kmer_hits(lib().fx_fasta_kmer_hits, (self._h, kset._s, *_sel(ids)), np.int64)
 
     def fastq_dup_first(self, ids=None, start=None, end=None, revcomp=False, hash_bits=0):
         """first[q] = the smallest query position whose key seq[start:end] is a duplicate of query q's (fx_fastq_dup_first) ->
         (first int64[n] in pinned memory, n_groups, n_rounds).  hash_bits: the fingerprint bits kept (0: 64); no result but
         n_rounds depends on it.  A bad id or interval raises FxError(FX_ERANGE) with .first_bad."""
-        q, keep = self._fastq_queries(ids, start, end)
-        p, n, groups, rounds, bad = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_dup_first(self._h, *q, FX_DUP_REVCOMP if revcomp else 0, int(hash_bits), C.byref(p), C.byref(n), C.byref(groups),
-                                      C.byref(rounds), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        return _pinned_columns([p], [np.int64], int(n.value)) + (int(groups.value), int(rounds.value))
+        head = (self._h, *self._fastq_queries(ids, start, end), FX_DUP_REVCOMP if revcomp else 0, int(hash_bits))
+        cols, (_, groups, rounds, _) = _call(lib().fx_fastq_dup_first, head, [np.int64], counters=(0, 0, 0, -1), err=("first_bad", 3))
+        return cols + (groups, rounds)
 
     def fastq_dedup(self, ids=None, start=None, end=None, revcomp=False, hash_bits=0, min_copies=1, max_copies=-1, want_copies=False):
         """The ascending positions of the first occurrences whose group has min_copies..max_copies members (fx_fastq_dedup;
         max_copies < 0: not asked) -> (pos int64 in pinned memory, copies int64 or None, n_groups, n_rounds)."""
-        q, keep = self._fastq_queries(ids, start, end)
-        p, pc, n, groups, rounds, bad = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
-        rc = lib().fx_fastq_dedup(self._h, *q, FX_DUP_REVCOMP if revcomp else 0, int(hash_bits), int(min_copies), int(max_copies), C.byref(p),
-                                  C.byref(pc) if want_copies else None, C.byref(n), C.byref(groups), C.byref(rounds), C.byref(bad))
-        if rc:
-            _raise(rc, first_bad=int(bad.value))
-        pos, copies = _pinned_columns([p, pc] if want_copies else [p], [np.int64] * 2, int(n.value)) + (() if want_copies else (None,))
-        return pos, copies, int(groups.value), int(rounds.value)
+        head = (self._h, *self._fastq_queries(ids, start, end), FX_DUP_REVCOMP if revcomp else 0, int(hash_bits), int(min_copies), int(max_copies))
+        cols, (_, groups, rounds, _) = _call(lib().fx_fastq_dedup, head, [np.int64, np.int64 if want_copies else None],
+                                             counters=(0, 0, 0, -1), err=("first_bad", 3))
+        return cols + (groups, rounds)
 
     def fastq_fetch(self, read_id, rlen, phred=0, seq_flags=0, want=("seq", "qual", "quali")):
         read_id = self._i64(read_id)
@@ -1623,10 +1544,6 @@ class Blob:
             check(lib().fx_read_fetch(self._h, FX_HOST, n, _ptr(soff), _ptr(qoff), _ptr(rlen), int(phred),
                                       int(seq_flags), _ptr(seq), _ptr(qual), _ptr(qi), _ptr(offs)))
         return seq, qual, qi, offs
-
-
-def _noop():
-    pass
 
 
 def revcomp_bytes(b, mode=FX_REVERSE | FX_COMPLEMENT, device=0):

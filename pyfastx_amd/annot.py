@@ -169,9 +169,7 @@ def window_blob(blob, slen, window, step=None, ids=None, partial=True, max_windo
     try:
         rec, a, b, counts = blob.fasta_window_counts(window, step, partial, ids, cap=int(max_windows))
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_rows", 0) > max_windows:
-            raise ValueError("%d windows, more than max_windows=%d" % (e.n_rows, max_windows))
-        raise
+        raise _lib.too_many(e, "windows", "max_windows", max_windows)
     return RegionStats(rec, a, b, counts)
 
 
@@ -182,7 +180,5 @@ def runs_blob(blob, kind=None, min_len=1, ids=None, max_runs=10**8, letters=None
     try:
         rec, a, b = blob.fasta_class_runs(bits, min_len, ids, cap=max_runs)
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_rows", 0) > max_runs:
-            raise ValueError("%d runs, more than max_runs=%d" % (e.n_rows, max_runs))
-        raise
+        raise _lib.too_many(e, "runs", "max_runs", max_runs)
     return ClassRuns(rec, a, b, names)

@@ -54,12 +54,6 @@ def _queries(ids, start, end, n_reads):
     return ids, start, end
 
 
-def _range_error(e):
-    if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
-        return ValueError("the interval of query %d lies outside its read" % e.first_bad)
-    return e
-
-
 def duplicates_blob(blob, n_reads, ids=None, start=None, end=None, revcomp=False, hash_bits=0):
     """-> (first int64[n], n_groups, n_rounds); ids, start and end by the rules of Fastq.records."""
     revcomp, hash_bits = check_flag(revcomp, "revcomp"), check_hash_bits(hash_bits)
@@ -67,7 +61,7 @@ def duplicates_blob(blob, n_reads, ids=None, start=None, end=None, revcomp=False
     try:
         return blob.fastq_dup_first(ids, start, end, revcomp, hash_bits)
     except _lib.FxError as e:
-        raise _range_error(e)
+        raise _lib.outside(e)
 
 
 def dedup_blob(blob, n_reads, ids=None, start=None, end=None, revcomp=False, min_copies=1, max_copies=None, return_counts=False, hash_bits=0):
@@ -79,7 +73,7 @@ def dedup_blob(blob, n_reads, ids=None, start=None, end=None, revcomp=False, min
     try:
         return blob.fastq_dedup(ids, start, end, revcomp, hash_bits, lo, hi, return_counts)
     except _lib.FxError as e:
-        raise _range_error(e)
+        raise _lib.outside(e)
 
 
 def duplication_levels(copies):

@@ -70,9 +70,7 @@ def fastq_counts_blob(blob, n_reads, k, canonical=False, ids=None, start=None, e
     try:
         return blob.fastq_kmers(k, bool(canonical), ids, start, end)
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
-            raise ValueError("the interval of query %d lies outside its read" % e.first_bad)
-        raise
+        raise _lib.outside(e)
 
 
 # ------------------------------------------------------------------ sparse tables (1 <= k <= 31)
@@ -207,9 +205,7 @@ def fastq_table_blob(blob, n_reads, k, canonical=False, ids=None, start=None, en
     try:
         codes, counts, nw, parts = blob.fastq_kmer_table(k, bool(canonical), ids, start, end, min_count, max_bytes)
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
-            raise ValueError("the interval of query %d lies outside its read" % e.first_bad)
-        raise
+        raise _lib.outside(e)
     return KmerTable(k, canonical, codes, counts, nw, parts)
 
 
@@ -249,12 +245,6 @@ def device_set(table, blob, device):
     return s
 
 
-def _range_error(e, what):
-    if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
-        return ValueError("the interval of query %d lies outside its %s" % (e.first_bad, what))
-    return e
-
-
 def fastq_hits_blob(blob, device, n_reads, table, ids=None, start=None, end=None):
     """(n_windows, n_hits), int32, of seq[start:end] of the reads `ids` against the table; ids, start and end by the rules of
     Fastq.records."""
@@ -264,7 +254,7 @@ def fastq_hits_blob(blob, device, n_reads, table, ids=None, start=None, end=None
     try:
         return blob.fastq_kmer_hits(device_set(table, blob, device), ids, start, end)
     except _lib.FxError as e:
-        raise _range_error(e, "read")
+        raise _lib.outside(e)
 
 
 def fastq_screen_blob(blob, device, n_reads, table, min_hits=1, min_frac=None, invert=False, ids=None, start=None, end=None):
@@ -276,7 +266,7 @@ def fastq_screen_blob(blob, device, n_reads, table, min_hits=1, min_frac=None, i
     try:
         return blob.fastq_kmer_screen(device_set(table, blob, device), ids, start, end, min_hits, frac, invert)
     except _lib.FxError as e:
-        raise _range_error(e, "read")
+        raise _lib.outside(e)
 
 
 def fasta_hits_blob(blob, device, table, ids=None):

@@ -148,9 +148,7 @@ def minimizers_blob(blob, k, w, canonical=True, order="hash", ids=None, max_hits
     try:
         total, rows, _ = blob.fasta_minimizers(k, w, _flags(canonical, order), ids=ids, cap=int(max_hits))
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_hits", 0) > max_hits:
-            raise ValueError("%d minimizers, more than max_hits=%d" % (e.n_hits, max_hits))
-        raise
+        raise _lib.too_many(e, "minimizers", "max_hits", max_hits)
     if rows is None:
         return _empty()
     rec, starts, strands, codes = rows

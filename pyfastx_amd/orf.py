@@ -239,7 +239,5 @@ def orfs_run(blob, args, ids=None, names=None):
     try:
         cols = blob.fasta_orfs(stop_mask, start_mask, m, s, min_len, ids, cap=max_orfs)
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_rows", 0) > max_orfs:
-            raise ValueError("%d open reading frames, more than max_orfs=%d" % (e.n_rows, max_orfs))
-        raise
+        raise _lib.too_many(e, "open reading frames", "max_orfs", max_orfs)
     return Orfs(*cols, names=names, translate=lambda i, a, b, sd: translate_blob(blob, i, a, b, sd, table))

@@ -55,9 +55,7 @@ def merge_blob(blob1, blob2, n_reads, ids, diag, min_len):
     try:
         return blob1.fastq_pair_merge_alloc(blob2, diag, ids, min_len)
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
-            raise ValueError("the diagonal of query %d lies outside its pair" % e.first_bad)
-        raise
+        raise _lib.outside(e, "diagonal", "pair")
 
 
 def clamp_intervals(t1, t2, ov):

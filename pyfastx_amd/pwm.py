@@ -232,9 +232,7 @@ def scan_blob(blob, pwm, min_score, strand="both", ids=None, max_hits=10**8):
     try:
         total, hits, _ = blob.fasta_pwm_scan(pwm.ints, mode, min_score, ids=ids, cap=int(max_hits))
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_hits", 0) > max_hits:
-            raise ValueError("%d hits, more than max_hits=%d" % (e.n_hits, max_hits))
-        raise
+        raise _lib.too_many(e, "hits", "max_hits", max_hits)
     if hits is None:
         z = np.zeros(0, dtype=np.int64)
         return PwmHits(z, z.copy(), z.copy(), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.int32))

@@ -78,9 +78,7 @@ def search_blob(blob, pattern, strand="both", degenerate=False, uppercase=False,
     try:
         total, hits, _ = blob.fasta_search(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, ids=ids, cap=int(max_hits))
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_hits", 0) > max_hits:
-            raise ValueError("%d hits, more than max_hits=%d" % (e.n_hits, max_hits))
-        raise
+        raise _lib.too_many(e, "hits", "max_hits", max_hits)
     if hits is None:
         z = np.zeros(0, dtype=np.int64)
         return SearchHits(z, z.copy(), z.copy(), np.zeros(0, dtype=np.uint8))
@@ -139,9 +137,7 @@ def approx_blob(blob, pattern, mismatches, anchor=None, strand="both", degenerat
         total, hits, _ = blob.fasta_search_approx(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, d, mask, ids=ids,
                                                   cap=int(max_hits))
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_hits", 0) > max_hits:
-            raise ValueError("%d hits, more than max_hits=%d" % (e.n_hits, max_hits))
-        raise
+        raise _lib.too_many(e, "hits", "max_hits", max_hits)
     if hits is None:
         z = np.zeros(0, dtype=np.int64)
         return ApproxHits(z, z.copy(), z.copy(), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))

@@ -257,11 +257,9 @@ def _wrap(call, what):
     try:
         return call()
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
-            raise ValueError("the interval of query %d lies outside its read" % e.first_bad)
-        if e.code == _lib.FX_ERANGE:
+        if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) < 0:
             raise ValueError("%s: %s" % (what, e))
-        raise
+        raise _lib.outside(e)
 
 
 def fasta_sketch_blob(blob, k, scaled=None, size=None, canonical=True, ids=None, pooled=False, names=None, oversample=0, device=0):

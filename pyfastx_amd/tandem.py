@@ -145,7 +145,5 @@ def repeats_blob(blob, min_copies=KRAIT_DEFAULT, min_len=0, ids=None, max_repeat
     try:
         cols = blob.fasta_tandem_repeats(mc, min_len, ids, cap=max_repeats)
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "n_rows", 0) > max_repeats:
-            raise ValueError("%d repeats, more than max_repeats=%d" % (e.n_rows, max_repeats))
-        raise
+        raise _lib.too_many(e, "repeats", "max_repeats", max_repeats)
     return TandemRepeats(*cols, names=names)

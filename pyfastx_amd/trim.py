@@ -100,9 +100,7 @@ def records_blob(blob, n_reads, ids, start, end, min_len):
     try:
         return blob.fastq_format_alloc(ids, start, end, min_len)
     except _lib.FxError as e:
-        if e.code == _lib.FX_ERANGE and getattr(e, "first_bad", -1) >= 0:
-            raise ValueError("the interval of query %d lies outside its read" % e.first_bad)
-        raise
+        raise _lib.outside(e)
 
 
 def batches(tab, ids, n_reads, batch_bytes):

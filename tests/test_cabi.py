@@ -27,6 +27,48 @@ def test_every_declared_symbol_is_exported():
     assert b"gfx950" in L.fx_version()
 
 
+_POINTERS = (C.c_void_p, C.c_char_p, C._Pointer)
+_SCALARS = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32), "int64_t": (C.c_int64,), "uint64_t": (C.c_uint64,),
+            "uint8_t": (C.c_uint8,), "double": (C.c_double,)}
+
+
+def _agrees(ctype, text, what):
+    """One argument or return type of the binding against the header's text for it, by class."""
+    text = " ".join(w for w in re.sub(r"[*\[]", " * ", text).split() if w != "const")
+    if "*" in text:
+        assert isinstance(ctype, type) and issubclass(ctype, _POINTERS), "%s: %r is a pointer, bound as %r" % (what, text, ctype)
+    elif text == "void":
+        assert ctype is None, "%s: void, bound as %r" % (what, ctype)
+    else:
+        assert text in _SCALARS, "%s: %r is outside the mapping" % (what, text)
+        assert any(ctype is t for t in _SCALARS[text]), "%s: %r bound as %r" % (what, text, ctype)
+
+
+def test_every_prototype_matches_the_binding_table():
+    """include/fxgpu.h against _lib.PROTOTYPES: the return type, the number of arguments and the class of every argument (an
+    int bound where the header says int64_t would load, run and truncate).  Reads the table, not the library."""
+    from pyfastx_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "fxgpu.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", "", hdr, flags=re.M)                     # line comments, preprocessor lines
+    seen, n_args = set(), 0
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s]*?[\s*]+)(fx_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr):
+        assert name not in seen, "%s is declared twice" % name
+        seen.add(name)
+        assert name in _lib.PROTOTYPES, "%s is declared but not in the table" % name
+        res, bound = _lib.PROTOTYPES[name]
+        _agrees(res, ret, name + " returns")
+        args = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
+        assert len(args) == len(bound), "%s: %d arguments declared, %d bound" % (name, len(args), len(bound))
+        for j, (a, t) in enumerate(zip(args, bound)):
+            m = re.fullmatch(r"(.*?)\b[A-Za-z_]\w*\s*((?:\[\w*\])?)", a)             # type, parameter name, [n]
+            assert m and m.group(1).strip(), "%s: argument %d (%r) does not read as `type name`" % (name, j, a)
+            _agrees(t, m.group(1) + m.group(2), "%s argument %d" % (name, j))
+        n_args += len(args)
+    assert sorted(seen) == declared() and len(seen) == len(_lib.PROTOTYPES), set(declared()) ^ seen
+    assert n_args == sum(len(a) for _, a in _lib.PROTOTYPES.values()) > 0
+
+
 def test_summary_struct_layout_matches_header():
     from pyfastx_amd import _lib, shard
     assert C.sizeof(_lib.ShardSummary) == 8 * shard.NWORDS == 224
