@@ -353,6 +353,38 @@ int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const uint8_t *rpat
                            uint64_t anchor, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
                            uint8_t **strand, uint8_t **mismatch, int64_t *n_hits, int64_t *counts);
 
+/* ------------------------------------------------------------------ search with insertions and deletions
+ * Extension (nearest reference function: Sequence.search, sequence.c:519-558, exact and first hit only).  Every place in the
+ * `seq` of the records -- the text fx_fasta_search walks, with its rules: bytes 10/13/32 dropped, across line ends and never
+ * across records, cut at slen -- where the pattern ENDS within max_edits edits (Levenshtein distance: a substituted, an
+ * inserted and a deleted letter cost 1 each), with its distance and the start of its shortest span
+ * (pyfastx_amd/csrc/fx_search_edit.hpp: Myers' bit-vector column per strand).  A text letter matches a pattern letter
+ * exactly where fx_fasta_search would match it under the same mode.
+ *   pat, rpat, plen, mode, ids, n_ids, strand, counts: as for fx_fasta_search.
+ *   max_edits    0..min(8, plen - 1).
+ *   Ends         letter e of a record is an end on a strand when D[e], the least distance between that strand's pattern and
+ *                any stretch of the text that ends with letter e, is at most max_edits.
+ *   Rows         one per reported end: stop = e + 1, edits = D[e], start = stop - m for the smallest m such that the last m
+ *                letters up to e are at distance D[e] (so plen - max_edits <= stop - start <= plen + max_edits); by
+ *                (record, stop), '+' before '-' at one stop; starts are not monotone.
+ *   report       FX_EDIT_ALL: every end (with max_edits = 0: fx_fasta_search's hits, row for row).  FX_EDIT_BEST: per record
+ *                and strand the ends e such that e - 1 is no end or D[e-1] > D[e], and e + 1 is no end or D[e+1] >= D[e]:
+ *                the leftmost minimum of every dip, at least one per stretch of consecutive ends.
+ *   rec, start, stop, strand, edits   the rows: pinned blocks of fx_pinned_alloc that belong to the caller (fx_pinned_free
+ *                each); edits is uint8, 0..max_edits.
+ *   n_hits, n_ends   *n_hits = the rows `report` gives, *n_ends = the ends in front of the filter (equal under FX_EDIT_ALL).
+ *   cap          room for ENDS, since every end is held on the device before the filter: *n_ends above cap gives FX_ERANGE
+ *                and nothing is allocated, however few rows FX_EDIT_BEST would keep.  cap = 0 with counts != NULL: counts
+ *                only -- the rows `report` would give per searched record on + and on -; no start is computed and no row
+ *                comes home.
+ * FX_EINVAL: plen outside 1..64, max_edits outside its range, an unknown report (these three are refused before the handle is
+ * looked at), no strand, a null pattern of a strand asked for, a null output, a byte-range shard.  FX_ESTATE: no table built.
+ * FX_ERANGE: more than cap ends. */
+enum { FX_EDIT_ALL = 0, FX_EDIT_BEST = 1 };
+int fx_fasta_search_edit(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int32_t max_edits,
+                         int32_t report, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
+                         int64_t **stop, uint8_t **strand, uint8_t **edits, int64_t *n_hits, int64_t *n_ends, int64_t *counts);
+
 /* ------------------------------------------------------------------ position weight matrices
  * Extension.  Every window of plen letters of the `seq` of the records -- the text fx_fasta_search walks, with its rules:
  * bytes 10/13/32 dropped, windows across line ends and never across records, cut at slen -- whose SCORE under one position

@@ -13,6 +13,7 @@ _LIB = None
 FX_HOST, FX_DEVICE = 0, 1
 FX_UPPER, FX_REVERSE, FX_COMPLEMENT, FX_RAW = 1, 2, 4, 8
 FX_SEARCH_DEGENERATE, FX_SEARCH_UPPER, FX_SEARCH_PLUS, FX_SEARCH_MINUS = 1, 2, 4, 8
+FX_EDIT_ALL, FX_EDIT_BEST = 0, 1
 FX_KMER_CANONICAL = 1
 FX_MZ_CANONICAL, FX_MZ_LEX = 1, 2
 FX_SK_CANONICAL, FX_SK_POOLED = 1, 2
@@ -105,6 +106,7 @@ PROTOTYPES = {
     "fx_fasta_fetch_alloc": (i32, [vp, i64, vp, vp, vp, i32, vp, pvp, pvp, pi64]),
     "fx_fasta_search": (i32, [vp, vp, vp, i32, i32, vp, i64, i64, pvp, pvp, pvp, pi64, vp]),
     "fx_fasta_search_approx": (i32, [vp, vp, vp, i32, i32, i32, u64, vp, i64, i64, pvp, pvp, pvp, pvp, pi64, vp]),
+    "fx_fasta_search_edit": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, i64, i64, pvp, pvp, pvp, pvp, pvp, pi64, pi64, vp]),
     "fx_fasta_pwm_scan": (i32, [vp, vp, i32, i32, i32, vp, i64, i64, pvp, pvp, pvp, pvp, pi64, vp]),
     "fx_fasta_pwm_best": (i32, [vp, vp, i32, i32, vp, i64, vp, vp]),
     "fx_fasta_minimizers": (i32, [vp, i32, i32, i32, vp, i64, i64, pvp, pvp, pvp, pvp, pi64, vp]),
@@ -1218,6 +1220,20 @@ class Blob:
         `anchor` (bit j = letter j of `pattern`) (fx_fasta_search_approx) -> (n_hits, (rec, start, strand, mismatch) pinned
         arrays or None, counts or None)."""
         return self.fasta_search(pattern, rpattern, mode, ids, cap, counts, int(max_mismatch), anchor)
+
+    def fasta_search_edit(self, pattern, rpattern, mode, max_edits, report=FX_EDIT_BEST, ids=None, cap=0, counts=False):
+        """Every end of the pattern within max_edits edits (Levenshtein) on the resident table, all of them or the best of every
+        dip (report: FX_EDIT_ALL / FX_EDIT_BEST) (fx_fasta_search_edit) -> (n_hits, n_ends, (rec, start, stop, strand, edits)
+        pinned arrays or None, counts int64[n_sel, 2] or None); more than `cap` ENDS raise FxError(FX_ERANGE) whose .n_ends is
+        the true count.  cap = 0 with counts: counts only."""
+        plen = len(pattern if pattern is not None else rpattern)
+        pat = None if pattern is None else np.frombuffer(bytes(pattern), dtype=np.uint8)
+        rpat = None if rpattern is None else np.frombuffer(bytes(rpattern), dtype=np.uint8)
+        ids, n_ids = _sel(ids)
+        cnt = np.zeros((self._n_selected(ids, n_ids), 2), dtype=np.int64) if counts else None
+        rows, (n, n_ends) = _call(lib().fx_fasta_search_edit, (self._h, pat, rpat, plen, int(mode), int(max_edits), int(report), ids, n_ids, int(cap)),
+                                  (np.int64, np.int64, np.int64, np.uint8, np.uint8), counters=(0, 0), err=("n_ends", 1), tail=(cnt,))
+        return n, n_ends, (None if rows[0] is None else rows), cnt
 
     def _n_selected(self, ids, n_ids):
         if ids is not None:

@@ -862,6 +862,32 @@ class Fasta(_fxobj.FastaCore):
         blob = self._search_blob()
         return search.approx_count_blob(blob, pattern, mismatches, anchor, strand, degenerate, self._uppercase, self._st.device)
 
+    def search_edit(self, pattern, edits, strand="both", degenerate=False, report="best", ids=None, max_hits=10**8):
+        """Extension: search_all with up to `edits` (0..8, below the pattern's length) substituted, inserted or deleted
+        letters -- every place of a record's `seq` where the pattern ENDS within that Levenshtein distance: letter e is an end
+        when D[e], the least distance between the pattern and any stretch of the text that ends with letter e, is at most
+        `edits`.  A text letter matches a pattern letter exactly where search_all would match it (byte equality, or the IUPAC
+        subset rule under degenerate=True); '-' searches the reverse complement on the forward text, as search_all does.
+        -> EditHits(ids, starts, stops, strands, edits): per reported end stop = e + 1, edits = D[e] (uint8) and start = the
+        beginning of the SHORTEST stretch that has that distance (a hit never begins with a letter it pays for), so
+        len(pattern) - edits <= stop - start <= len(pattern) + edits; ordered by (record, stop), '+' before '-' at one
+        stop -- the starts are not monotone.  report='all': every end (with edits=0: search_all's rows).  report='best':
+        per record and strand the leftmost minimum of every dip of D -- end e stays when e - 1 is no end or has more
+        edits, and e + 1 is no end or has no fewer; every stretch of consecutive ends keeps at least one row.  ids: as for
+        search_all.  max_hits bounds the ENDS, which the device holds before 'best' thins them out: more of them is a
+        ValueError with their count.  On the GPU from the resident stream (csrc/fx_search_edit.hpp)."""
+        from . import search
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        blob = self._search_blob()
+        return search.edit_blob(blob, pattern, edits, strand, degenerate, report, self._uppercase, sel, max_hits, self._st.device)
+
+    def search_edit_counts(self, pattern, edits, strand="both", degenerate=False, report="best"):
+        """Extension: rows of search_edit per record -> int64[len(fa), 2] (column 0 '+', column 1 '-'); the rows themselves
+        are never materialised and no start is computed."""
+        from . import search
+        blob = self._search_blob()
+        return search.edit_count_blob(blob, pattern, edits, strand, degenerate, report, self._uppercase, self._st.device)
+
     def pwm_scan(self, pwm, min_score=None, threshold=None, pvalue=None, strand="both", ids=None, max_hits=10**8):
         """Extension: every window of len(pwm) letters of a record's `seq` whose score under the position weight matrix
         `pwm` (pwm.Pwm) reaches a threshold, on strand '+', '-' or 'both'.  Letters A C G T in either case, U = T

@@ -97,6 +97,30 @@ __device__ __forceinline__ void run_walk(const SearchPlan &P, int64_t lo, int64_
     }
 }
 
+// run_walk that hands f(c, at) the address of the byte as well (P.base[at] is c).  A copy, not a wrapper of or under run_walk:
+// with one body for both, the kernels that stand on run_walk compile to other code.
+template <class F>
+__device__ __forceinline__ void run_walk_at(const SearchPlan &P, int64_t lo, int64_t hi, F &&f) {
+    auto feed = [&](uint32_t x, bool live, int64_t at) {
+        if (!live || srch_space(x)) return;
+        f(x, at);
+    };
+    int64_t c = lo & ~(int64_t)15;
+    uint4 v = *reinterpret_cast<const uint4 *>(P.base + c);
+    for (; c < hi; c += 16) {
+        const uint4 cur = v;
+        if (c + 16 < hi) v = *reinterpret_cast<const uint4 *>(P.base + c + 16);
+        const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
+        if (c >= lo && c + 16 <= hi) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, true, c + i);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) feed((w[i >> 2] >> (8 * (i & 3))) & 0xFFu, c + i >= lo && c + i < hi, c + i);
+        }
+    }
+}
+
 // Walk one run: raw bytes [lo, hi) of the address space, after a warm-up on the L - 1 kept bytes in front of it.  Kept bytes
 // whose local index (0 at lo) is below `limit` may end a hit; hits go to on_hit(kidx, fwd, rev).  -> kept bytes in [lo, hi).
 template <bool WIDE, class F>

@@ -44,6 +44,7 @@
 #include "fx_kseq.hpp"
 #include "fx_search.hpp"
 #include "fx_search_approx.hpp"
+#include "fx_search_edit.hpp"
 #include "fx_pwm.hpp"
 #include "fx_annot.hpp"
 #include "fx_tandem.hpp"
@@ -334,10 +335,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_ESEARCH_COUNT, K_ESEARCH_EMIT, K_ESEARCH_BEST, K_ESEARCH_START, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_esearch_count", "k_esearch_emit", "k_esearch_best", "k_esearch_start", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce"};
 
 struct Prof {
     bool on = false;
@@ -3922,16 +3923,26 @@ struct HitRuns {
 //   emit(R, list, n_list, K, Pp, Pm, o_rec, o_start, o_strand, o_extra)     the hits of the runs that have some
 // with the scans, the per-record counts, the totals home, the cap, the pinned blocks and the way home between them.
 // extra_size: bytes per hit of the form's fourth column (0: none), whose pinned block goes to *extra.
-template <class Count, class Fix, class Emit>
-static int run_hits(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t *counts,
-                    int extra_size, const char *what, Count &&count, Fix &&fix, Emit &&emit, int64_t **rec, int64_t **start, uint8_t **strand,
-                    void **extra, int64_t *n_hits) {
-    int rc;
+//
+// hit_scans is the part in front of the cap, which fx_fasta_search_edit (whose rows pass a filter and a start pass before they
+// go home) shares: the head, count, the kept-byte scan, fix, the hit scans, the per-record counts where asked for, the totals
+// home -> S.total hits in S.n_list runs.  S.R.P.n_runs == 0 afterwards: nothing was launched.
+struct HitScans {
     HitRuns R;
+    int64_t *K = nullptr, *Pp = nullptr, *Pm = nullptr, *NZ = nullptr;      // n_runs + 1 each: kept bytes, hits on +, on -, runs with a hit
+    unsigned grid_sel = 1;
+    int64_t total = 0, n_list = 0;
+};
+template <class Count, class Fix>
+static int hit_scans(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int64_t *counts,
+                     Count &&count, Fix &&fix, HitScans &S) {
+    int rc;
+    HitRuns &R = S.R;
     if ((rc = R.open(h, st, K_SEARCH_SCAN, masks, plen, ids, n_ids, 4, counts)) || R.P.n_runs == 0) return rc;
     const SearchPlan &P = R.P;
-    int64_t *K = R.pref.p, *Pp = K + R.nr1, *Pm = K + 2 * R.nr1, *NZ = K + 3 * R.nr1;
-    const unsigned grid_sel = nblocks(P.n_sel, BLOCK);
+    int64_t *K = S.K = R.pref.p, *Pp = S.Pp = K + R.nr1, *Pm = S.Pm = K + 2 * R.nr1;
+    S.NZ = K + 3 * R.nr1;
+    const unsigned grid_sel = S.grid_sel = nblocks(P.n_sel, BLOCK);
     // count pass, kept-byte scan, the cut at slen, hit scans
     count(R);
     if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{R.packed.p}, P.n_runs, K, R.d_tot))) return rc;
@@ -3946,7 +3957,22 @@ static int run_hits(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen,
     }
     const int64_t *tot = R.tot.get();
     if ((rc = read_home(h, R.tot.get(), R.d_tot, 24))) return rc;
-    const int64_t total = tot[0] + tot[1], n_list = tot[2];
+    S.total = tot[0] + tot[1];
+    S.n_list = tot[2];
+    return FX_OK;
+}
+
+template <class Count, class Fix, class Emit>
+static int run_hits(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t *counts,
+                    int extra_size, const char *what, Count &&count, Fix &&fix, Emit &&emit, int64_t **rec, int64_t **start, uint8_t **strand,
+                    void **extra, int64_t *n_hits) {
+    int rc;
+    HitScans S;
+    if ((rc = hit_scans(h, st, masks, plen, ids, n_ids, counts, count, fix, S)) || S.R.P.n_runs == 0) return rc;
+    HitRuns &R = S.R;
+    const SearchPlan &P = R.P;
+    const int64_t *K = S.K, *Pp = S.Pp, *Pm = S.Pm, *NZ = S.NZ;
+    const int64_t total = S.total, n_list = S.n_list;
     *n_hits = total;
     if (cap == 0 && counts) { h->prof.drain(); return FX_OK; }
     if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
@@ -4064,6 +4090,130 @@ extern "C" int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const ui
         return fail(FX_EINVAL, "max_mismatch %d outside 0..%d", (int)max_mismatch, std::min(8, plen - 1));
     if (plen < 64 && (anchor >> plen)) return fail(FX_EINVAL, "anchor position at or above the pattern length %d", (int)plen);
     return fasta_search(h, pat, rpat, plen, mode, max_mismatch, anchor, ids, n_ids, cap, rec, start, strand, mismatch, n_hits, counts);
+}
+
+// (fx_search_edit.hpp)  What the numbers alone decide is refused first, before the handle is looked at.  hit_scans with the
+// count and fix kernels of the form gives the ENDS; they are emitted on the device, report = best flags and scans them there,
+// and only the rows that stay get a start and go home.
+extern "C" int fx_fasta_search_edit(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int32_t max_edits,
+                                    int32_t report, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
+                                    int64_t **stop, uint8_t **strand, uint8_t **edits, int64_t *n_hits, int64_t *n_ends, int64_t *counts) {
+    if (n_hits) *n_hits = 0;
+    if (n_ends) *n_ends = 0;
+    if (rec) *rec = nullptr; if (start) *start = nullptr; if (stop) *stop = nullptr; if (strand) *strand = nullptr; if (edits) *edits = nullptr;
+    if (plen < 1 || plen > 64) return fail(FX_EINVAL, "pattern length %d outside 1..64", (int)plen);
+    if (max_edits < 0 || max_edits > std::min(8, plen - 1))
+        return fail(FX_EINVAL, "max_edits %d outside 0..%d", (int)max_edits, std::min(8, plen - 1));
+    if (report != FX_EDIT_ALL && report != FX_EDIT_BEST) return fail(FX_EINVAL, "report %d is neither FX_EDIT_ALL nor FX_EDIT_BEST", (int)report);
+    if (!h || !n_hits || !n_ends) return fail(FX_EINVAL, "null argument");
+    if (!(mode & (FX_SEARCH_PLUS | FX_SEARCH_MINUS))) return fail(FX_EINVAL, "no strand selected");
+    if (((mode & FX_SEARCH_PLUS) && !pat) || ((mode & FX_SEARCH_MINUS) && !rpat)) return fail(FX_EINVAL, "null pattern");
+    const bool counts_only = cap == 0 && counts, best = report == FX_EDIT_BEST;
+    if (cap < 0 || (!counts_only && (!rec || !start || !stop || !strand || !edits))) return fail(FX_EINVAL, "null output");
+    int rc;
+    if ((rc = fasta_state(h, "hits", ids, n_ids)) || (rc = fasta_device(h))) return rc;
+    std::vector<ulonglong2> masks(256);
+    {
+        std::vector<uint64_t> f(256, 0), r(256, 0);
+        if (((mode & FX_SEARCH_PLUS) && !search_masks(pat, plen, mode, f.data())) ||
+            ((mode & FX_SEARCH_MINUS) && !search_masks(rpat, plen, mode, r.data())))
+            return fail(FX_EINVAL, "a pattern letter is not an IUPAC code");
+        for (int c = 0; c < 256; ++c) masks[c] = make_ulonglong2(f[c], r[c]);
+    }
+    const int64_t n_sel = ids ? n_ids : h->n_hdr;
+    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    if (n_sel == 0) return FX_OK;
+    Staged st(h);
+    const ulonglong2 *d_masks = nullptr;
+    if ((rc = st.up(h, masks.data(), 256, &d_masks))) return rc;
+    const bool wide = plen > 32;
+    const int k = max_edits;
+    HitScans S;
+    // the per-record counts of report = all are those of the ends; report = best counts its rows behind the filter
+    rc = hit_scans(
+        h, st, d_masks, plen, ids, n_ids, best ? nullptr : counts,
+        [&](HitRuns &R) { with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_ESEARCH_COUNT, k_esearch_count<W()>, dim3(R.grid_runs), dim3(BLOCK), R.P, k, R.packed.p); }); },
+        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
+            with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_esearch_fix<W()>, dim3(grid_sel), dim3(BLOCK), R.P, k, K, R.packed.p); });
+        },
+        S);
+    if (rc) return rc;
+    if (best && counts) memset(counts, 0, (size_t)n_sel * 16);
+    if (S.R.P.n_runs == 0) return FX_OK;
+    const SearchPlan &P = S.R.P;
+    const int64_t total = S.total;
+    *n_ends = total;
+    if (!best) *n_hits = total;
+    if (counts_only && (!best || total == 0)) { h->prof.drain(); return FX_OK; }
+    if (!counts_only && total > cap) {
+        h->prof.drain();
+        return fail(FX_ERANGE, "%lld ends, more than the %lld asked for", (long long)total, (long long)cap);
+    }
+    PinnedOut<5> out(h);                       // rec, start, stop, strand, edits
+    auto blocks = [&](int64_t n) {
+        const int64_t m = std::max<int64_t>(n, 1);
+        return out.alloc(0, m * 8) && out.alloc(1, m * 8) && out.alloc(2, m * 8) && out.alloc(3, m) && out.alloc(4, m);
+    };
+    if (total == 0) {
+        if (!blocks(0)) return fail(FX_ENOMEM, "pinned blocks for %lld rows", 0ll);
+        h->prof.drain();
+        out.release(rec, start, stop, strand, edits);
+        return FX_OK;
+    }
+    // the ends on the device: record, stop, address of the end letter; strand, edits, (best) the flags
+    ScratchBuf<int64_t> e64, list;
+    ScratchBuf<uint8_t> e8;
+    if ((rc = e64.alloc(h->device, 3 * total, h->stream)) || (rc = e8.alloc(h->device, 3 * total, h->stream)) ||
+        (rc = list.alloc(h->device, S.n_list, h->stream)))
+        return rc;
+    int64_t *e_rec = e64.p, *e_stop = e64.p + total, *e_at = e64.p + 2 * total;
+    uint8_t *e_strand = e8.p, *e_edits = e8.p + total, *keep = e8.p + 2 * total;
+    hipLaunchKernelGGL(k_search_list, dim3(S.R.grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)S.R.packed.p, (const int64_t *)S.NZ, P.n_runs, list.p);
+    with_bool(wide, [&](auto W) {
+        FX_LAUNCH(h, K_ESEARCH_EMIT, k_esearch_emit<W()>, dim3(nblocks(S.n_list, BLOCK)), dim3(BLOCK), P, k, (const int64_t *)list.p, S.n_list,
+                  (const int64_t *)S.K, (const int64_t *)S.Pp, (const int64_t *)S.Pm, e_rec, e_stop, e_at, e_strand, e_edits);
+    });
+    int64_t n_rows = total;
+    const int64_t *pos = nullptr;
+    ScratchBuf<int64_t> posbuf;
+    if (best) {
+        FX_LAUNCH(h, K_ESEARCH_BEST, k_esearch_best, dim3(nblocks(total, BLOCK)), dim3(BLOCK), (const int64_t *)e_rec, (const int64_t *)e_stop,
+                  (const uint8_t *)e_strand, (const uint8_t *)e_edits, total, keep);
+        if (counts) {                          // rows per record and strand: differences of the flags' prefixes at the records' first ends
+            ScratchBuf<int64_t> F;
+            int64_t *cnt_dev = nullptr;
+            if ((rc = F.alloc(h->device, 2 * (total + 1), h->stream)) || (rc = st.scratch<int64_t>(2 * n_sel, &cnt_dev)) ||
+                (rc = sscan<2>(h, st, K_ESEARCH_BEST, EdLdKeep{keep, e_strand}, total, F.p, S.R.d_tot)))
+                return rc;
+            FX_LAUNCH(h, K_ESEARCH_BEST, k_esearch_rec_counts, dim3(S.grid_sel), dim3(BLOCK), (const int64_t *)P.run0, P.n_sel, (const int64_t *)S.Pp,
+                      (const int64_t *)S.Pm, (const int64_t *)F.p, total, cnt_dev);
+            int64_t *tot = S.R.tot.get();
+            if ((rc = home(h, "edit search counts", {{counts, cnt_dev, n_sel * 16}, {tot, S.R.d_tot, 16}}))) return rc;
+            *n_hits = tot[0] + tot[1];
+            if (counts_only) return FX_OK;
+        }
+        int64_t *sums = nullptr;
+        if ((rc = sscan<1>(h, st, K_ESEARCH_BEST, QcLdPass{keep}, total, nullptr, S.R.d_tot, &sums)) || (rc = read_home(h, &n_rows, S.R.d_tot, 8)))
+            return rc;
+        if (n_rows <= 0 || n_rows > total) return fail(FX_EDEVICE, "edit search: %lld rows out of %lld ends", (long long)n_rows, (long long)total);
+        if ((rc = posbuf.alloc(h->device, n_rows, h->stream))) return rc;
+        FX_LAUNCH(h, K_ESEARCH_BEST, k_fq_select_emit, dim3(nblocks(total, SRCH_CHUNK)), dim3(BLOCK), (const uint8_t *)keep, total, (const int64_t *)sums,
+                  posbuf.p);
+        pos = posbuf.p;
+    }
+    *n_hits = n_rows;
+    if (!blocks(n_rows)) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n_rows);
+    ScratchBuf<int64_t> o64;
+    ScratchBuf<uint8_t> o8;
+    if ((rc = o64.alloc(h->device, 3 * n_rows, h->stream)) || (rc = o8.alloc(h->device, 2 * n_rows, h->stream))) return rc;
+    FX_LAUNCH(h, K_ESEARCH_START, k_esearch_start, dim3(nblocks(n_rows, BLOCK)), dim3(BLOCK), P, k, pos, n_rows, (const int64_t *)e_rec,
+              (const int64_t *)e_stop, (const int64_t *)e_at, (const uint8_t *)e_strand, (const uint8_t *)e_edits, o64.p, o64.p + n_rows,
+              o64.p + 2 * n_rows, o8.p, o8.p + n_rows);
+    if ((rc = home(h, "edit search rows", {{out.p[0], o64.p, n_rows * 8}, {out.p[1], o64.p + n_rows, n_rows * 8},
+                                           {out.p[2], o64.p + 2 * n_rows, n_rows * 8}, {out.p[3], o8.p, n_rows}, {out.p[4], o8.p + n_rows, n_rows}})))
+        return rc;
+    out.release(rec, start, stop, strand, edits);
+    return FX_OK;
 }
 
 // ------------------------------------------------------------------ position weight matrices (fx_pwm.hpp)

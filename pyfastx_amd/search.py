@@ -3,7 +3,8 @@
 Fasta.search_all / search_counts check the pattern here and hand it to fx_fasta_search (csrc/fx_search.hpp): every
 overlapping hit in the `seq` of the records, on one or both strands, exact or with IUPAC codes.  Fasta.search_approx /
 search_approx_counts allow up to `mismatches` substituted letters per hit, none of them inside an anchor
-(fx_fasta_search_approx, csrc/fx_search_approx.hpp)."""
+(fx_fasta_search_approx, csrc/fx_search_approx.hpp).  Fasta.search_edit / search_edit_counts allow up to `edits`
+substituted, inserted or deleted letters (fx_fasta_search_edit, csrc/fx_search_edit.hpp)."""
 from collections import namedtuple
 
 import numpy as np
@@ -12,9 +13,12 @@ from . import _lib
 
 SearchHits = namedtuple("SearchHits", ["ids", "starts", "stops", "strands"])
 ApproxHits = namedtuple("ApproxHits", ["ids", "starts", "stops", "strands", "mismatches"])
+EditHits = namedtuple("EditHits", ["ids", "starts", "stops", "strands", "edits"])
 
 MAX_PATTERN = 64
 MAX_MISMATCH = 8
+MAX_EDITS = 8
+_REPORTS = {"all": _lib.FX_EDIT_ALL, "best": _lib.FX_EDIT_BEST}
 
 # the base set of every IUPAC letter (U is T)
 IUPAC = {k: frozenset(v) for k, v in {
@@ -154,3 +158,56 @@ def approx_count_blob(blob, pattern, mismatches, anchor=None, strand="both", deg
         mode |= _lib.FX_SEARCH_UPPER
     _, _, counts = blob.fasta_search_approx(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, d, mask, cap=0, counts=True)
     return counts
+
+
+def compile_edit(pattern, edits, strand="both", degenerate=False, report="best", device=0):
+    """compile_pattern plus the edit budget and the report -> (mode bits, bytes on +, bytes on -, edits, report code).
+    TypeError for edits that is no integer or a report that is no string; ValueError for what compile_pattern refuses, edits
+    outside 0..min(8, len(pattern) - 1) or a report other than 'all' / 'best'.  Everything is checked before the '-' pattern
+    of an exact search is made."""
+    if isinstance(edits, bool) or not isinstance(edits, (int, np.integer)):
+        raise TypeError("edits must be an integer, not %r" % (edits,))
+    if not isinstance(report, str):
+        raise TypeError("report must be 'all' or 'best', not %r" % (report,))
+    if report not in _REPORTS:
+        raise ValueError("report must be 'all' or 'best', not %r" % (report,))
+    if strand not in _STRANDS:
+        raise ValueError("strand must be '+', '-' or 'both', not %r" % (strand,))
+    L = len(_as_text(pattern))
+    if not 1 <= L <= MAX_PATTERN:
+        raise ValueError("pattern length %d outside 1..%d" % (L, MAX_PATTERN))
+    if not 0 <= edits <= min(MAX_EDITS, L - 1):
+        raise ValueError("edits=%d outside 0..%d for a pattern of %d letters" % (edits, min(MAX_EDITS, L - 1), L))
+    mode, fwd, rev = compile_pattern(pattern, strand, degenerate, device)
+    return mode, fwd, rev, int(edits), _REPORTS[report]
+
+
+def edit_blob(blob, pattern, edits, strand="both", degenerate=False, report="best", uppercase=False, ids=None, max_hits=10**8,
+              device=0):
+    """Every end of `pattern` within `edits` edits on a Blob whose FASTA table is resident -> EditHits (arrays in pinned
+    memory; edits: uint8, the Levenshtein distance of every row).  max_hits bounds the ENDS, which the device holds before
+    report='best' thins them out."""
+    mode, fwd, rev, k, rep = compile_edit(pattern, edits, strand, degenerate, report, device)
+    if uppercase:
+        mode |= _lib.FX_SEARCH_UPPER
+    if max_hits < 0:
+        raise ValueError("max_hits must not be negative")
+    try:
+        total, _, rows, _ = blob.fasta_search_edit(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, k, rep, ids=ids, cap=int(max_hits))
+    except _lib.FxError as e:
+        n = getattr(e, "n_ends", 0)
+        if e.code == _lib.FX_ERANGE and n > max_hits:
+            raise ValueError("%d ends within %d edits, more than max_hits=%d" % (n, k, max_hits))
+        raise
+    if rows is None:
+        z = np.zeros(0, dtype=np.int64)
+        return EditHits(z, z.copy(), z.copy(), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8))
+    return EditHits(*rows)
+
+
+def edit_count_blob(blob, pattern, edits, strand="both", degenerate=False, report="best", uppercase=False, device=0):
+    """Rows of edit_blob per record on + and on - -> int64[n_records, 2]; the rows themselves never leave the device."""
+    mode, fwd, rev, k, rep = compile_edit(pattern, edits, strand, degenerate, report, device)
+    if uppercase:
+        mode |= _lib.FX_SEARCH_UPPER
+    return blob.fasta_search_edit(fwd if mode & _lib.FX_SEARCH_PLUS else None, rev, mode, k, rep, cap=0, counts=True)[3]
