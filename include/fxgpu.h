@@ -125,6 +125,12 @@ int fx_release_scratch(void);
  * bytes, one more of `cap` bytes comes back, keep_bytes are allowed in all.  -> 1: the new block is kept and the idle
  * blocks with evict[i] = 1 (the smallest, as many as needed) are freed; 0: the new block is freed and nothing else. */
 int fx_scratch_policy(const int64_t *idle_caps, int n, int64_t cap, int64_t keep_bytes, int32_t *evict);
+/* FX_DEBUG_FILL=<0..255> (decimal; read once at load; unset or empty: off) fills every block a plain device allocation or the
+ * scratch pool hands out, fresh or reused, with that byte over its whole capacity, the device waited for on both sides of the
+ * fill: a test mode that turns a forgotten clear into a wrong number (tests/test_gpu_clean_memory.py runs with 255).  The reuse
+ * of a handle's grow-only arrays, its per-call scratch arena among them, is not filled.  This reports that the mode was on: *byte = the value in force or -1,
+ * *blocks and *bytes = what has been filled since load (any pointer may be NULL). */
+int fx_debug_fill_info(int *byte, int64_t *blocks, int64_t *bytes);
 /* Pinned (page-locked) host memory out of a per-process pool, for the arrays a caller hands to the batched entry
  * points with FX_HOST: answers land in it by DMA -- no bounce buffer, no first-touch page faults of a fresh buffer
  * (what the copy out of pyfastx_index_fill_cache's cache costs the reference per getter, sequence.c:346-347, is paid

@@ -178,6 +178,7 @@ PROTOTYPES = {
     "fx_fxi_join_write": (i32, [vp, cs, i32, i32, i64, i64, vp, i64, pf64]),
     "fx_fxi_join_end": (None, [vp]),
     "fx_scratch_policy": (i32, [vp, i32, i64, i64, vp]),
+    "fx_debug_fill_info": (i32, [pi32, pi64, pi64]),
     "fx_open_file_async": (i32, [cs, i32, pvp]),
     "fx_stage_wait": (i32, [vp, i64]),
     "fx_sync": (i32, [vp]),
@@ -225,6 +226,13 @@ def build_laps():
     a = (C.c_double * 8)()
     lib().fx_build_laps(a)
     return {"sample": float(a[0]), "count_pass_enqueue": float(a[1]), "count_pass_wait": float(a[2]), "table_alloc": float(a[4]), "rows": float(a[5])}
+
+
+def debug_fill_info():
+    """(byte, blocks, bytes) of FX_DEBUG_FILL: the byte in force or -1, and what has been filled since load."""
+    b, n, t = C.c_int(0), C.c_int64(0), C.c_int64(0)
+    lib().fx_debug_fill_info(C.byref(b), C.byref(n), C.byref(t))
+    return int(b.value), int(n.value), int(t.value)
 
 
 def fxi_presize_begin(path, nbytes, device=-1):

@@ -111,9 +111,40 @@ extern "C" int fx_device_count(void) {
 
 // ------------------------------------------------------------------ handle
 static void scratch_trim();              // the idle blocks of the scratch pool below go back to the driver
+// FX_DEBUG_FILL (read once at load; unset or empty: off; else a byte value 0..255): every block dev_malloc or the scratch pool
+// hands out is filled with that byte over its whole capacity first, so a test can show that no result depends on what
+// device memory held before a call (a fresh hipMalloc of a few KB very often comes back zero and hides a missing clear).
+// The handle streams are non-blocking, a memset on the null stream orders with nothing: the device is waited for on both
+// sides of the fill.  Off, it is one branch on a constant.  DevBuf's reuse path is NOT filled: some members are tables that
+// must outlive an alloc of the same size -- and so the handle's arena (Staged, below) is filled when it grows and when a
+// request spills past it, not when a later call takes the same bytes again.
+static const int g_fill_byte = [] {
+    const char *e = getenv("FX_DEBUG_FILL");
+    if (!e || !*e) return -1;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);                      // decimal only: 010 is ten, 0x7f is no value
+    if (end == e || *end || v < 0 || v > 255) { fprintf(stderr, "[fxgpu] FX_DEBUG_FILL=%s is no byte value 0..255: off\n", e); return -1; }
+    return (int)v;
+}();
+static std::atomic<int64_t> g_fill_blocks{0}, g_fill_bytes{0};
+static hipError_t debug_fill(void *p, size_t cap) {        // the current device is the block's
+    if (g_fill_byte < 0 || !p || !cap) return hipSuccess;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemset(p, g_fill_byte, cap);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) { g_fill_blocks.fetch_add(1, std::memory_order_relaxed); g_fill_bytes.fetch_add((int64_t)cap, std::memory_order_relaxed); }
+    return e;
+}
+extern "C" int fx_debug_fill_info(int *byte, int64_t *blocks, int64_t *bytes) {
+    if (byte) *byte = g_fill_byte;
+    if (blocks) *blocks = g_fill_blocks.load(std::memory_order_relaxed);
+    if (bytes) *bytes = g_fill_bytes.load(std::memory_order_relaxed);
+    return FX_OK;
+}
 static hipError_t dev_malloc(void **p, size_t bytes) {     // hipMalloc; when memory is short the pool is emptied and it is tried again
     hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); scratch_trim(); e = hipMalloc(p, bytes); }
+    if (e == hipSuccess && g_fill_byte >= 0 && (e = debug_fill(*p, bytes)) != hipSuccess) { (void)hipFree(*p); *p = nullptr; }
     return e;
 }
 
@@ -207,6 +238,11 @@ struct ScratchPool {
             else ++i;
     }
     void *get(int dev, size_t bytes, size_t *cap) {
+        void *p = get_block(dev, bytes, cap);
+        if (p && g_fill_byte >= 0 && debug_fill(p, *cap) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p); p = nullptr; }
+        return p;
+    }
+    void *get_block(int dev, size_t bytes, size_t *cap) {
         std::vector<Block> old;
         {
             std::lock_guard<std::mutex> g(mu);
@@ -3018,7 +3054,7 @@ struct Staged {
             return p;
         }
         void *d = nullptr;
-        if (hipMalloc(&d, (size_t)bytes) != hipSuccess) return nullptr;
+        if (dev_malloc(&d, (size_t)bytes) != hipSuccess) return nullptr;     // (filled under FX_DEBUG_FILL, as every fresh block is)
         spill.push_back(d);
         return d;
     }
@@ -7883,9 +7919,9 @@ extern "C" int fx_comm_init(int rank, int world, const uint8_t id[128], int devi
     memcpy(&u, id, 128);
     ncclResult_t r = rccl().CommInitRank(&c->comm, world, u, rank);
     if (r != ncclSuccess) { c->comm = nullptr; fx_comm_destroy(c); return fail(FX_EDEVICE, "ncclCommInitRank: %s", rccl().GetErrorString(r)); }
-    hipError_t e = hipMalloc((void **)&c->d_send, sizeof(fx_shard_summary));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_recv, sizeof(fx_shard_summary) * (size_t)world);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_buf, (size_t)COMM_SLOT * (size_t)(world + 1));
+    hipError_t e = dev_malloc((void **)&c->d_send, sizeof(fx_shard_summary));
+    if (e == hipSuccess) e = dev_malloc((void **)&c->d_recv, sizeof(fx_shard_summary) * (size_t)world);
+    if (e == hipSuccess) e = dev_malloc((void **)&c->d_buf, (size_t)COMM_SLOT * (size_t)(world + 1));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { fx_comm_destroy(c); return fail(FX_ENOMEM, "fx_comm_init: %s", hipGetErrorString(e)); }
     *out = c;

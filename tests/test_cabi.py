@@ -90,6 +90,22 @@ def test_no_cpu_fallback_without_gpu():
         pyfastx_amd.Fasta(os.path.join(ROOT, "tests", "data", "test.fa"), memory_index=True)
 
 
+@pytest.mark.parametrize("value,byte", [(None, -1), ("", -1), ("255", 255), ("0", 0), ("010", 10), ("0x7f", -1), ("256", -1), ("-1", -1), ("12x", -1)])
+def test_debug_fill_switch_is_read_once_at_load(value, byte):
+    """FX_DEBUG_FILL: unset or empty is off, a decimal 0..255 the byte in force, anything else off; nothing is filled before a block is
+    asked for.  A process of its own each: the library reads the variable when it is loaded."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "FX_DEBUG_FILL"}
+    env["FX_NO_TORCH"] = "1"
+    if value is not None:
+        env["FX_DEBUG_FILL"] = value
+    r = subprocess.run([sys.executable, "-c", "from pyfastx_amd import _lib; print(*_lib.debug_fill_info())"], env=env, cwd=ROOT,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split() == [str(byte), "0", "0"], (r.stdout, r.stderr[-500:])
+
+
 def test_missing_file_status():
     from pyfastx_amd import _lib
     h = C.c_void_p()
