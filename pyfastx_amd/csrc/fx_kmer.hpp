@@ -219,18 +219,12 @@ __global__ __launch_bounds__(BLOCK) void k_kmer_fix(SearchPlan P, int k, const i
                                                    unsigned long long *__restrict__ table) {
     const int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= P.n_sel) return;
-    const int64_t g0 = P.run0[s], g1 = P.run0[s + 1];
-    const int64_t slen = P.slen[srch_rec(P, s)];
-    if (g0 == g1 || K[g1] - K[g0] <= slen) return;
-    int64_t lo_g = g0, hi_g = g1 - 1;                        // first run whose kept bytes end past slen
-    while (lo_g < hi_g) { const int64_t m = (lo_g + hi_g) >> 1; if (K[m + 1] - K[g0] > slen) hi_g = m; else lo_g = m + 1; }
     unsigned long long *row = table + s * row_stride;
-    for (int64_t g = lo_g; g < g1; ++g) {
-        const int64_t base = K[g] - K[g0];
+    srch_cut(P, K, s, [&](int64_t g, int64_t base, int64_t slen) {
         int64_t r, b, lo, hi;
         srch_run(P, g, s, r, b, lo, hi);
         kmer_walk<uint32_t, CANON>(P, k, b, lo, hi, max(slen - base, (int64_t)0), INT64_MAX, [&](uint32_t code) { atomicAdd(row + code, ~0ull); });
-    }
+    });
 }
 
 // ------------------------------------------------------------------ FASTQ

@@ -105,71 +105,29 @@ __device__ __forceinline__ uint32_t mz_walk(const SearchPlan &P, int k, int w, u
     return kidx;
 }
 
-// per run: the packed word of fx_search.hpp (srch_pack): rows on '+', rows on '-', kept bytes (at most 256 rows in all)
+// The form of the three passes (k_hits_count / _fix / _emit of fx_search.hpp): no table, the lanes' rings in dynamic LDS; a
+// window is a row on one strand, its position lies `age` in front of the window's last k-mer, its column is the code.  A
+// window that ends in front of the cut reads nothing behind it.
 template <bool CANON, bool LEX>
-__global__ __launch_bounds__(BLOCK) void k_mz_count(SearchPlan P, int k, int w, uint32_t *__restrict__ packed) {
-    extern __shared__ __align__(16) uint64_t mz_ring[];
-    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= P.n_runs) return;
-    int64_t r, b, lo, hi;
-    srch_run(P, g, srch_slot(P, g), r, b, lo, hi);
-    uint32_t hp = 0, hm = 0;
-    const uint32_t kept = mz_walk<CANON, LEX>(P, k, w, mz_ring + threadIdx.x, b, lo, hi, INT64_MAX,
-                                              [&](uint32_t, int, uint32_t minus, uint64_t) { hp += 1u - minus; hm += minus; });
-    packed[g] = srch_pack(hp, hm, kept);
-}
-
-// The cut at slen, as k_search_fix makes it: one lane per selected record; where the kept bytes run past slen, the run that
-// crosses the cut is counted again with the cut and the runs behind it lose their rows.  A window that ends in front of the
-// cut reads nothing behind it.
-template <bool CANON, bool LEX>
-__global__ __launch_bounds__(BLOCK) void k_mz_fix(SearchPlan P, int k, int w, const int64_t *__restrict__ K, uint32_t *__restrict__ packed) {
-    extern __shared__ __align__(16) uint64_t mz_ring[];
-    const int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (s >= P.n_sel) return;
-    const int64_t g0 = P.run0[s], g1 = P.run0[s + 1];
-    const int64_t slen = P.slen[srch_rec(P, s)];
-    if (g0 == g1 || K[g1] - K[g0] <= slen) return;
-    int64_t lo_g = g0, hi_g = g1 - 1;                        // first run whose kept bytes end past slen
-    while (lo_g < hi_g) { const int64_t m = (lo_g + hi_g) >> 1; if (K[m + 1] - K[g0] > slen) hi_g = m; else lo_g = m + 1; }
-    for (int64_t g = lo_g; g < g1; ++g) {
-        const int64_t base = K[g] - K[g0];
-        uint32_t hp = 0, hm = 0;
-        const uint32_t kept = (packed[g] >> 18) & 511u;
-        if (base < slen && (packed[g] & 0x3FFFFu)) {
-            int64_t r, b, lo, hi;
-            srch_run(P, g, s, r, b, lo, hi);
-            mz_walk<CANON, LEX>(P, k, w, mz_ring + threadIdx.x, b, lo, hi, slen - base,
-                                [&](uint32_t, int, uint32_t minus, uint64_t) { hp += 1u - minus; hm += minus; });
-        }
-        packed[g] = srch_pack(hp, hm, kept);
+struct MzForm {
+    struct Win { int age; uint32_t minus; uint64_t key; };
+    using Col = uint64_t;
+    static constexpr bool COL = true, AT = false, ONE = true;
+    int k, w;
+    __device__ __forceinline__ uint64_t *table(const SearchPlan &) const {
+        extern __shared__ __align__(16) uint64_t mz_ring[];
+        return mz_ring + threadIdx.x;
     }
-}
-
-// The runs of the list walk again and store their rows at Pp[g] + Pm[g], by start: record, start, strand and the code.
-template <bool CANON, bool LEX>
-__global__ __launch_bounds__(BLOCK) void k_mz_emit(SearchPlan P, int k, int w, const int64_t *__restrict__ list, int64_t n_list,
-                                                   const int64_t *__restrict__ K, const int64_t *__restrict__ Pp,
-                                                   const int64_t *__restrict__ Pm, int64_t *__restrict__ o_rec,
-                                                   int64_t *__restrict__ o_start, uint8_t *__restrict__ o_strand,
-                                                   uint64_t *__restrict__ o_code) {
-    extern __shared__ __align__(16) uint64_t mz_ring[];
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_list) return;
-    const int64_t g = list[i], s = srch_slot(P, g);
-    int64_t r, b, lo, hi;
-    srch_run(P, g, s, r, b, lo, hi);
-    const int64_t base = K[g] - K[P.run0[s]];
-    const int64_t first = base - (k - 1);
-    const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;
-    int64_t o = Pp[g] + Pm[g];
-    mz_walk<CANON, LEX>(P, k, w, mz_ring + threadIdx.x, b, lo, hi, P.slen[r] - base, [&](uint32_t kidx, int age, uint32_t minus, uint64_t key) {
-        o_rec[o] = r;
-        o_start[o] = first + kidx - age;
-        o_strand[o] = minus ? '-' : '+';
-        o_code[o] = LEX ? key : mz_unmix(key, mask);
-        ++o;
-    });
-}
+    template <bool ROWS, class F>
+    __device__ __forceinline__ uint32_t walk(const SearchPlan &P, uint64_t *ring, int64_t b, int64_t lo, int64_t hi, int64_t limit, F &&on) const {
+        return mz_walk<CANON, LEX>(P, k, w, ring, b, lo, hi, limit,
+                                   [&](uint32_t kidx, int age, uint32_t minus, uint64_t key) { on(kidx, Win{age, minus, key}); });
+    }
+    __device__ __forceinline__ uint32_t plus(const Win &x) const { return 1u - x.minus; }
+    __device__ __forceinline__ uint32_t minus(const Win &x) const { return x.minus; }
+    __device__ __forceinline__ int64_t first(const SearchPlan &, int64_t base) const { return base - (k - 1); }
+    __device__ __forceinline__ int64_t pos(int64_t first, int64_t kidx, const Win &x) const { return first + kidx - x.age; }
+    __device__ __forceinline__ Col col(const Win &x, bool) const { return LEX ? x.key : mz_unmix(x.key, ((uint64_t)1 << (2 * k)) - 1); }
+};
 
 }  // namespace fx

@@ -95,78 +95,30 @@ __device__ __forceinline__ uint32_t pwm_walk(const SearchPlan &P, const int2 *ta
     return (uint32_t)kidx;
 }
 
-// per run: the packed word of fx_search.hpp (srch_pack): hits on +, hits on -, kept bytes (at most 256 each).  G = 0: the kept
-// bytes alone (what k_pwm_best needs before it can place the cut).
+// The form of the three passes (k_hits_count / _fix / _emit of fx_search.hpp): the thresholds decide what is a row, the score
+// is its column.  G = 0: the kept bytes alone (what k_pwm_best needs before it can place the cut).
 template <int G>
-__global__ __launch_bounds__(BLOCK) void k_pwm_count(SearchPlan P, PwmArg A, uint32_t *__restrict__ packed) {
-    __shared__ int2 tab[pwm_lds<G>()];
-    pwm_load_tab<G>(A, tab);
-    __syncthreads();
-    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= P.n_runs) return;
-    int64_t r, b, lo, hi;
-    srch_run(P, g, srch_slot(P, g), r, b, lo, hi);
-    uint32_t hp = 0, hm = 0;
-    const uint32_t kept = pwm_walk<G>(P, tab, b, lo, hi, INT64_MAX, [&](int64_t, int32_t sf, int32_t sr) {
-        hp += sf >= A.thr_f ? 1u : 0u;
-        hm += sr >= A.thr_r ? 1u : 0u;
-    });
-    packed[g] = srch_pack(hp, hm, kept);
-}
-
-// The cut at slen, as k_search_fix makes it: one lane per selected record; where the kept bytes run past slen, the run that
-// crosses the cut is counted again with the cut and the runs behind it lose their hits.
-template <int G>
-__global__ __launch_bounds__(BLOCK) void k_pwm_fix(SearchPlan P, PwmArg A, const int64_t *__restrict__ K, uint32_t *__restrict__ packed) {
-    __shared__ int2 tab[pwm_lds<G>()];
-    pwm_load_tab<G>(A, tab);
-    __syncthreads();
-    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (k >= P.n_sel) return;
-    const int64_t g0 = P.run0[k], g1 = P.run0[k + 1];
-    const int64_t slen = P.slen[srch_rec(P, k)];
-    if (g0 == g1 || K[g1] - K[g0] <= slen) return;
-    int64_t lo_g = g0, hi_g = g1 - 1;                        // first run whose kept bytes end past slen
-    while (lo_g < hi_g) { const int64_t m = (lo_g + hi_g) >> 1; if (K[m + 1] - K[g0] > slen) hi_g = m; else lo_g = m + 1; }
-    for (int64_t g = lo_g; g < g1; ++g) {
-        const int64_t base = K[g] - K[g0];
-        uint32_t hp = 0, hm = 0;
-        const uint32_t kept = (packed[g] >> 18) & 511u;
-        if (base < slen && (packed[g] & 0x3FFFFu)) {
-            int64_t r, b, lo, hi;
-            srch_run(P, g, k, r, b, lo, hi);
-            pwm_walk<G>(P, tab, b, lo, hi, slen - base, [&](int64_t, int32_t sf, int32_t sr) {
-                hp += sf >= A.thr_f ? 1u : 0u;
-                hm += sr >= A.thr_r ? 1u : 0u;
-            });
-        }
-        packed[g] = srch_pack(hp, hm, kept);
+struct PwmForm {
+    struct Win { int32_t sf, sr; };
+    using Col = int32_t;
+    static constexpr bool COL = true, AT = false, ONE = false;
+    PwmArg A;
+    __device__ __forceinline__ const int2 *table(const SearchPlan &) const {
+        __shared__ int2 tab[pwm_lds<G>()];
+        pwm_load_tab<G>(A, tab);
+        __syncthreads();
+        return tab;
     }
-}
-
-// k_search_emit with the score column: by start, '+' before '-' at the same start, at Pp[g] + Pm[g].
-template <int G>
-__global__ __launch_bounds__(BLOCK) void k_pwm_emit(SearchPlan P, PwmArg A, const int64_t *__restrict__ list, int64_t n_list,
-                                                    const int64_t *__restrict__ K, const int64_t *__restrict__ Pp,
-                                                    const int64_t *__restrict__ Pm, int64_t *__restrict__ o_rec,
-                                                    int64_t *__restrict__ o_start, uint8_t *__restrict__ o_strand,
-                                                    int32_t *__restrict__ o_score) {
-    __shared__ int2 tab[pwm_lds<G>()];
-    pwm_load_tab<G>(A, tab);
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_list) return;
-    const int64_t g = list[i], k = srch_slot(P, g);
-    int64_t r, b, lo, hi;
-    srch_run(P, g, k, r, b, lo, hi);
-    const int64_t base = K[g] - K[P.run0[k]];
-    const int64_t first = base - P.plen + 1;
-    int64_t o = Pp[g] + Pm[g];
-    pwm_walk<G>(P, tab, b, lo, hi, P.slen[r] - base, [&](int64_t kidx, int32_t sf, int32_t sr) {
-        if (sf >= A.thr_f) { o_rec[o] = r; o_start[o] = first + kidx; o_strand[o] = '+'; o_score[o] = sf; ++o; }
-        if (sr >= A.thr_r) { o_rec[o] = r; o_start[o] = first + kidx; o_strand[o] = '-'; o_score[o] = sr; ++o; }
-    });
-}
+    template <bool ROWS, class F>
+    __device__ __forceinline__ uint32_t walk(const SearchPlan &P, const int2 *tab, int64_t b, int64_t lo, int64_t hi, int64_t limit, F &&on) const {
+        return pwm_walk<G>(P, tab, b, lo, hi, limit, [&](int64_t kidx, int32_t sf, int32_t sr) { on(kidx, Win{sf, sr}); });
+    }
+    __device__ __forceinline__ uint32_t plus(const Win &w) const { return w.sf >= A.thr_f ? 1u : 0u; }
+    __device__ __forceinline__ uint32_t minus(const Win &w) const { return w.sr >= A.thr_r ? 1u : 0u; }
+    __device__ __forceinline__ int64_t first(const SearchPlan &P, int64_t base) const { return base - P.plen + 1; }
+    __device__ __forceinline__ int64_t pos(int64_t first, int64_t kidx, const Win &) const { return first + kidx; }
+    __device__ __forceinline__ Col col(const Win &w, bool minus) const { return minus ? w.sr : w.sf; }
+};
 
 __device__ __forceinline__ unsigned long long pwm_wave_max(unsigned long long v) {
 #pragma unroll

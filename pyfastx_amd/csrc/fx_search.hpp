@@ -11,12 +11,13 @@
 // patterns keep two 64-bit words.  Before its run the lane warms the state up on the L - 1 kept bytes in front of it (or
 // fewer, at the record's boff): the state after them is exactly the state a single walk over the record would have.
 //
-// Passes.  k_search_count: per run, hits on + and - and the kept bytes (one 32-bit word).  A device scan of the kept
+// Passes.  k_hits_count: per run, hits on + and - and the kept bytes (one 32-bit word).  A device scan of the kept
 // counts gives each run's first base (segmented at the records' first runs: record-local positions, whatever the line
-// layout).  k_search_fix: the rare record whose kept bytes outnumber slen (the cut of `seq`) has the run that crosses the
+// layout).  k_hits_fix: the rare record whose kept bytes outnumber slen (the cut of `seq`) has the run that crosses the
 // cut counted again and the runs behind it emptied.  A scan of the hit counts gives every run's output offset and the
-// total; the host reads only the totals.  k_search_emit: only the runs that have hits (a compacted list) walk again and
-// store (record, start, strand) at their offsets -- file order comes from the layout, no sort, no atomic.
+// total; the host reads only the totals.  k_hits_emit: only the runs that have hits (a compacted list) walk again and
+// store (record, start, strand) at their offsets -- file order comes from the layout, no sort, no atomic.  The three kernels
+// are templates on a FORM (below): ExactForm here, and those of fx_search_approx, fx_search_edit, fx_pwm and fx_minimizer.
 #pragma once
 #include "fx_kernels.hpp"
 
@@ -162,45 +163,87 @@ __device__ __forceinline__ int64_t srch_slot(const SearchPlan &P, int64_t g) { r
 // per run: hits on + (bits 0..8), on - (9..17), kept bytes (18..26)
 __device__ __forceinline__ uint32_t srch_pack(uint32_t hp, uint32_t hm, uint32_t kept) { return hp | (hm << 9) | (kept << 18); }
 
+// ------------------------------------------------------------------ the three passes of every window-hit form
+// A FORM is a small trivially copyable struct, a kernel argument, that says what the families of window hits differ in and
+// nothing else (ExactForm below, ApproxForm, EditForm, PwmForm, MzForm in the headers on top of this one):
+//   table(P)                                   its table in LDS, loaded and synced (every thread of the block calls it) -> tab
+//   walk<ROWS>(P, tab, b, lo, hi, limit, on)   its walk over one run: on(kidx, Win w) for every window that may be a row and
+//                                              ends at a kept byte in front of `limit` (ROWS: what a row stores is wanted too)
+//                                              -> kept bytes in [lo, hi)
+//   plus(w), minus(w)                          the window is a row on '+', on '-'
+//   first(P, base), pos(first, kidx, w)        a row's position; base: the record-local index of the run's first kept byte
+//   Col, COL, col(w, minus)                    the type of its own column, whether it has one, its value for the row of a strand
+//   AT                                         a row stores w.at, the address of its last byte, too
+//   ONE                                        a window is a row on exactly one strand
+// The kernels own the rest: the run geometry, the packed word, the cut, base, the offset Pp[g] + Pm[g] and the order '+' before
+// '-'.
 template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void k_search_count(SearchPlan P, uint32_t *__restrict__ packed) {
-    __shared__ ulonglong2 tab[256];
-    srch_load_tab<WIDE>(P, tab);
-    __syncthreads();
+struct ExactForm {
+    struct Win { uint32_t f, r; };
+    using Col = uint8_t;
+    static constexpr bool COL = false, AT = false, ONE = false;
+    __device__ __forceinline__ const ulonglong2 *table(const SearchPlan &P) const {
+        __shared__ ulonglong2 tab[256];
+        srch_load_tab<WIDE>(P, tab);
+        __syncthreads();
+        return tab;
+    }
+    template <bool ROWS, class F>
+    __device__ __forceinline__ uint32_t walk(const SearchPlan &P, const ulonglong2 *tab, int64_t b, int64_t lo, int64_t hi, int64_t limit,
+                                             F &&on) const {
+        return srch_walk<WIDE>(P, tab, b, lo, hi, limit, [&](int64_t kidx, uint32_t f, uint32_t rv) { on(kidx, Win{f, rv}); });
+    }
+    __device__ __forceinline__ uint32_t plus(const Win &w) const { return w.f; }
+    __device__ __forceinline__ uint32_t minus(const Win &w) const { return w.r; }
+    __device__ __forceinline__ int64_t first(const SearchPlan &P, int64_t base) const { return base - P.plen + 1; }
+    __device__ __forceinline__ int64_t pos(int64_t first, int64_t kidx, const Win &) const { return first + kidx; }
+    __device__ __forceinline__ Col col(const Win &, bool) const { return 0; }
+};
+
+template <class Form>
+__global__ __launch_bounds__(BLOCK) void k_hits_count(SearchPlan P, Form F, uint32_t *__restrict__ packed) {
+    auto *tab = F.table(P);
     const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (g >= P.n_runs) return;
     int64_t r, b, lo, hi;
     srch_run(P, g, srch_slot(P, g), r, b, lo, hi);
     uint32_t hp = 0, hm = 0;
-    const uint32_t kept = srch_walk<WIDE>(P, tab, b, lo, hi, INT64_MAX, [&](int64_t, uint32_t f, uint32_t rv) { hp += f; hm += rv; });
+    const uint32_t kept = F.template walk<false>(P, tab, b, lo, hi, INT64_MAX, [&](int64_t, const typename Form::Win &w) { hp += F.plus(w); hm += F.minus(w); });
     packed[g] = srch_pack(hp, hm, kept);
 }
 
-// One lane per selected record: where the kept bytes run past slen, the run that crosses the cut is counted again with
-// the cut and the runs behind it lose their hits.  K: exclusive prefix of the kept counts (n_runs + 1).
-template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void k_search_fix(SearchPlan P, const int64_t *__restrict__ K, uint32_t *__restrict__ packed) {
-    __shared__ ulonglong2 tab[256];
-    srch_load_tab<WIDE>(P, tab);
-    __syncthreads();
-    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (k >= P.n_sel) return;
-    const int64_t g0 = P.run0[k], g1 = P.run0[k + 1];
-    const int64_t slen = P.slen[srch_rec(P, k)];
+// The cut at slen of selected record s: where its kept bytes run past slen, f(g, base, slen) for every run from the one that
+// crosses the cut on, base: the run's first kept byte.  K: exclusive prefix of the kept counts (n_runs + 1).
+template <class F>
+__device__ __forceinline__ void srch_cut(const SearchPlan &P, const int64_t *K, int64_t s, F &&f) {
+    const int64_t g0 = P.run0[s], g1 = P.run0[s + 1];
+    const int64_t slen = P.slen[srch_rec(P, s)];
     if (g0 == g1 || K[g1] - K[g0] <= slen) return;
     int64_t lo_g = g0, hi_g = g1 - 1;                        // first run whose kept bytes end past slen
     while (lo_g < hi_g) { const int64_t m = (lo_g + hi_g) >> 1; if (K[m + 1] - K[g0] > slen) hi_g = m; else lo_g = m + 1; }
     for (int64_t g = lo_g; g < g1; ++g) {
         const int64_t base = K[g] - K[g0];
+        f(g, base, slen);
+    }
+}
+
+// One lane per selected record: the run that crosses the cut is counted again with the cut and the runs behind it lose their
+// rows.
+template <class Form>
+__global__ __launch_bounds__(BLOCK) void k_hits_fix(SearchPlan P, Form F, const int64_t *__restrict__ K, uint32_t *__restrict__ packed) {
+    auto *tab = F.table(P);
+    const int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= P.n_sel) return;
+    srch_cut(P, K, s, [&](int64_t g, int64_t base, int64_t slen) {
         uint32_t hp = 0, hm = 0;
         const uint32_t kept = (packed[g] >> 18) & 511u;
         if (base < slen && (packed[g] & 0x3FFFFu)) {
             int64_t r, b, lo, hi;
-            srch_run(P, g, k, r, b, lo, hi);
-            srch_walk<WIDE>(P, tab, b, lo, hi, slen - base, [&](int64_t, uint32_t f, uint32_t rv) { hp += f; hm += rv; });
+            srch_run(P, g, s, r, b, lo, hi);
+            F.template walk<false>(P, tab, b, lo, hi, slen - base, [&](int64_t, const typename Form::Win &w) { hp += F.plus(w); hm += F.minus(w); });
         }
         packed[g] = srch_pack(hp, hm, kept);
-    }
+    });
 }
 
 // list[NZ[g]] = g for every run with a hit (NZ: exclusive prefix of "has a hit")
@@ -210,27 +253,38 @@ __global__ __launch_bounds__(BLOCK) void k_search_list(const uint32_t *__restric
     if (g < n_runs && (packed[g] & 0x3FFFFu)) list[NZ[g]] = g;
 }
 
-// The runs of the list walk again and store their hits at Pp[g] + Pm[g] (exclusive prefixes of the + and - counts):
-// by start, '+' before '-' at the same start.  Record-local starts: base of the run (K, segmented) + kept index - L + 1.
-template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void k_search_emit(SearchPlan P, const int64_t *__restrict__ list, int64_t n_list,
-                                                       const int64_t *__restrict__ K, const int64_t *__restrict__ Pp,
-                                                       const int64_t *__restrict__ Pm, int64_t *__restrict__ o_rec,
-                                                       int64_t *__restrict__ o_start, uint8_t *__restrict__ o_strand) {
-    __shared__ ulonglong2 tab[256];
-    srch_load_tab<WIDE>(P, tab);
-    __syncthreads();
+// The runs of the list walk again and store their rows at Pp[g] + Pm[g] (exclusive prefixes of the + and - counts): by
+// position, '+' before '-' at the same position.  Record-local positions: the run's first kept byte (K, segmented) + the kept
+// index, moved by the form.  o_col / o_at: the form's column and the address column, where it has them.
+template <class Form>
+__global__ __launch_bounds__(BLOCK) void k_hits_emit(SearchPlan P, Form F, const int64_t *__restrict__ list, int64_t n_list,
+                                                     const int64_t *__restrict__ K, const int64_t *__restrict__ Pp,
+                                                     const int64_t *__restrict__ Pm, int64_t *__restrict__ o_rec,
+                                                     int64_t *__restrict__ o_pos, int64_t *__restrict__ o_at,
+                                                     uint8_t *__restrict__ o_strand, typename Form::Col *__restrict__ o_col) {
+    auto *tab = F.table(P);
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n_list) return;
     const int64_t g = list[i], k = srch_slot(P, g);
     int64_t r, b, lo, hi;
     srch_run(P, g, k, r, b, lo, hi);
     const int64_t base = K[g] - K[P.run0[k]];
-    const int64_t first = base - P.plen + 1;
+    const int64_t first = F.first(P, base);
     int64_t o = Pp[g] + Pm[g];
-    srch_walk<WIDE>(P, tab, b, lo, hi, P.slen[r] - base, [&](int64_t kidx, uint32_t f, uint32_t rv) {
-        if (f) { o_rec[o] = r; o_start[o] = first + kidx; o_strand[o] = '+'; ++o; }
-        if (rv) { o_rec[o] = r; o_start[o] = first + kidx; o_strand[o] = '-'; ++o; }
+    F.template walk<true>(P, tab, b, lo, hi, P.slen[r] - base, [&](int64_t kidx, const typename Form::Win &w) {
+        auto put = [&](bool minus) {
+            o_rec[o] = r;
+            o_pos[o] = F.pos(first, kidx, w);
+            if constexpr (Form::AT) o_at[o] = w.at;
+            o_strand[o] = minus ? '-' : '+';
+            if constexpr (Form::COL) o_col[o] = F.col(w, minus);
+            ++o;
+        };
+        if constexpr (Form::ONE) put(F.minus(w));
+        else {
+            if (F.plus(w)) put(false);
+            if (F.minus(w)) put(true);
+        }
     });
 }
 

@@ -105,72 +105,30 @@ __device__ __forceinline__ uint32_t asrch_walk(const SearchPlan &P, const Approx
     return (uint32_t)kidx;
 }
 
-// per run: the packed word of fx_search.hpp (srch_pack): hits on +, hits on -, kept bytes
+// The form of the three passes (k_hits_count / _fix / _emit of fx_search.hpp): the level words, the mismatch column.
 template <bool WIDE, int NLEV>
-__global__ __launch_bounds__(BLOCK) void k_asearch_count(SearchPlan P, ApproxArg A, uint32_t *__restrict__ packed) {
-    __shared__ asrch_tab_t<WIDE> tab[256];
-    asrch_load_tab<WIDE>(P, tab);
-    __syncthreads();
-    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= P.n_runs) return;
-    int64_t r, b, lo, hi;
-    srch_run(P, g, srch_slot(P, g), r, b, lo, hi);
-    uint32_t hp = 0, hm = 0;
-    const uint32_t kept = asrch_walk<WIDE, NLEV, false>(P, A, tab, b, lo, hi, INT64_MAX,
-                                                        [&](int64_t, uint32_t f, uint32_t rv, uint32_t, uint32_t) { hp += f; hm += rv; });
-    packed[g] = srch_pack(hp, hm, kept);
-}
-
-// The cut at slen, as k_search_fix makes it: one lane per selected record; where the kept bytes run past slen, the run that
-// crosses the cut is counted again with the cut and the runs behind it lose their hits.
-template <bool WIDE, int NLEV>
-__global__ __launch_bounds__(BLOCK) void k_asearch_fix(SearchPlan P, ApproxArg A, const int64_t *__restrict__ K, uint32_t *__restrict__ packed) {
-    __shared__ asrch_tab_t<WIDE> tab[256];
-    asrch_load_tab<WIDE>(P, tab);
-    __syncthreads();
-    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (k >= P.n_sel) return;
-    const int64_t g0 = P.run0[k], g1 = P.run0[k + 1];
-    const int64_t slen = P.slen[srch_rec(P, k)];
-    if (g0 == g1 || K[g1] - K[g0] <= slen) return;
-    int64_t lo_g = g0, hi_g = g1 - 1;                        // first run whose kept bytes end past slen
-    while (lo_g < hi_g) { const int64_t m = (lo_g + hi_g) >> 1; if (K[m + 1] - K[g0] > slen) hi_g = m; else lo_g = m + 1; }
-    for (int64_t g = lo_g; g < g1; ++g) {
-        const int64_t base = K[g] - K[g0];
-        uint32_t hp = 0, hm = 0;
-        const uint32_t kept = (packed[g] >> 18) & 511u;
-        if (base < slen && (packed[g] & 0x3FFFFu)) {
-            int64_t r, b, lo, hi;
-            srch_run(P, g, k, r, b, lo, hi);
-            asrch_walk<WIDE, NLEV, false>(P, A, tab, b, lo, hi, slen - base,
-                                          [&](int64_t, uint32_t f, uint32_t rv, uint32_t, uint32_t) { hp += f; hm += rv; });
-        }
-        packed[g] = srch_pack(hp, hm, kept);
+struct ApproxForm {
+    struct Win { uint32_t f, r, df, dr; };
+    using Col = uint8_t;
+    static constexpr bool COL = true, AT = false, ONE = false;
+    ApproxArg A;
+    __device__ __forceinline__ const asrch_tab_t<WIDE> *table(const SearchPlan &P) const {
+        __shared__ asrch_tab_t<WIDE> tab[256];
+        asrch_load_tab<WIDE>(P, tab);
+        __syncthreads();
+        return tab;
     }
-}
-
-// k_search_emit with the mismatch column: by start, '+' before '-' at the same start, at Pp[g] + Pm[g].
-template <bool WIDE, int NLEV>
-__global__ __launch_bounds__(BLOCK) void k_asearch_emit(SearchPlan P, ApproxArg A, const int64_t *__restrict__ list, int64_t n_list,
-                                                        const int64_t *__restrict__ K, const int64_t *__restrict__ Pp,
-                                                        const int64_t *__restrict__ Pm, int64_t *__restrict__ o_rec,
-                                                        int64_t *__restrict__ o_start, uint8_t *__restrict__ o_strand,
-                                                        uint8_t *__restrict__ o_mis) {
-    __shared__ asrch_tab_t<WIDE> tab[256];
-    asrch_load_tab<WIDE>(P, tab);
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_list) return;
-    const int64_t g = list[i], k = srch_slot(P, g);
-    int64_t r, b, lo, hi;
-    srch_run(P, g, k, r, b, lo, hi);
-    const int64_t base = K[g] - K[P.run0[k]];
-    const int64_t first = base - P.plen + 1;
-    int64_t o = Pp[g] + Pm[g];
-    asrch_walk<WIDE, NLEV, true>(P, A, tab, b, lo, hi, P.slen[r] - base, [&](int64_t kidx, uint32_t f, uint32_t rv, uint32_t df, uint32_t dr) {
-        if (f) { o_rec[o] = r; o_start[o] = first + kidx; o_strand[o] = '+'; o_mis[o] = (uint8_t)df; ++o; }
-        if (rv) { o_rec[o] = r; o_start[o] = first + kidx; o_strand[o] = '-'; o_mis[o] = (uint8_t)dr; ++o; }
-    });
-}
+    template <bool ROWS, class F>
+    __device__ __forceinline__ uint32_t walk(const SearchPlan &P, const asrch_tab_t<WIDE> *tab, int64_t b, int64_t lo, int64_t hi, int64_t limit,
+                                             F &&on) const {
+        return asrch_walk<WIDE, NLEV, ROWS>(P, A, tab, b, lo, hi, limit,
+                                            [&](int64_t kidx, uint32_t f, uint32_t rv, uint32_t df, uint32_t dr) { on(kidx, Win{f, rv, df, dr}); });
+    }
+    __device__ __forceinline__ uint32_t plus(const Win &w) const { return w.f; }
+    __device__ __forceinline__ uint32_t minus(const Win &w) const { return w.r; }
+    __device__ __forceinline__ int64_t first(const SearchPlan &P, int64_t base) const { return base - P.plen + 1; }
+    __device__ __forceinline__ int64_t pos(int64_t first, int64_t kidx, const Win &) const { return first + kidx; }
+    __device__ __forceinline__ Col col(const Win &w, bool minus) const { return (uint8_t)(minus ? w.dr : w.df); }
+};
 
 }  // namespace fx

@@ -26,7 +26,7 @@
 // Forms.  L <= 32: a 32-bit Pv / Mv per strand, so the add never carries from one strand into the other; the two strands'
 // masks share one 64-bit LDS entry (the narrow table of fx_search_approx.hpp).  L > 32: 64-bit words.
 //
-// Rows.  k_esearch_emit stores per end the record, the stop (the run's first base from K + the kept index + 1), the strand,
+// Rows.  k_hits_emit with EditForm stores per end the record, the stop (the run's first base from K + the kept index + 1), the strand,
 // the edits and the byte address of the end letter, by (record, stop), '+' before '-' at one stop.  report = best:
 // k_esearch_best flags the ends that are the leftmost minimum of their dip -- the neighbour on the same strand, one letter to
 // either side, lies within two rows because at most one row of the other strand sits between them -- and a scan of the flags
@@ -96,73 +96,33 @@ __device__ __forceinline__ uint32_t esrch_walk(const SearchPlan &P, int k, const
     return (uint32_t)kidx;
 }
 
-// per run: the packed word of fx_search.hpp (srch_pack): ends on +, ends on - (at most 256 each), kept bytes
+// The form of the three passes (k_hits_count / _fix / _emit of fx_search.hpp): a row is an END, by stop (the run's first base
+// from K + the kept index + 1), with its edits and the address of the end letter (address space of the plan: P.base[at] is the
+// letter), for k_esearch_start.
 template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void k_esearch_count(SearchPlan P, int k, uint32_t *__restrict__ packed) {
-    __shared__ asrch_tab_t<WIDE> tab[256];
-    asrch_load_tab<WIDE>(P, tab);
-    __syncthreads();
-    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= P.n_runs) return;
-    int64_t r, b, lo, hi;
-    srch_run(P, g, srch_slot(P, g), r, b, lo, hi);
-    uint32_t hp = 0, hm = 0;
-    const uint32_t kept = esrch_walk<WIDE>(P, k, tab, b, lo, hi, INT64_MAX,
-                                           [&](int64_t, int64_t, bool ef, bool er, uint32_t, uint32_t) { hp += ef; hm += er; });
-    packed[g] = srch_pack(hp, hm, kept);
-}
-
-// The cut at slen, as k_search_fix makes it: one lane per selected record; where the kept bytes run past slen, the run that
-// crosses the cut is counted again with the cut and the runs behind it lose their ends.
-template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void k_esearch_fix(SearchPlan P, int k, const int64_t *__restrict__ K, uint32_t *__restrict__ packed) {
-    __shared__ asrch_tab_t<WIDE> tab[256];
-    asrch_load_tab<WIDE>(P, tab);
-    __syncthreads();
-    const int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (s >= P.n_sel) return;
-    const int64_t g0 = P.run0[s], g1 = P.run0[s + 1];
-    const int64_t slen = P.slen[srch_rec(P, s)];
-    if (g0 == g1 || K[g1] - K[g0] <= slen) return;
-    int64_t lo_g = g0, hi_g = g1 - 1;                        // first run whose kept bytes end past slen
-    while (lo_g < hi_g) { const int64_t m = (lo_g + hi_g) >> 1; if (K[m + 1] - K[g0] > slen) hi_g = m; else lo_g = m + 1; }
-    for (int64_t g = lo_g; g < g1; ++g) {
-        const int64_t base = K[g] - K[g0];
-        uint32_t hp = 0, hm = 0;
-        const uint32_t kept = (packed[g] >> 18) & 511u;
-        if (base < slen && (packed[g] & 0x3FFFFu)) {
-            int64_t r, b, lo, hi;
-            srch_run(P, g, s, r, b, lo, hi);
-            esrch_walk<WIDE>(P, k, tab, b, lo, hi, slen - base,
-                             [&](int64_t, int64_t, bool ef, bool er, uint32_t, uint32_t) { hp += ef; hm += er; });
-        }
-        packed[g] = srch_pack(hp, hm, kept);
+struct EditForm {
+    struct Win { int64_t at; bool ef, er; uint32_t df, dr; };
+    using Col = uint8_t;
+    static constexpr bool COL = true, AT = true, ONE = false;
+    int k;
+    __device__ __forceinline__ const asrch_tab_t<WIDE> *table(const SearchPlan &P) const {
+        __shared__ asrch_tab_t<WIDE> tab[256];
+        asrch_load_tab<WIDE>(P, tab);
+        __syncthreads();
+        return tab;
     }
-}
-
-// k_search_emit for ends: by stop, '+' before '-' at the same stop, at Pp[g] + Pm[g]; o_at: the address of the end letter
-// (address space of the plan: P.base[o_at] is the letter), for k_esearch_start.
-template <bool WIDE>
-__global__ __launch_bounds__(BLOCK) void k_esearch_emit(SearchPlan P, int k, const int64_t *__restrict__ list, int64_t n_list,
-                                                        const int64_t *__restrict__ K, const int64_t *__restrict__ Pp,
-                                                        const int64_t *__restrict__ Pm, int64_t *__restrict__ o_rec,
-                                                        int64_t *__restrict__ o_stop, int64_t *__restrict__ o_at,
-                                                        uint8_t *__restrict__ o_strand, uint8_t *__restrict__ o_edits) {
-    __shared__ asrch_tab_t<WIDE> tab[256];
-    asrch_load_tab<WIDE>(P, tab);
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_list) return;
-    const int64_t g = list[i], s = srch_slot(P, g);
-    int64_t r, b, lo, hi;
-    srch_run(P, g, s, r, b, lo, hi);
-    const int64_t base = K[g] - K[P.run0[s]];
-    int64_t o = Pp[g] + Pm[g];
-    esrch_walk<WIDE>(P, k, tab, b, lo, hi, P.slen[r] - base, [&](int64_t kidx, int64_t at, bool ef, bool er, uint32_t df, uint32_t dr) {
-        if (ef) { o_rec[o] = r; o_stop[o] = base + kidx + 1; o_at[o] = at; o_strand[o] = '+'; o_edits[o] = (uint8_t)df; ++o; }
-        if (er) { o_rec[o] = r; o_stop[o] = base + kidx + 1; o_at[o] = at; o_strand[o] = '-'; o_edits[o] = (uint8_t)dr; ++o; }
-    });
-}
+    template <bool ROWS, class F>
+    __device__ __forceinline__ uint32_t walk(const SearchPlan &P, const asrch_tab_t<WIDE> *tab, int64_t b, int64_t lo, int64_t hi, int64_t limit,
+                                             F &&on) const {
+        return esrch_walk<WIDE>(P, k, tab, b, lo, hi, limit,
+                                [&](int64_t kidx, int64_t at, bool ef, bool er, uint32_t df, uint32_t dr) { on(kidx, Win{at, ef, er, df, dr}); });
+    }
+    __device__ __forceinline__ bool plus(const Win &w) const { return w.ef; }
+    __device__ __forceinline__ bool minus(const Win &w) const { return w.er; }
+    __device__ __forceinline__ int64_t first(const SearchPlan &, int64_t base) const { return base; }
+    __device__ __forceinline__ int64_t pos(int64_t first, int64_t kidx, const Win &) const { return first + kidx + 1; }
+    __device__ __forceinline__ Col col(const Win &w, bool minus) const { return (uint8_t)(minus ? w.dr : w.df); }
+};
 
 // report = best: keep[i] = 1 where end i is the leftmost minimum of its dip -- the end one letter to the left on the same
 // strand (if there is one) has more edits, the one to the right (if there is one) has no fewer.  Rows of one record and strand

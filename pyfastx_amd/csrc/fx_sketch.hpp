@@ -12,7 +12,7 @@
 // A lane owns the k-mers that END at a kept byte of its run and keeps those whose key lies below T[slot], the threshold of the
 // run's set (slot: the selected record, or 0 when pooled), read once per run.  No ring, no LDS.
 //   k_sk_count  rows per run (at most 256: bits 0..8 of the packed word of srch_pack) and its kept bytes
-//   k_sk_fix    the cut at slen once the kept-byte scan is there, as k_search_fix makes it
+//   k_sk_fix    the cut at slen once the kept-byte scan is there, as k_hits_fix makes it
 //   k_sk_emit   (slot, key) rows at the run's offset of the row scan; they never leave the device
 // A set that is not `active` (final in an earlier round) is not walked: its lanes leave after the binary search over run0.
 // Filter pass (FASTQ).  The lane groups and pieces of k_kt_fastq with one pooled slot: a count of the keys below T[0], then the
@@ -71,29 +71,22 @@ __global__ __launch_bounds__(BLOCK) void k_sk_count(SearchPlan P, int k, int poo
     packed[g] = srch_pack(rows, 0, kept);
 }
 
-// The cut at slen, as k_search_fix makes it: one lane per selected record.
+// The cut at slen, as k_hits_fix makes it: one lane per selected record.
 template <bool CANON>
 __global__ __launch_bounds__(BLOCK) void k_sk_fix(SearchPlan P, int k, int pooled, const uint64_t *__restrict__ T, const int64_t *__restrict__ K,
                                                   uint32_t *__restrict__ packed) {
     const int64_t s = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= P.n_sel) return;
-    const int64_t g0 = P.run0[s], g1 = P.run0[s + 1];
-    const int64_t slen = P.slen[srch_rec(P, s)];
-    if (g0 == g1 || K[g1] - K[g0] <= slen) return;
-    const uint64_t t = T[sk_set_of(P, pooled, s)];
-    int64_t lo_g = g0, hi_g = g1 - 1;                        // first run whose kept bytes end past slen
-    while (lo_g < hi_g) { const int64_t m = (lo_g + hi_g) >> 1; if (K[m + 1] - K[g0] > slen) hi_g = m; else lo_g = m + 1; }
-    for (int64_t g = lo_g; g < g1; ++g) {
-        const int64_t base = K[g] - K[g0];
+    srch_cut(P, K, s, [&](int64_t g, int64_t base, int64_t slen) {
         uint32_t rows = 0;
         const uint32_t kept = (packed[g] >> 18) & 511u;
         if (base < slen && (packed[g] & 0x3FFFFu)) {
             int64_t r, b, lo, hi;
             srch_run(P, g, s, r, b, lo, hi);
-            sk_walk<CANON>(P, k, t, b, lo, hi, slen - base, [&](uint64_t) { ++rows; });
+            sk_walk<CANON>(P, k, T[sk_set_of(P, pooled, s)], b, lo, hi, slen - base, [&](uint64_t) { ++rows; });
         }
         packed[g] = srch_pack(rows, 0, kept);
-    }
+    });
 }
 
 struct SkLdRows {                                            // rows of run g

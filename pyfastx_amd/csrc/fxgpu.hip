@@ -17,6 +17,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <optional>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -3952,26 +3953,32 @@ struct HitRuns {
     }
 };
 
-// What the window-hit entries (fx_fasta_search, _search_approx, _pwm_scan) do once their arguments are checked and their tables
-// are up: the head above, then
-//   count(R)                                   the form's count kernel: hits per run on both strands, kept bytes -> R.packed
-//   fix(R, K, grid_sel)                        the cut at slen once the kept-byte scan K is there (timed with the scans)
-//   emit(R, list, n_list, K, Pp, Pm, o_rec, o_start, o_strand, o_extra)     the hits of the runs that have some
-// with the scans, the per-record counts, the totals home, the cap, the pinned blocks and the way home between them.
-// extra_size: bytes per hit of the form's fourth column (0: none), whose pinned block goes to *extra.
+// What the window-hit entries (fx_fasta_search, _search_approx, _pwm_scan, _minimizers) do once their arguments are checked and
+// their tables are up: the head above, then the three kernels of fx_search.hpp with the entry's FORM F (what a family's table,
+// walk and row are)
+//   k_hits_count<Form>     rows per run on both strands, kept bytes -> R.packed                      timed under pass.count_id
+//   k_hits_fix<Form>       the cut at slen once the kept-byte scan K is there                         timed with the scans
+//   k_hits_emit<Form>      the rows of the runs that have some: rec, position, strand, the form's column    pass.emit_id
+// with the scans, the per-record counts, the totals home, the cap, the pinned blocks and the way home between them.  The pinned
+// block of the form's column (where it has one) goes to *extra.
 //
 // hit_scans is the part in front of the cap, which fx_fasta_search_edit (whose rows pass a filter and a start pass before they
 // go home) shares: the head, count, the kept-byte scan, fix, the hit scans, the per-record counts where asked for, the totals
-// home -> S.total hits in S.n_list runs.  S.R.P.n_runs == 0 afterwards: nothing was launched.
+// home -> S.total hits in S.n_list runs.  S.R.P.n_runs == 0 afterwards: nothing was launched.  hit_emit: the run list and the
+// emit kernel, into device rows.
+struct HitPass {
+    int count_id, emit_id;        // the timing ids of the form's count and emit launches
+    size_t lds;                   // dynamic LDS of its three kernels
+};
 struct HitScans {
     HitRuns R;
     int64_t *K = nullptr, *Pp = nullptr, *Pm = nullptr, *NZ = nullptr;      // n_runs + 1 each: kept bytes, hits on +, on -, runs with a hit
     unsigned grid_sel = 1;
     int64_t total = 0, n_list = 0;
 };
-template <class Count, class Fix>
+template <class Form>
 static int hit_scans(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int64_t *counts,
-                     Count &&count, Fix &&fix, HitScans &S) {
+                     const Form &F, const HitPass &pass, HitScans &S) {
     int rc;
     HitRuns &R = S.R;
     if ((rc = R.open(h, st, K_SEARCH_SCAN, masks, plen, ids, n_ids, 4, counts)) || R.P.n_runs == 0) return rc;
@@ -3980,9 +3987,9 @@ static int hit_scans(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen
     S.NZ = K + 3 * R.nr1;
     const unsigned grid_sel = S.grid_sel = nblocks(P.n_sel, BLOCK);
     // count pass, kept-byte scan, the cut at slen, hit scans
-    count(R);
+    FX_LAUNCH_LDS(h, pass.count_id, k_hits_count<Form>, dim3(R.grid_runs), dim3(BLOCK), pass.lds, P, F, R.packed.p);
     if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{R.packed.p}, P.n_runs, K, R.d_tot))) return rc;
-    fix(R, (const int64_t *)K, grid_sel);
+    FX_LAUNCH_LDS(h, K_SEARCH_SCAN, k_hits_fix<Form>, dim3(grid_sel), dim3(BLOCK), pass.lds, P, F, (const int64_t *)K, R.packed.p);
     if ((rc = sscan<3>(h, st, K_SEARCH_SCAN, SrchLdHits{R.packed.p}, P.n_runs, Pp, R.d_tot))) return rc;        // Pp, Pm, NZ are consecutive arrays of nr1
     if (counts) {
         int64_t *cnt_dev = nullptr;
@@ -3997,18 +4004,25 @@ static int hit_scans(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen
     S.n_list = tot[2];
     return FX_OK;
 }
+// list: S.n_list words of scratch; o_at: null where the form stores none
+template <class Form>
+static void hit_emit(fx_handle *h, const HitScans &S, const Form &F, const HitPass &pass, int64_t *list, int64_t *o_rec, int64_t *o_pos,
+                     int64_t *o_at, uint8_t *o_strand, typename Form::Col *o_col) {
+    const HitRuns &R = S.R;
+    hipLaunchKernelGGL(k_search_list, dim3(R.grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)R.packed.p, (const int64_t *)S.NZ, R.P.n_runs, list);
+    FX_LAUNCH_LDS(h, pass.emit_id, k_hits_emit<Form>, dim3(nblocks(S.n_list, BLOCK)), dim3(BLOCK), pass.lds, R.P, F, (const int64_t *)list, S.n_list,
+                  (const int64_t *)S.K, (const int64_t *)S.Pp, (const int64_t *)S.Pm, o_rec, o_pos, o_at, o_strand, o_col);
+}
 
-template <class Count, class Fix, class Emit>
+template <class Form>
 static int run_hits(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t *counts,
-                    int extra_size, const char *what, Count &&count, Fix &&fix, Emit &&emit, int64_t **rec, int64_t **start, uint8_t **strand,
-                    void **extra, int64_t *n_hits) {
+                    const char *what, const Form &F, const HitPass &pass, int64_t **rec, int64_t **start, uint8_t **strand, void **extra,
+                    int64_t *n_hits) {
+    constexpr int extra_size = Form::COL ? (int)sizeof(typename Form::Col) : 0;
     int rc;
     HitScans S;
-    if ((rc = hit_scans(h, st, masks, plen, ids, n_ids, counts, count, fix, S)) || S.R.P.n_runs == 0) return rc;
-    HitRuns &R = S.R;
-    const SearchPlan &P = R.P;
-    const int64_t *K = S.K, *Pp = S.Pp, *Pm = S.Pm, *NZ = S.NZ;
-    const int64_t total = S.total, n_list = S.n_list;
+    if ((rc = hit_scans(h, st, masks, plen, ids, n_ids, counts, F, pass, S)) || S.R.P.n_runs == 0) return rc;
+    const int64_t total = S.total;
     *n_hits = total;
     if (cap == 0 && counts) { h->prof.drain(); return FX_OK; }
     if (total > cap) { h->prof.drain(); return fail(FX_ERANGE, "%lld hits, more than the %lld asked for", (long long)total, (long long)cap); }
@@ -4022,18 +4036,42 @@ static int run_hits(fx_handle *h, Staged &st, const ulonglong2 *masks, int plen,
         ScratchBuf<int64_t> out64, list;
         ScratchBuf<uint8_t> out8;              // the form's column, then strand
         if ((rc = out64.alloc(h->device, 2 * total, h->stream)) || (rc = out8.alloc(h->device, (extra_size + 1) * total, h->stream)) ||
-            (rc = list.alloc(h->device, n_list, h->stream)))
+            (rc = list.alloc(h->device, S.n_list, h->stream)))
             return rc;
         uint8_t *d_strand = out8.p + extra_size * total;
-        hipLaunchKernelGGL(k_search_list, dim3(R.grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)R.packed.p, (const int64_t *)NZ, P.n_runs, list.p);
-        emit(R, (const int64_t *)list.p, n_list, (const int64_t *)K, (const int64_t *)Pp, (const int64_t *)Pm, out64.p, out64.p + total, d_strand,
-             (void *)out8.p);
+        hit_emit(h, S, F, pass, list.p, out64.p, out64.p + total, nullptr, d_strand, (typename Form::Col *)out8.p);
         if ((rc = home(h, what, {{out.p[0], out64.p, total * 8}, {out.p[1], out64.p + total, total * 8}, {out.p[2], d_strand, total},
                                  {out.p[3], out8.p, extra_size * total}})))
             return rc;
     }
     out.release(rec, start, strand, extra);
     return FX_OK;
+}
+
+// What fx_fasta_search, _search_approx and _search_edit repeat once their own numbers and the handle are checked: the strands
+// and the patterns, `bad_out` (the entry's own test of its output pointers), the table and the device, the masks of both strands
+// (the letters of the pattern are looked at before the ids: fasta_enter in two parts), the ids -> *n_sel; 0: nothing to do,
+// otherwise the call's Staged is made (only now: a refused call leaves the handle's staging as it was) and the masks are up
+// at *d_masks.
+static int search_head(fx_handle *h, std::optional<Staged> &st, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, bool bad_out, const int64_t *ids,
+                       int64_t n_ids, int64_t *n_sel, const ulonglong2 **d_masks) {
+    if (!(mode & (FX_SEARCH_PLUS | FX_SEARCH_MINUS))) return fail(FX_EINVAL, "no strand selected");
+    if (((mode & FX_SEARCH_PLUS) && !pat) || ((mode & FX_SEARCH_MINUS) && !rpat)) return fail(FX_EINVAL, "null pattern");
+    if (bad_out) return fail(FX_EINVAL, "null output");
+    int rc;
+    if ((rc = fasta_state(h, "hits", ids, n_ids)) || (rc = fasta_device(h))) return rc;
+    std::vector<ulonglong2> masks(256);
+    {
+        std::vector<uint64_t> f(256, 0), r(256, 0);
+        if (((mode & FX_SEARCH_PLUS) && !search_masks(pat, plen, mode, f.data())) ||
+            ((mode & FX_SEARCH_MINUS) && !search_masks(rpat, plen, mode, r.data())))
+            return fail(FX_EINVAL, "a pattern letter is not an IUPAC code");
+        for (int c = 0; c < 256; ++c) masks[c] = make_ulonglong2(f[c], r[c]);
+    }
+    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
+    if ((*n_sel = ids ? n_ids : h->n_hdr) == 0) return FX_OK;
+    st.emplace(h);
+    return st->up(h, masks.data(), 256, d_masks);
 }
 
 // Both search entries.  max_mismatch < 0: the exact automaton (fx_search.hpp); otherwise the approximate one
@@ -4046,69 +4084,30 @@ static int fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, i
     *n_hits = 0;
     if (rec) *rec = nullptr; if (start) *start = nullptr; if (strand) *strand = nullptr; if (mismatch) *mismatch = nullptr;
     if (plen < 1 || plen > 64) return fail(FX_EINVAL, "pattern length %d outside 1..64", (int)plen);
-    if (!(mode & (FX_SEARCH_PLUS | FX_SEARCH_MINUS))) return fail(FX_EINVAL, "no strand selected");
-    if (((mode & FX_SEARCH_PLUS) && !pat) || ((mode & FX_SEARCH_MINUS) && !rpat)) return fail(FX_EINVAL, "null pattern");
     const bool counts_only = cap == 0 && counts;
-    if (cap < 0 || (!counts_only && (!rec || !start || !strand || (approx && !mismatch)))) return fail(FX_EINVAL, "null output");
     int rc;
-    if ((rc = fasta_state(h, "hits", ids, n_ids)) || (rc = fasta_device(h))) return rc;
-    std::vector<ulonglong2> masks(256);                    // (the letters of the pattern are looked at before the ids: fasta_enter in two parts)
-    {
-        std::vector<uint64_t> f(256, 0), r(256, 0);
-        if (((mode & FX_SEARCH_PLUS) && !search_masks(pat, plen, mode, f.data())) ||
-            ((mode & FX_SEARCH_MINUS) && !search_masks(rpat, plen, mode, r.data())))
-            return fail(FX_EINVAL, "a pattern letter is not an IUPAC code");
-        for (int c = 0; c < 256; ++c) masks[c] = make_ulonglong2(f[c], r[c]);
-    }
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
-    if (n_sel == 0) return FX_OK;
-    Staged st(h);
+    int64_t n_sel = 0;
+    std::optional<Staged> st;
     const ulonglong2 *d_masks = nullptr;
-    if ((rc = st.up(h, masks.data(), 256, &d_masks))) return rc;
-    const bool wide = plen > 32;
+    if ((rc = search_head(h, st, pat, rpat, plen, mode, cap < 0 || (!counts_only && (!rec || !start || !strand || (approx && !mismatch))), ids, n_ids,
+                          &n_sel, &d_masks)) || n_sel == 0)
+        return rc;
     ApproxArg A{0, 0, 0};
     if (approx) {                              // where a mismatch may fall: the pattern's positions minus the anchor, mirrored for '-'
         const uint64_t valid = plen == 64 ? ~0ull : (1ull << plen) - 1;
         uint64_t mirror = 0;
         for (int j = 0; j < plen; ++j) mirror |= ((anchor >> j) & 1ull) << (plen - 1 - j);
         const uint64_t nf = (mode & FX_SEARCH_PLUS) ? valid & ~anchor : 0, nr = (mode & FX_SEARCH_MINUS) ? valid & ~mirror : 0;
-        A = wide ? ApproxArg{nf, nr, max_mismatch} : ApproxArg{nf | (nr << 32), 0, max_mismatch};
+        A = plen > 32 ? ApproxArg{nf, nr, max_mismatch} : ApproxArg{nf | (nr << 32), 0, max_mismatch};
     }
-    // the approximate kernels of this call: f(WIDE, NLEV)
-    auto with_form = [&](auto &&f) { with_bool(wide, [&](auto W) { with_levels(A.d, [&](auto N) { f(W, N); }); }); };
-    return run_hits(
-        h, st, d_masks, plen, ids, n_ids, cap, counts, approx ? 1 : 0, "search emit",
-        [&](HitRuns &R) {
-            if (approx)
-                with_form([&](auto W, auto N) {
-                    FX_LAUNCH(h, K_ASEARCH_COUNT, (k_asearch_count<decltype(W)::value, decltype(N)::value>), dim3(R.grid_runs), dim3(BLOCK), R.P, A, R.packed.p);
-                });
-            else
-                with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_COUNT, k_search_count<W()>, dim3(R.grid_runs), dim3(BLOCK), R.P, R.packed.p); });
-        },
-        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
-            if (approx)
-                with_form([&](auto W, auto N) {
-                    FX_LAUNCH(h, K_SEARCH_SCAN, (k_asearch_fix<decltype(W)::value, decltype(N)::value>), dim3(grid_sel), dim3(BLOCK), R.P, A, K, R.packed.p);
-                });
-            else
-                with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_search_fix<W()>, dim3(grid_sel), dim3(BLOCK), R.P, K, R.packed.p); });
-        },
-        [&](HitRuns &R, const int64_t *list, int64_t n_list, const int64_t *K, const int64_t *Pp, const int64_t *Pm, int64_t *o_rec, int64_t *o_start,
-            uint8_t *o_strand, void *o_mis) {
-            if (approx)
-                with_form([&](auto W, auto N) {
-                    FX_LAUNCH(h, K_ASEARCH_EMIT, (k_asearch_emit<decltype(W)::value, decltype(N)::value>), dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), R.P, A,
-                              list, n_list, K, Pp, Pm, o_rec, o_start, o_strand, (uint8_t *)o_mis);
-                });
-            else
-                with_bool(wide, [&](auto W) {
-                    FX_LAUNCH(h, K_SEARCH_EMIT, k_search_emit<W()>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), R.P, list, n_list, K, Pp, Pm, o_rec, o_start,
-                              o_strand);
-                });
-        },
-        rec, start, strand, (void **)mismatch, n_hits);
+    auto run = [&](const auto &F, const HitPass &pass) {
+        rc = run_hits(h, *st, d_masks, plen, ids, n_ids, cap, counts, "search emit", F, pass, rec, start, strand, (void **)mismatch, n_hits);
+    };
+    with_bool(plen > 32, [&](auto W) {         // the form of this call: wide, levels
+        if (approx) with_levels(A.d, [&](auto N) { run(ApproxForm<W(), N()>{A}, HitPass{K_ASEARCH_COUNT, K_ASEARCH_EMIT, 0}); });
+        else run(ExactForm<W()>{}, HitPass{K_SEARCH_COUNT, K_SEARCH_EMIT, 0});
+    });
+    return rc;
 }
 
 extern "C" int fx_fasta_search(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, const int64_t *ids,
@@ -4129,50 +4128,18 @@ extern "C" int fx_fasta_search_approx(fx_handle *h, const uint8_t *pat, const ui
 }
 
 // (fx_search_edit.hpp)  What the numbers alone decide is refused first, before the handle is looked at.  hit_scans with the
-// count and fix kernels of the form gives the ENDS; they are emitted on the device, report = best flags and scans them there,
-// and only the rows that stay get a start and go home.
-extern "C" int fx_fasta_search_edit(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int32_t max_edits,
-                                    int32_t report, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
-                                    int64_t **stop, uint8_t **strand, uint8_t **edits, int64_t *n_hits, int64_t *n_ends, int64_t *counts) {
-    if (n_hits) *n_hits = 0;
-    if (n_ends) *n_ends = 0;
-    if (rec) *rec = nullptr; if (start) *start = nullptr; if (stop) *stop = nullptr; if (strand) *strand = nullptr; if (edits) *edits = nullptr;
-    if (plen < 1 || plen > 64) return fail(FX_EINVAL, "pattern length %d outside 1..64", (int)plen);
-    if (max_edits < 0 || max_edits > std::min(8, plen - 1))
-        return fail(FX_EINVAL, "max_edits %d outside 0..%d", (int)max_edits, std::min(8, plen - 1));
-    if (report != FX_EDIT_ALL && report != FX_EDIT_BEST) return fail(FX_EINVAL, "report %d is neither FX_EDIT_ALL nor FX_EDIT_BEST", (int)report);
-    if (!h || !n_hits || !n_ends) return fail(FX_EINVAL, "null argument");
-    if (!(mode & (FX_SEARCH_PLUS | FX_SEARCH_MINUS))) return fail(FX_EINVAL, "no strand selected");
-    if (((mode & FX_SEARCH_PLUS) && !pat) || ((mode & FX_SEARCH_MINUS) && !rpat)) return fail(FX_EINVAL, "null pattern");
-    const bool counts_only = cap == 0 && counts, best = report == FX_EDIT_BEST;
-    if (cap < 0 || (!counts_only && (!rec || !start || !stop || !strand || !edits))) return fail(FX_EINVAL, "null output");
-    int rc;
-    if ((rc = fasta_state(h, "hits", ids, n_ids)) || (rc = fasta_device(h))) return rc;
-    std::vector<ulonglong2> masks(256);
-    {
-        std::vector<uint64_t> f(256, 0), r(256, 0);
-        if (((mode & FX_SEARCH_PLUS) && !search_masks(pat, plen, mode, f.data())) ||
-            ((mode & FX_SEARCH_MINUS) && !search_masks(rpat, plen, mode, r.data())))
-            return fail(FX_EINVAL, "a pattern letter is not an IUPAC code");
-        for (int c = 0; c < 256; ++c) masks[c] = make_ulonglong2(f[c], r[c]);
-    }
-    const int64_t n_sel = ids ? n_ids : h->n_hdr;
-    if ((rc = check_ids(ids, n_ids, h->n_hdr, nullptr, kBadRecord))) return rc;
-    if (n_sel == 0) return FX_OK;
-    Staged st(h);
-    const ulonglong2 *d_masks = nullptr;
-    if ((rc = st.up(h, masks.data(), 256, &d_masks))) return rc;
-    const bool wide = plen > 32;
-    const int k = max_edits;
+// form gives the ENDS; they are emitted on the device (hit_emit), report = best flags and scans them there, and only the rows
+// that stay get a start and go home (search_edit_rows: all of it behind the shared head, for the form of the call).
+template <class Form>
+static int search_edit_rows(fx_handle *h, Staged &st, const ulonglong2 *d_masks, int32_t plen, const Form &F, bool best, const int64_t *ids,
+                            int64_t n_ids, int64_t n_sel, int64_t cap, int64_t **rec, int64_t **start, int64_t **stop, uint8_t **strand,
+                            uint8_t **edits, int64_t *n_hits, int64_t *n_ends, int64_t *counts) {
+    const bool counts_only = cap == 0 && counts;
+    const int k = F.k;
+    const HitPass pass{K_ESEARCH_COUNT, K_ESEARCH_EMIT, 0};
     HitScans S;
     // the per-record counts of report = all are those of the ends; report = best counts its rows behind the filter
-    rc = hit_scans(
-        h, st, d_masks, plen, ids, n_ids, best ? nullptr : counts,
-        [&](HitRuns &R) { with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_ESEARCH_COUNT, k_esearch_count<W()>, dim3(R.grid_runs), dim3(BLOCK), R.P, k, R.packed.p); }); },
-        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
-            with_bool(wide, [&](auto W) { FX_LAUNCH(h, K_SEARCH_SCAN, k_esearch_fix<W()>, dim3(grid_sel), dim3(BLOCK), R.P, k, K, R.packed.p); });
-        },
-        S);
+    int rc = hit_scans(h, st, d_masks, plen, ids, n_ids, best ? nullptr : counts, F, pass, S);
     if (rc) return rc;
     if (best && counts) memset(counts, 0, (size_t)n_sel * 16);
     if (S.R.P.n_runs == 0) return FX_OK;
@@ -4204,11 +4171,7 @@ extern "C" int fx_fasta_search_edit(fx_handle *h, const uint8_t *pat, const uint
         return rc;
     int64_t *e_rec = e64.p, *e_stop = e64.p + total, *e_at = e64.p + 2 * total;
     uint8_t *e_strand = e8.p, *e_edits = e8.p + total, *keep = e8.p + 2 * total;
-    hipLaunchKernelGGL(k_search_list, dim3(S.R.grid_runs), dim3(BLOCK), 0, h->stream, (const uint32_t *)S.R.packed.p, (const int64_t *)S.NZ, P.n_runs, list.p);
-    with_bool(wide, [&](auto W) {
-        FX_LAUNCH(h, K_ESEARCH_EMIT, k_esearch_emit<W()>, dim3(nblocks(S.n_list, BLOCK)), dim3(BLOCK), P, k, (const int64_t *)list.p, S.n_list,
-                  (const int64_t *)S.K, (const int64_t *)S.Pp, (const int64_t *)S.Pm, e_rec, e_stop, e_at, e_strand, e_edits);
-    });
+    hit_emit(h, S, F, pass, list.p, e_rec, e_stop, e_at, e_strand, e_edits);
     int64_t n_rows = total;
     const int64_t *pos = nullptr;
     ScratchBuf<int64_t> posbuf;
@@ -4252,6 +4215,32 @@ extern "C" int fx_fasta_search_edit(fx_handle *h, const uint8_t *pat, const uint
     return FX_OK;
 }
 
+extern "C" int fx_fasta_search_edit(fx_handle *h, const uint8_t *pat, const uint8_t *rpat, int32_t plen, int mode, int32_t max_edits,
+                                    int32_t report, const int64_t *ids, int64_t n_ids, int64_t cap, int64_t **rec, int64_t **start,
+                                    int64_t **stop, uint8_t **strand, uint8_t **edits, int64_t *n_hits, int64_t *n_ends, int64_t *counts) {
+    if (n_hits) *n_hits = 0;
+    if (n_ends) *n_ends = 0;
+    if (rec) *rec = nullptr; if (start) *start = nullptr; if (stop) *stop = nullptr; if (strand) *strand = nullptr; if (edits) *edits = nullptr;
+    if (plen < 1 || plen > 64) return fail(FX_EINVAL, "pattern length %d outside 1..64", (int)plen);
+    if (max_edits < 0 || max_edits > std::min(8, plen - 1))
+        return fail(FX_EINVAL, "max_edits %d outside 0..%d", (int)max_edits, std::min(8, plen - 1));
+    if (report != FX_EDIT_ALL && report != FX_EDIT_BEST) return fail(FX_EINVAL, "report %d is neither FX_EDIT_ALL nor FX_EDIT_BEST", (int)report);
+    if (!h || !n_hits || !n_ends) return fail(FX_EINVAL, "null argument");
+    const bool counts_only = cap == 0 && counts;
+    int rc;
+    int64_t n_sel = 0;
+    std::optional<Staged> st;
+    const ulonglong2 *d_masks = nullptr;
+    if ((rc = search_head(h, st, pat, rpat, plen, mode, cap < 0 || (!counts_only && (!rec || !start || !stop || !strand || !edits)), ids, n_ids, &n_sel,
+                          &d_masks)) || n_sel == 0)
+        return rc;
+    with_bool(plen > 32, [&](auto W) {         // the form of this call: wide
+        rc = search_edit_rows(h, *st, d_masks, plen, EditForm<W()>{max_edits}, report == FX_EDIT_BEST, ids, n_ids, n_sel, cap, rec, start, stop, strand,
+                              edits, n_hits, n_ends, counts);
+    });
+    return rc;
+}
+
 // ------------------------------------------------------------------ position weight matrices (fx_pwm.hpp)
 // What the numbers alone decide: refused before the handle is looked at.
 static int pwm_check(const int32_t *mat, int32_t plen, int mode) {
@@ -4281,7 +4270,7 @@ static std::vector<int2> pwm_tables(const int32_t *mat, int W) {
         }
     return t;
 }
-// f(G) for the group count of this call, 1..16 (k_pwm_count alone has a G = 0 form)
+// f(G) for the group count of this call, 1..16 (k_hits_count alone has a G = 0 form)
 template <class F> static void with_groups(int G, F &&f) {
     with_int<16>(G, [&](auto N) { if constexpr (decltype(N)::value > 0) f(N); });
 }
@@ -4315,7 +4304,7 @@ static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, i
         unsigned long long *keys = nullptr;
         if ((rc = st.scratch<unsigned long long>(2 * n_sel, &keys))) return rc;
         HIPCHK(hipMemsetAsync(keys, 0, (size_t)n_sel * 16, h->stream));
-        FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<0>, dim3(R.grid_runs), dim3(BLOCK), R.P, A, R.packed.p);
+        FX_LAUNCH(h, K_PWM_COUNT, k_hits_count<PwmForm<0>>, dim3(R.grid_runs), dim3(BLOCK), R.P, PwmForm<0>{A}, R.packed.p);
         if ((rc = sscan<1>(h, st, K_SEARCH_SCAN, SrchLdKept{R.packed.p}, R.P.n_runs, R.pref.p, R.d_tot))) return rc;
         with_groups(G, [&](auto N) {
             FX_LAUNCH(h, K_PWM_BEST, k_pwm_best<decltype(N)::value>, dim3(R.grid_runs), dim3(BLOCK), R.P, A, (const int64_t *)R.pref.p, keys);
@@ -4329,22 +4318,11 @@ static int fasta_pwm(fx_handle *h, const int32_t *mat, int32_t plen, int mode, i
             }
         return FX_OK;
     }
-    return run_hits(
-        h, st, nullptr, plen, ids, n_ids, cap, counts, 4, "pwm emit",
-        [&](HitRuns &R) {
-            with_groups(G, [&](auto N) { FX_LAUNCH(h, K_PWM_COUNT, k_pwm_count<decltype(N)::value>, dim3(R.grid_runs), dim3(BLOCK), R.P, A, R.packed.p); });
-        },
-        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
-            with_groups(G, [&](auto N) { FX_LAUNCH(h, K_SEARCH_SCAN, k_pwm_fix<decltype(N)::value>, dim3(grid_sel), dim3(BLOCK), R.P, A, K, R.packed.p); });
-        },
-        [&](HitRuns &R, const int64_t *list, int64_t n_list, const int64_t *K, const int64_t *Pp, const int64_t *Pm, int64_t *o_rec, int64_t *o_start,
-            uint8_t *o_strand, void *o_score) {
-            with_groups(G, [&](auto N) {
-                FX_LAUNCH(h, K_PWM_EMIT, k_pwm_emit<decltype(N)::value>, dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), R.P, A, list, n_list, K, Pp, Pm, o_rec,
-                          o_start, o_strand, (int32_t *)o_score);
-            });
-        },
-        rec, start, strand, (void **)score, n_hits);
+    with_groups(G, [&](auto N) {               // the form of this call: groups
+        rc = run_hits(h, st, nullptr, plen, ids, n_ids, cap, counts, "pwm emit", PwmForm<N()>{A}, HitPass{K_PWM_COUNT, K_PWM_EMIT, 0}, rec, start, strand,
+                      (void **)score, n_hits);
+    });
+    return rc;
 }
 
 extern "C" int fx_fasta_pwm_scan(fx_handle *h, const int32_t *mat, int32_t plen, int mode, int32_t min_score, const int64_t *ids,
@@ -4362,8 +4340,8 @@ extern "C" int fx_fasta_pwm_best(fx_handle *h, const int32_t *mat, int32_t plen,
 }
 
 // ------------------------------------------------------------------ minimizers (fx_minimizer.hpp)
-// What the numbers alone decide is refused first, before the handle is looked at; then run_hits with the three kernels of the
-// form, each with the lanes' key rings in dynamic LDS (BLOCK * w * 8 bytes).
+// What the numbers alone decide is refused first, before the handle is looked at; then run_hits with the form, whose three
+// kernels have the lanes' key rings in dynamic LDS (BLOCK * w * 8 bytes).
 extern "C" int fx_fasta_minimizers(fx_handle *h, int32_t k, int32_t w, int flags, const int64_t *ids, int64_t n_ids, int64_t cap,
                                    int64_t **rec, int64_t **start, uint8_t **strand, uint64_t **code, int64_t *n_hits, int64_t *counts) {
     if (n_hits) *n_hits = 0;
@@ -4378,38 +4356,18 @@ extern "C" int fx_fasta_minimizers(fx_handle *h, int32_t k, int32_t w, int flags
     int64_t n_sel = 0;
     if ((rc = fasta_state(h, "windows", ids, n_ids)) || (rc = fasta_enter(h, ids, n_ids, nullptr, &n_sel))) return rc;
     if (n_sel == 0) return FX_OK;
-    const size_t lds = (size_t)BLOCK * w * sizeof(uint64_t);
-    // the kernels of this call: f(CANON, LEX)
-    auto with_form = [&](auto &&f) { with_bool(flags & FX_MZ_CANONICAL, [&](auto C) { with_bool(flags & FX_MZ_LEX, [&](auto L) { f(C, L); }); }); };
-    with_form([&](auto C, auto L) {                          // 64 KiB at w = 32: the most a launch takes without asking
-        constexpr bool c = decltype(C)::value, l = decltype(L)::value;
-        (void)hipFuncSetAttribute((const void *)k_mz_count<c, l>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
-        (void)hipFuncSetAttribute((const void *)k_mz_fix<c, l>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
-        (void)hipFuncSetAttribute((const void *)k_mz_emit<c, l>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
-    });
     Staged st(h);
-    return run_hits(
-        h, st, nullptr, k, ids, n_ids, cap, counts, 8, "minimizer emit",
-        [&](HitRuns &R) {
-            with_form([&](auto C, auto L) {
-                FX_LAUNCH_LDS(h, K_MZ_COUNT, (k_mz_count<decltype(C)::value, decltype(L)::value>), dim3(R.grid_runs), dim3(BLOCK), lds, R.P, (int)k, (int)w,
-                              R.packed.p);
-            });
-        },
-        [&](HitRuns &R, const int64_t *K, unsigned grid_sel) {
-            with_form([&](auto C, auto L) {
-                FX_LAUNCH_LDS(h, K_SEARCH_SCAN, (k_mz_fix<decltype(C)::value, decltype(L)::value>), dim3(grid_sel), dim3(BLOCK), lds, R.P, (int)k, (int)w, K,
-                              R.packed.p);
-            });
-        },
-        [&](HitRuns &R, const int64_t *list, int64_t n_list, const int64_t *K, const int64_t *Pp, const int64_t *Pm, int64_t *o_rec, int64_t *o_start,
-            uint8_t *o_strand, void *o_code) {
-            with_form([&](auto C, auto L) {
-                FX_LAUNCH_LDS(h, K_MZ_EMIT, (k_mz_emit<decltype(C)::value, decltype(L)::value>), dim3(nblocks(n_list, BLOCK)), dim3(BLOCK), lds, R.P, (int)k,
-                              (int)w, list, n_list, K, Pp, Pm, o_rec, o_start, o_strand, (uint64_t *)o_code);
-            });
-        },
-        rec, start, strand, (void **)code, n_hits);
+    with_bool(flags & FX_MZ_CANONICAL, [&](auto C) {         // the form of this call: canonical, lex
+        with_bool(flags & FX_MZ_LEX, [&](auto L) {
+            using Form = MzForm<C(), L()>;                   // 64 KiB at w = 32: the most a launch takes without asking
+            (void)hipFuncSetAttribute((const void *)k_hits_count<Form>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
+            (void)hipFuncSetAttribute((const void *)k_hits_fix<Form>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
+            (void)hipFuncSetAttribute((const void *)k_hits_emit<Form>, hipFuncAttributeMaxDynamicSharedMemorySize, BLOCK * MZ_MAX_W * 8);
+            rc = run_hits(h, st, nullptr, k, ids, n_ids, cap, counts, "minimizer emit", Form{(int)k, (int)w},
+                          HitPass{K_MZ_COUNT, K_MZ_EMIT, (size_t)BLOCK * w * sizeof(uint64_t)}, rec, start, strand, (void **)code, n_hits);
+        });
+    });
+    return rc;
 }
 
 // ------------------------------------------------------------------ regions, windows, class runs (fx_annot.hpp)

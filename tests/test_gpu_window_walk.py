@@ -107,20 +107,28 @@ def _lines(s, width):
     return "".join(s[a:a + width] + "\n" for a in range(0, len(s), width))
 
 
+class _Text:
+    """A FASTA under construction: the file, the letters of every record and the offset of every record's first sequence byte."""
+
+    def __init__(self):
+        self.text, self.seqs, self.boff = "", [], []
+
+    def add(self, at, body, letters, eol="\n"):
+        """One more record whose bytes begin at offset `at` inside a 256-byte block: its header is padded for that."""
+        head = ">r%d_" % len(self.seqs)
+        pad = (at - (len(self.text) + len(head) + len(eol))) % RUN
+        self.text += head + "x" * pad + eol
+        assert len(self.text) % RUN == at
+        self.boff.append(len(self.text))
+        self.seqs.append(letters)
+        self.text += body
+
+
 def _build_fasta(rng):
     """-> (text, seqs, boff): the file, the letters of every record and the offset of every record's first sequence byte.
     A header is padded so that the record's bytes begin at the wanted offset inside a 256-byte block."""
-    text, seqs, boff = "", [], []
-
-    def add(at, body, letters):
-        nonlocal text
-        head = ">r%d_" % len(seqs)
-        pad = (at - (len(text) + len(head) + 1)) % RUN
-        text += head + "x" * pad + "\n"
-        assert len(text) % RUN == at
-        boff.append(len(text))
-        seqs.append(letters)
-        text += body
+    t = _Text()
+    add = t.add
 
     s = _rand(rng, 300)
     add(37, _lines(s, 60), s)                                  # begins and ends off the 16-byte grid, crosses one boundary
@@ -138,14 +146,14 @@ def _build_fasta(rng):
     a, b, c = _rand(rng, 135), _rand(rng, 5), _rand(rng, 230)
     body = a + "\n" + "\n" * 4 + "\n" * 3 + b[:3] + "\r\n" + "\n" * 6 + b[3:] + c[:58] + "\n" + _lines(c[58:], 60)
     add(100, body, a + b + c)
-    assert (boff[-1] + body.index(c[:58])) % RUN == 0 and body[body.index(c[:58]) - 16:body.index(c[:58])].count("\n") == 10
+    assert (t.boff[-1] + body.index(c[:58])) % RUN == 0 and body[body.index(c[:58]) - 16:body.index(c[:58])].count("\n") == 10
     s = _rand(rng, 50)
     add(37, s + "\n", s)                                       # one short run: a masked first and last chunk and nothing between
     s = _rand(rng, 41, "ACGTN")
     add(70, s + "\n", s)
     s = _rand(rng, 310)
     add(250, _lines(s, 80)[:-1], s)                            # the last record has no final newline
-    return text, seqs, boff
+    return t.text, t.seqs, t.boff
 
 
 @pytest.fixture(scope="module")
@@ -257,6 +265,175 @@ def test_fasta_pwm(fasta, W):
     got = list(zip(h.ids.tolist(), h.starts.tolist(), h.stops.tolist(), [chr(c) for c in h.strands.tolist()], h.scores.tolist()))
     want = pwm_rows(seqs, ints, t)
     assert len(want) > 10 and len(set(row[0] for row in want)) > 3 and got == want
+
+
+# ------------------------------------------------------------------ the cut at slen
+# One count, fix and emit kernel runs under every window-hit form, and one helper places the cut for them, for the spectra and for
+# the sketches.  A record whose first line ends in CR LF and whose later lines end in LF alone has more kept bytes than slen (one
+# per later line) and `seq` stops at slen: no row may come from behind that cut.  Four records: A with whole runs behind the cut,
+# B with the cut on a 256-byte boundary of the stream, C inside one block, D without a cut.
+CUT_LINES = dict(A=(700, 60), B=(320, 60), C=(8, 20))          # record -> (lines, letters per line)
+
+
+def _mixed(s, width):
+    """The first line CR LF, the later ones LF."""
+    return s[:width] + "\r\n" + _lines(s[width:], width)
+
+
+def _cut_of(n_lines, width):
+    """(slen, raw offset of kept byte number slen from the record's first byte) of _mixed(): the index takes two bytes off every line."""
+    slen = n_lines * width - (n_lines - 1)
+    line, col = divmod(slen, width)
+    return slen, (width + 2) + (line - 1) * (width + 1) + col
+
+
+def _build_cut_fasta(rng):
+    """-> (text, kept): the file and the kept letters of every record (seq is kept[i][:slen])."""
+    t = _Text()
+    for name, at in (("A", -5), ("B", 0), ("C", None)):         # A, B: where in its block the first byte behind the cut lies
+        n, width = CUT_LINES[name]
+        s = _rand(rng, n * width)
+        t.add(60 if at is None else (at - _cut_of(n, width)[1]) % RUN, _mixed(s, width), s, eol="\r\n")      # (the header's line end is what the index goes by)
+    s = _rand(rng, 90)
+    t.add(200, s + "\n", s)                                    # D
+    return t.text, t.seqs
+
+
+def _cut_patterns(kept, slens, L):
+    """Per cut record: the site that ends exactly at slen, the same site one letter later, the last kept letters."""
+    return [(i, kept[i][n - L:n], kept[i][n - L + 1:n + 1], kept[i][-L:]) for i, n in enumerate(slens[:3])]
+
+
+@pytest.fixture(scope="module")
+def cut_text():
+    text, kept = _build_cut_fasta(np.random.default_rng(22))
+    assert 20_000 < len(text) < 80_000
+    slens = [_cut_of(*CUT_LINES[name])[0] for name in "ABC"] + [len(kept[3])]
+    return text, kept, slens, [s[:n] for s, n in zip(kept, slens)]
+
+
+def test_cut_text_is_what_the_cases_need(cut_text, oracle):
+    """No device: the conditions that keep test_cut_at_slen from passing vacuously, from the bytes and the CPU oracle's index."""
+    text, kept, slens, seqs = cut_text
+    raw = text.encode("latin-1")
+    recs, _ = oracle.fasta_index(raw)
+    assert recs["slen"].tolist() == slens
+    body = [raw[int(r["boff"]):int(r["boff"] + r["blen"])] for r in recs]
+    at = [np.flatnonzero(~np.isin(np.frombuffer(b, dtype=np.uint8), (10, 13, 32))) for b in body]      # raw offsets of the kept bytes
+    assert [bytes(np.frombuffer(b, dtype=np.uint8)[a]).decode() for b, a in zip(body, at)] == kept
+    cut = [int(r["boff"]) + int(a[n]) if n < a.size else None for r, a, n in zip(recs, at, slens)]      # stream address of kept byte number slen
+    end = [int(r["boff"] + r["blen"]) for r in recs]
+    assert end[0] // RUN - -(-cut[0] // RUN) >= 2                                   # A: two whole runs behind the cut
+    assert cut[1] % RUN == 0 and end[1] - cut[1] >= RUN and cut[1] - int(recs["boff"][1]) >= RUN      # B: a whole run on either side
+    assert int(recs["boff"][2]) // RUN == (end[2] - 1) // RUN and cut[2] is not None and len(kept[2]) - slens[2] >= 5      # C
+    assert cut[3] is None and len(kept[3]) == slens[3]                              # D
+    for L in (12, 40):
+        for i, q_at, q_past, q_tail in _cut_patterns(kept, slens, L):
+            n = slens[i]
+            assert (i, n - L, n, "+") in [row[:4] for row in hamming_rows(seqs, q_at, 0)]
+            assert not [row for row in hamming_rows(seqs, q_past, 0) + hamming_rows(seqs, q_tail, 0) if row[0] == i]
+            assert kept[i].find(q_past) == n - L + 1 and kept[i].find(q_tail) == len(kept[i]) - L      # they are there, behind the cut
+
+
+@pytest.fixture(scope="module")
+def cut_fasta(fx, cut_text, tmp_path_factory):
+    text, kept, slens, seqs = cut_text
+    fa = fx.Fasta(_write(tmp_path_factory.mktemp("wc") / "cut.fa", text))
+    assert [fa[i].seq for i in range(len(fa))] == seqs
+    return fa, seqs, kept, slens
+
+
+def _counts_of(rows, n):
+    c = np.zeros((n, 2), dtype=np.int64)
+    for row in rows:
+        c[row[0], int(row[3] == "-")] += 1
+    return c
+
+
+def _hits(h, *cols):
+    return list(zip(h.ids.tolist(), h.starts.tolist(), h.stops.tolist(), [chr(c) for c in h.strands.tolist()], *[getattr(h, c).tolist() for c in cols]))
+
+
+def _match_ints(q):
+    """The matrix that scores a letter of q 10 and any other -10."""
+    return np.array([[10 if DIGIT[c] == j else -10 for j in range(4)] for c in q], dtype=np.int32)
+
+
+@pytest.mark.parametrize("form", ["exact", "approx", "edit", "pwm-A", "pwm-B", "pwm-C", "minimizers", "kmers", "sketch"])
+def test_cut_at_slen(cut_fasta, form):
+    """Every form that shares the cut, asked for rows and for counts about the three sites of A, B and C (the matrix, whose brute
+    force is the slowest, one record's sites per case)."""
+    fa, seqs, kept, slens = cut_fasta
+    n_rec = len(seqs)
+    if form == "exact":
+        for L in (12, 40):                                     # both register widths
+            for i, q_at, q_past, q_tail in _cut_patterns(kept, slens, L):
+                for q in (q_at, q_past, q_tail):
+                    want = [row[:4] for row in hamming_rows(seqs, q, 0)]
+                    assert _hits(fa.search_all(q)) == want, (i, q)
+                    assert np.array_equal(fa.search_counts(q), _counts_of(want, n_rec)), (i, q)
+                assert (i, slens[i] - L, slens[i], "+") in _hits(fa.search_all(q_at))
+    elif form == "approx":
+        for i, q_at, q_past, q_tail in _cut_patterns(kept, slens, 12):
+            for q in (q_at, q_past, q_tail):
+                q = q[:3] + "ACGT"[(DIGIT[q[3]] + 1) % 4] + q[4:]                  # one letter off
+                want = hamming_rows(seqs, q, 2)
+                assert _hits(fa.search_approx(q, 2), "mismatches") == want, (i, q)
+                assert np.array_equal(fa.search_approx_counts(q, 2), _counts_of(want, n_rec)), (i, q)
+            assert (i, slens[i] - 12, slens[i], "+", 0) in _hits(fa.search_approx(q_at, 2), "mismatches")
+    elif form == "edit":
+        from search_edit_truth import truth
+        for i, q_at, q_past, q_tail in _cut_patterns(kept, slens, 12):
+            for q in (q_at, q_past, q_tail):
+                for report in ("all", "best"):
+                    want = truth(seqs, q, 1, report=report, rev=_rc(q))
+                    assert _hits(fa.search_edit(q, 1, report=report), "edits") == want, (i, q, report)
+                    assert np.array_equal(fa.search_edit_counts(q, 1, report=report), _counts_of(want, n_rec)), (i, q, report)
+            assert (i, slens[i] - 12, slens[i], "+", 0) in _hits(fa.search_edit(q_at, 1, report="best"), "edits")
+    elif form.startswith("pwm"):
+        from pyfastx_amd.pwm import Pwm
+        for i, q_at, q_past, q_tail in _cut_patterns(kept, slens, 12)["ABC".index(form[-1]):][:1]:
+            for q in (q_at, q_past, q_tail):
+                ints = _match_ints(q)
+                every = pwm_rows(seqs, ints, -10 ** 9)
+                want = [row for row in every if row[4] >= 80]                       # two letters off at the most
+                assert _hits(fa.pwm_scan(Pwm.from_ints(ints), min_score=80), "scores") == want, (i, q)
+                assert np.array_equal(fa.pwm_counts(Pwm.from_ints(ints), min_score=80), _counts_of(want, n_rec)), (i, q)
+                top = {}
+                for r, a, _, strand, score in every:           # the larger score, then the smaller start
+                    if (r, strand) not in top or score > top[r, strand][0]:
+                        top[r, strand] = (score, a)
+                b = fa.pwm_best(Pwm.from_ints(ints))
+                got = {(r, strand): (int(b.scores[r, col]), int(b.starts[r, col])) for r in range(n_rec) for col, strand in enumerate("+-")}
+                assert got == top, (i, q)
+                assert (got[i, "+"][0] == 120) == (q is q_at), (i, q)               # the whole site: in front of the cut only
+    elif form == "minimizers":
+        from minimizer_truth import truth
+        for k, w, canonical in ((5, 4, True), (7, 3, False)):
+            rows, counts = truth(seqs, k, w, canonical, "hash")
+            m = fa.minimizers(k, w, canonical=canonical)
+            assert list(zip(m.ids.tolist(), m.starts.tolist(), [chr(c) for c in m.strands.tolist()], m.codes.tolist())) == rows, (k, w, canonical)
+            assert np.array_equal(fa.minimizer_counts(k, w, canonical=canonical), counts), (k, w, canonical)
+            assert all((m.starts[m.ids == i] + k <= slens[i]).all() for i in range(n_rec))
+    elif form == "kmers":
+        for k, canonical in ((6, False), (3, True)):
+            per = [np.bincount(codes_of(s, k, canonical), minlength=4 ** k) for s in seqs]
+            got = fa.kmer_profile(k, canonical=canonical)
+            assert got.dtype == np.int64 and np.array_equal(got, np.array(per)), (k, canonical)
+            for i in range(n_rec):
+                assert np.array_equal(fa.kmer_counts(k, canonical=canonical, ids=[i]), per[i]), (k, canonical, i)
+            assert np.array_equal(fa.kmer_counts(k, canonical=canonical), sum(per)), (k, canonical)
+    else:
+        from sketch_truth import key_set_np
+        for k, canonical in ((15, True), (9, False)):
+            per = [key_set_np(s, k, canonical) for s in seqs]
+            sk = fa.sketch(k, scaled=1, canonical=canonical)
+            assert sk.sizes.tolist() == [p.size for p in per], (k, canonical)
+            assert all(np.array_equal(sk.hashes(i), per[i]) for i in range(n_rec)), (k, canonical)
+            pooled = fa.sketch(k, scaled=1, canonical=canonical, pooled=True)
+            assert np.array_equal(pooled.hashes(0), np.unique(np.concatenate(per))), (k, canonical)
+            behind = [np.setdiff1d(key_set_np(kept[i], k, canonical), per[i]).size for i in range(3)]
+            assert min(behind) > 0                             # keys that only the letters behind the cut hold: none came back
 
 
 # ------------------------------------------------------------------ the FASTQ
