@@ -941,6 +941,54 @@ int fx_fastq_dedup(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_
                    int64_t **pos, int64_t **copies, int64_t *n_pos, int64_t *n_groups, int64_t *n_rounds,
                    int64_t *first_bad);
 
+/* ------------------------------------------------------------------ FASTA records written back out (extension)
+ * The reference writes a record only as a verbatim copy (Sequence.raw, sequence.c:314-335) and slices one interval per call
+ * (sequence.c:76-125).  fx_fasta_format_alloc turns a batch of records or intervals of the resident stream back into FASTA text
+ * -- the counterpart of fx_fastq_format_alloc -- formatted and laid out on the device (pyfastx_amd/csrc/fx_fasta_format.hpp).
+ *
+ * Queries.  Query k is (seq_id[k], start[k], stop[k]), half-open and 0-based, exactly as fx_fasta_fetch takes them.  start =
+ *   stop = NULL: whole records, [0, slen).  seq_id = NULL is allowed only then and means the records 0..n-1.  An id outside
+ *   the table or an interval outside 0 <= start <= stop <= slen (or longer than 2^31 - 1): *first_bad = the first such query,
+ *   FX_ERANGE, nothing allocated.
+ * Letters S_k, made in this order:
+ *   1 what fx_fasta_fetch returns for the query with flags 0: the forward letters, bytes 10 / 13 / 32 dropped (a record that
+ *     is not line-regular is despaced first and sliced then);
+ *   2 FX_UPPER: a..z become A..Z;
+ *   3 the mask: a letter whose forward coordinate lies in a mask row of its record is changed -- FX_MASK_SOFT turns A..Z
+ *     into a..z, FX_MASK_UPPER a..z into A..Z, FX_MASK_HARD replaces every byte with mask_byte (0..255);
+ *   4 FX_COMPLEMENT through the IUPAC table of the fetch kernels: case is kept, so a soft mask survives;
+ *   5 FX_REVERSE.
+ *   flags (bits FX_UPPER | FX_REVERSE | FX_COMPLEMENT only) hold for every query unless flags_per_query gives a byte per query,
+ *   of which those three bits count.  L_k = |S_k|: for an irregular record the letters actually there, which can be fewer
+ *   than stop - start.
+ * Mask rows.  n_mask rows (mask_id, mask_start, mask_stop) sorted by (mask_id, mask_start), 0 <= start <= stop <= slen, every
+ *   row of a record beginning at or after the end of the row before it; empty rows are allowed.  Anything else: *first_bad =
+ *   the first such row, FX_EINVAL, nothing allocated (checked on the device).  mask_mode = FX_MASK_NONE ignores the rows.
+ * Header H_k.  hdr = NULL: the record's own header line without '>' and without its terminator, one trailing '\r' dropped
+ *   (what Sequence.description shows), copied from the stream on the device; this needs the table of fx_fasta_build
+ *   (fx_fasta_set_table installs no header columns: FX_ESTATE).  Otherwise the bytes hdr[hdr_off[k] .. hdr_off[k + 1]) as
+ *   they are (hdr_off: n + 1 ascending offsets from 0 on).
+ * Record k is '>' H_k '\n', then S_k in lines of `width` letters, each followed by '\n'; the last line may be shorter.  width
+ *   = 0: one line; L_k = 0: no sequence line; width < 0: FX_EINVAL.  Its size is |H_k| + 2 + L_k + ceil(L_k / width).  A
+ *   query with L_k < min_len (>= 0) produces no bytes.
+ * Outputs.  Record k is dst[dst_off[k] .. dst_off[k + 1]); *dst and *dst_off (n + 1 entries) are pinned blocks of
+ *   fx_pinned_alloc that belong to the caller (fx_pinned_free each), never NULL after FX_OK.  *n_kept = the records that
+ *   produced bytes, *n_bases = the sum of their L_k.  Sizes, offsets and bytes are made on the device; only the finished
+ *   bytes and the offsets come to the host.
+ * Errors: a null handle or output pointer, start without stop, seq_id = NULL with intervals, n < 0, unknown flag bits, a
+ *   mask_mode outside the four, hdr without hdr_off or offsets that descend: FX_EINVAL, nothing touched; before
+ *   fx_fasta_build: FX_ESTATE; a byte-range shard: FX_EINVAL; 2^31 queries or more: FX_ERANGE; no device: FX_EDEVICE (there is
+ *   no CPU path).
+ * fx_fasta_format_tile: the bytes of the output one workgroup of the emit kernel owns (tests place records across its edges). */
+enum { FX_MASK_NONE = 0, FX_MASK_SOFT = 1, FX_MASK_HARD = 2, FX_MASK_UPPER = 3 };
+int fx_fasta_format_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
+                          int flags, const uint8_t *flags_per_query, int64_t width,
+                          const uint8_t *hdr, const int64_t *hdr_off,
+                          int64_t n_mask, const int64_t *mask_id, const int64_t *mask_start, const int64_t *mask_stop,
+                          int mask_mode, int mask_byte, int64_t min_len,
+                          uint8_t **dst, int64_t **dst_off, int64_t *n_kept, int64_t *n_bases, int64_t *first_bad);
+int fx_fasta_format_tile(void);
+
 /* ------------------------------------------------------------------ Fastx
  * Replaces kseq_read (kseq.c:138-179) as pyfastx_fastx_next drives it (fastx.c:124-130): index-free iteration over a
  * file with kseq's own record rules -- FASTA and FASTQ records mixed, sequence / quality over any number of lines,

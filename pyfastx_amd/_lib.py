@@ -126,6 +126,8 @@ PROTOTYPES = {
     "fx_fastq_select": (i32, [vp, i32, i32, i64, i64, i64, i64, i64, i64, i64, pvp, pi64]),
     "fx_fastq_trim": (i32, [vp, vp, i64, i32, i64, i64, vp, i32, i32, i64, i64, i32, i32, i64, i64, i32, pvp, pvp, pi64, pi64]),
     "fx_fastq_format_alloc": (i32, [vp, vp, i64, vp, vp, i64, pvp, pvp, pi64, pi64, pi64]),
+    "fx_fasta_format_alloc": (i32, [vp, i64, vp, vp, vp, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, i64, pvp, pvp, pi64, pi64, pi64]),
+    "fx_fasta_format_tile": (i32, []),
     "fx_fastq_demux": (i32, [vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, i32] + [pvp] * 6 + [pi64, pi64]),
     "fx_fastq_pair_overlap": (i32, [vp, vp, vp, i64, i32, i32, i64, i64, pvp, pvp, pvp, pvp, pvp, pi64, pi64]),
     "fx_fastq_pair_merge_alloc": (i32, [vp, vp, vp, i64, vp, i64, pvp, pvp, pi64, pi64, pi64]),
@@ -889,16 +891,19 @@ class Blob:
         check(lib().fx_fasta_set_table(self._h, a[0].size, *[_ptr(x) for x in a + b]))
         self._table_ready = True
         self._n_fasta = int(a[0].size)
+        self._hdr_cols = False                              # (the .fxi rows say nothing of where the header lines lie)
 
     def fasta_build_begin(self, full_name=False, comp=False):
         """Enqueue the build and return (no host synchronisation); see fasta_build_end.  comp: the composition counters
         ride on the scan (one read of the stream for index + composition; fasta_comp* then only attribute them)."""
+        self._hdr_cols = True
         self._table_ready = True
         self._n_fasta = None
         check(lib().fx_fasta_build_begin(self._h, int(bool(full_name)) | (2 if comp else 0)))
 
     def fasta_build_sharded_begin(self, comm, full_name=False, comp=False):
         """fx_fasta_build_sharded_begin: scan + tables + summary + ncclAllGather + stitch, enqueued on the handle's stream."""
+        self._hdr_cols = True
         self._table_ready = True
         self._n_fasta = None
         check(lib().fx_fasta_build_sharded_begin(self._h, comm._c, int(bool(full_name)) | (2 if comp else 0)))
@@ -915,6 +920,7 @@ class Blob:
         return s
 
     def fasta_build(self, full_name=False, comp=False):
+        self._hdr_cols = True
         self._table_ready = True
         s = FastaSummary()
         check(lib().fx_fasta_build(self._h, int(bool(full_name)) | (2 if comp else 0), C.byref(s)))
@@ -1199,6 +1205,31 @@ class Blob:
             _raise(rc, first_bad=int(bad.value))
         o = pinned_array(offs.value, n + 2, np.int64)[:n + 1]
         return pinned_array(dst.value, max(int(o[n]), 1))[:int(o[n])], o
+
+    def fasta_format_alloc(self, n, seq_id=None, start=None, stop=None, flags=0, flags_per_query=None, width=60, hdr=None,
+                           hdr_off=None, mask=None, mask_mode=0, mask_byte=78, min_len=0):
+        """FASTA records of n queries (fx_fasta_format_alloc): seq_id None: the records 0..n-1; start = stop = None: whole
+        records; hdr / hdr_off: the headers' bytes and their n + 1 offsets, or None for the records' own; mask: None or
+        (ids, starts, stops) sorted and disjoint -> (uint8 buffer, int64 offsets[n + 1], records kept, their letters), pinned.
+        A bad query raises FxError(FX_ERANGE), a bad mask row FxError(FX_EINVAL), each with .first_bad."""
+        def i64(a):
+            return None if a is None else np.ascontiguousarray(a, dtype=np.int64)
+        seq_id, start, stop, hdr_off = i64(seq_id), i64(start), i64(stop), i64(hdr_off)
+        fpq = None if flags_per_query is None else np.ascontiguousarray(flags_per_query, dtype=np.uint8)
+        hdr = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.uint8)
+        m = (None, None, None) if mask is None else tuple(i64(a) for a in mask)
+        n_mask = 0 if mask is None else int(m[0].size)
+        if n_mask == 0:
+            m = (None, None, None)
+        for a in (seq_id, start, stop, fpq):
+            if a is not None and a.size != n:
+                raise ValueError("a query array does not hold one row per query (%d)" % n)
+        if hdr is not None and (hdr_off is None or hdr_off.size != n + 1):
+            raise ValueError("hdr_off must hold n + 1 offsets")
+        head = (self._h, int(n), _ptr(seq_id), _ptr(start), _ptr(stop), int(flags), _ptr(fpq), int(width), _ptr(hdr), _ptr(hdr_off),
+                n_mask, _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), int(mask_mode), int(mask_byte), int(min_len))
+        (dst, offs), (kept, bases, _) = _call(lib().fx_fasta_format_alloc, head, (RAW, RAW), counters=(0, 0, -1), err=("first_bad", 2))
+        return _ragged(dst, offs, int(n)) + (kept, bases)
 
     def fasta_search(self, pattern, rpattern, mode, ids=None, cap=0, counts=False, max_mismatch=None, anchor=0):
         """Every overlapping hit of one pattern on the resident table (fx_fasta_search): pattern / rpattern are the bytes

@@ -1174,6 +1174,164 @@ class Fasta(_fxobj.FastaCore):
         buf, offs, _ = self._st.blob.fetch_ranges(off, ln, ln, flags=_F_RAW)
         return buf, offs
 
+    # ------------------------------------------------------------- records written back out (fasta_out.py)
+    def _records_plan(self, names_or_ids, starts, stops, strand, width, mask, mask_mode, mask_char, uppercase, headers, min_len):
+        """The arguments of records / write, checked, as one dict of per-query arrays that _records_call cuts batches from."""
+        from . import fasta_out as fo
+        width = fo.check_width(width)
+        mode = fo.check_mask_mode(mask_mode)
+        byte = fo.check_mask_char(mask_char)
+        min_len = fo._int(min_len, "min_len", 0)
+        rows = fo.mask_rows(mask)
+        blob = self._search_blob()
+        t = self._table()
+        names = None
+        if names_or_ids is None:
+            ids, n = None, self._seq_counts
+        else:
+            n = len(names_or_ids)
+            if n and isinstance(names_or_ids[0], str):
+                names = list(names_or_ids)
+                ids = np.empty(n, dtype=np.int64)
+                bad = _fxobj.ids_of_names(names, t["index"], ids)
+                if bad >= 0:
+                    raise KeyError("%s does not exist in fasta file" % names[bad])
+            else:
+                ids = np.ascontiguousarray(names_or_ids, dtype=np.int64)
+                if ids.ndim != 1:
+                    raise ValueError("ids must be one-dimensional")
+        starts, stops = fo.check_intervals(starts, stops, n)
+        if ids is None and starts is not None:
+            ids = np.arange(n, dtype=np.int64)
+        neg = fo.strand_flags(strand, n)
+        fl = _F_UP if (uppercase or self._uppercase) else 0
+        fpq = (neg.view(np.uint8) * np.uint8(_F_REV | _F_COMP) | np.uint8(fl)) if neg.any() else None
+        hdr = None
+        if isinstance(headers, str) and headers == "auto":
+            if starts is not None:
+                if names is None:
+                    self._check_id_rows(ids)
+                    chroms = self._chrom_names()
+                    names = [chroms[i] for i in ids.tolist()]
+                hdr = fo.pack_headers(fo.auto_headers(names, starts, stops, neg), n)
+            elif not getattr(blob, "_hdr_cols", False):     # a table installed from the .fxi: the header lines in ONE gather
+                hdr = self._own_headers(ids)
+        else:
+            hdr = fo.pack_headers(headers, n)
+        return {"blob": blob, "n": n, "ids": ids, "starts": starts, "stops": stops, "neg": neg, "flags": fl, "fpq": fpq, "width": width,
+                "mask": rows if mode else None, "mode": mode, "byte": byte, "hdr": hdr, "min_len": min_len}
+
+    def _check_id_rows(self, ids):
+        """The IndexError of the first id outside the table, naming its row (what the device reports for the batch)."""
+        if ids.size and (ids.min() < 0 or ids.max() >= self._seq_counts):
+            k = int(np.flatnonzero((ids < 0) | (ids >= self._seq_counts))[0])
+            err = IndexError("index out of range (query %d)" % k)
+            err.first_bad = k
+            raise err
+
+    def _chrom_names(self):
+        if getattr(self, "_chroms", None) is None:
+            self._chroms = [r[0] for r in self._db.execute("SELECT chrom FROM seq ORDER BY ID")]
+        return self._chroms
+
+    def _hdr_cols_host(self):
+        """(offset, length) of every record's header line behind '>', from the .fxi rows (sequence.c:299-313)."""
+        if getattr(self, "_hdr_host", None) is None:
+            a = np.array(self._db.execute("SELECT boff,elen,dlen FROM seq ORDER BY ID").fetchall(), dtype=np.int64).reshape(-1, 3)
+            self._hdr_host = (a[:, 0] - a[:, 2] - a[:, 1], a[:, 2])
+        return self._hdr_host
+
+    def _own_headers(self, ids):
+        off, ln = self._hdr_cols_host()
+        if ids is not None:
+            self._check_id_rows(ids)
+            off, ln = off[ids], ln[ids]
+        if off.size == 0:
+            return np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.int64)
+        buf, offs, _ = self._st.blob.fetch_ranges(off, ln, ln, flags=_F_RAW)
+        return (buf if buf.size else np.zeros(1, dtype=np.uint8)), np.ascontiguousarray(offs, dtype=np.int64)
+
+    def _records_call(self, q, lo, hi):
+        """Queries [lo, hi) of a plan through fx_fasta_format_alloc -> (buffer, offsets, records kept, their letters)."""
+        from . import fasta_out as fo
+        whole = lo == 0 and hi == q["n"]
+        cut = (lambda a: a if a is None or whole else a[lo:hi])
+        ids = q["ids"]
+        if ids is None and lo:
+            ids = np.arange(lo, hi, dtype=np.int64)
+        else:
+            ids = cut(ids)
+        hdr = hdr_off = None
+        if q["hdr"] is not None:
+            hdr, hdr_off = q["hdr"]
+            if not whole:
+                b0, b1 = int(hdr_off[lo]), int(hdr_off[hi])
+                hdr, hdr_off = (hdr[b0:b1] if b1 > b0 else np.zeros(1, dtype=np.uint8)), hdr_off[lo:hi + 1] - b0
+        mask = q["mask"]
+        if mask is not None and not whole:
+            mask = fo.slice_mask(mask, ids if ids is not None else np.arange(lo, hi, dtype=np.int64))
+        try:
+            return q["blob"].fasta_format_alloc(hi - lo, ids, cut(q["starts"]), cut(q["stops"]), flags=q["flags"], flags_per_query=cut(q["fpq"]),
+                                                width=q["width"], hdr=hdr, hdr_off=hdr_off, mask=mask, mask_mode=q["mode"], mask_byte=q["byte"],
+                                                min_len=q["min_len"])
+        except _lib.FxError as e:
+            err = fo.bad_query(e, ids, self._seq_counts, lo)
+            raise (_fx_to_py(e) if err is e else err)
+
+    def records(self, names_or_ids=None, starts=None, stops=None, strand=None, width=60, mask=None, mask_mode="soft", mask_char="N",
+                uppercase=False, headers="auto", min_len=0):
+        """Extension: FASTA records of whole sequences (names_or_ids None: every record) or of 0-based half-open intervals
+        (starts, stops), formatted and laid out back to back on the GPU (csrc/fx_fasta_format.hpp) -> (uint8 buffer, int64
+        offsets[n + 1]) in pinned memory.  A record is '>' header, then the letters in lines of `width` (0: one line).  The
+        letters are those of fetch_many, then: upper-cased (uppercase=True, or a file opened with it); masked where `mask`
+        -- any object with .ids / .starts / .stops (ClassRuns, TandemRepeats, Orfs, hit rows) or a 3-tuple of arrays, merged
+        first -- covers their forward coordinate (mask_mode "soft": lower case, "upper": upper case, "hard": mask_char,
+        "none"); reverse-complemented where strand (None, '+', '-' or one per row) says '-', case kept.  headers "auto": a
+        whole record keeps its own header line, an interval gets name:start+1-stop, "(-)" appended on the minus strand;
+        else one str / bytes per row.  A query with fewer than min_len letters produces no bytes (an empty range).  An
+        unknown name: KeyError; a bad id or interval: IndexError / ValueError naming the row; a bad width, mask_mode or
+        mask_char: ValueError."""
+        q = self._records_plan(names_or_ids, starts, stops, strand, width, mask, mask_mode, mask_char, uppercase, headers, min_len)
+        buf, offs, _, _ = self._records_call(q, 0, q["n"])
+        return buf, offs
+
+    def write(self, path, names_or_ids=None, starts=None, stops=None, strand=None, width=60, mask=None, mask_mode="soft", mask_char="N",
+              uppercase=False, headers="auto", min_len=0, batch_bytes=1 << 30):
+        """Extension: the records of `records` written to the plain file `path`, in batches of consecutive queries whose
+        size bound fits batch_bytes of pinned memory (a single larger query goes alone) -> {"records": records written,
+        "bases": their letters, "dropped": queries that fell below min_len}."""
+        from . import fasta_out as fo
+        q = self._records_plan(names_or_ids, starts, stops, strand, width, mask, mask_mode, mask_char, uppercase, headers, min_len)
+        n, ids = q["n"], q["ids"]
+        slen = np.asarray(self._table()["slen"], dtype=np.int64)
+        if ids is not None:
+            self._check_id_rows(ids)
+        sl = slen if ids is None else slen[ids]
+        if q["starts"] is not None:
+            bad = np.flatnonzero((q["starts"] < 0) | (q["stops"] < q["starts"]) | (q["stops"] > sl))
+            if bad.size:
+                err = ValueError("interval outside the sequence (query %d)" % int(bad[0]))
+                err.first_bad = int(bad[0])
+                raise err
+            letters = q["stops"] - q["starts"]
+        else:
+            letters = sl
+        if q["hdr"] is not None:
+            hl = np.diff(q["hdr"][1])
+        else:
+            hl = self._hdr_cols_host()[1]
+            hl = hl if ids is None else hl[ids]
+        bound = fo.size_bound(hl, letters, q["width"])
+        fo._int(batch_bytes, "batch_bytes", 1)
+        kept = bases = 0
+        with open(path, "wb") as f:
+            for lo, hi in fo.batches(bound, batch_bytes):
+                buf, _, k, b = self._records_call(q, lo, hi)
+                f.write(memoryview(buf))
+                kept += k
+                bases += b
+        return {"records": int(kept), "bases": int(bases), "dropped": int(n - kept)}
+
 
 class FastaKeys:
     """pyfastx.FastaKeys (fakeys.c): a view of the sequence names over the .fxi with the reference's sort / filter

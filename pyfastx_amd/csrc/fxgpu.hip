@@ -52,6 +52,7 @@
 #include "fx_orf.hpp"
 #include "fx_fastq_qc.hpp"
 #include "fx_fastq_trim.hpp"
+#include "fx_fasta_format.hpp"
 #include "fx_fastq_demux.hpp"
 #include "fx_fastq_pair.hpp"
 #include "fx_kmer.hpp"
@@ -372,10 +373,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_ESEARCH_COUNT, K_ESEARCH_EMIT, K_ESEARCH_BEST, K_ESEARCH_START, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_ESEARCH_COUNT, K_ESEARCH_EMIT, K_ESEARCH_BEST, K_ESEARCH_START, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_FA_FORMAT_SIZE, K_FA_FORMAT_SCAN, K_FA_FORMAT_EMIT, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_esearch_count", "k_esearch_emit", "k_esearch_best", "k_esearch_start", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_esearch_count", "k_esearch_emit", "k_esearch_best", "k_esearch_start", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce", "k_fa_format_size", "k_fa_format_scan", "k_fa_format_emit"};
 
 struct Prof {
     bool on = false;
@@ -471,6 +472,7 @@ struct fx_handle {
     DevBuf<uint32_t> fa_bad;
     int64_t n_hdr = 0, fa_seqlen = 0;
     bool fasta_built = false;
+    bool fa_hdr_cols = false;                 // hoff / dlen hold the header lines (a build; not fx_fasta_set_table)
     bool build_pending = false;               // fx_fasta_build_begin enqueued, totals not read back yet
     int pending_full_name = 0;
     DevBuf<uint32_t> comp_runs;               // a build with composition (k_scan_comp): 16 words per run of comp_gpw granules
@@ -2308,7 +2310,7 @@ extern "C" int fx_fasta_build_begin(fx_handle *h, int full_name) {
     if ((rc = enqueue_records(h, full_name))) return rc;
     h->build_pending = true;
     h->pending_full_name = full_name;
-    h->fasta_built = true;
+    h->fasta_built = h->fa_hdr_cols = true;
     return FX_OK;
 }
 
@@ -2374,6 +2376,7 @@ extern "C" int fx_fasta_set_table(fx_handle *h, int64_t n, const int64_t *boff, 
     HIPCHK(hipStreamSynchronize(h->stream));
     h->n_hdr = n;
     h->fasta_built = true;
+    h->fa_hdr_cols = false;                                  // (the .fxi rows say nothing of where the header lines lie)
     return FX_OK;
 }
 
@@ -5022,6 +5025,125 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
     };
     if ((rc = run_records(h, st, n, K_FQ_FORMAT_SCAN, "format", kBadInterval, count, emit, dst, dst_off, n_kept, first_bad))) return rc;
     *n_rows = n;
+    return FX_OK;
+}
+
+// ------------------------------------------------------------------ FASTA records written back out (fx_fasta_format.hpp)
+// Extension: the reference has no counterpart (verbatim copies only, sequence.c:314-335).
+extern "C" int fx_fasta_format_tile(void) { return FAF_TILE; }
+
+extern "C" int fx_fasta_format_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop, int flags,
+                                     const uint8_t *flags_per_query, int64_t width, const uint8_t *hdr, const int64_t *hdr_off, int64_t n_mask,
+                                     const int64_t *mask_id, const int64_t *mask_start, const int64_t *mask_stop, int mask_mode, int mask_byte,
+                                     int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_kept, int64_t *n_bases, int64_t *first_bad) {
+    if (!h || !dst || !dst_off || !n_kept || !n_bases || !first_bad) return fail(FX_EINVAL, "null argument");
+    *dst = nullptr; *dst_off = nullptr; *n_kept = 0; *n_bases = 0; *first_bad = -1;
+    if (n < 0) return fail(FX_EINVAL, "negative query count");
+    if ((start == nullptr) != (stop == nullptr)) return fail(FX_EINVAL, "start and stop come together");
+    if (!seq_id && start) return fail(FX_EINVAL, "intervals need record ids");
+    if (width < 0) return fail(FX_EINVAL, "negative line width");
+    if (min_len < 0) return fail(FX_EINVAL, "negative min_len");
+    if (flags & ~(FX_UPPER | FX_REVERSE | FX_COMPLEMENT)) return fail(FX_EINVAL, "unknown flag bits");
+    if (mask_mode < FX_MASK_NONE || mask_mode > FX_MASK_UPPER) return fail(FX_EINVAL, "mask_mode %d is none of the four", mask_mode);
+    if (mask_byte < 0 || mask_byte > 255) return fail(FX_EINVAL, "mask_byte %d outside 0..255", mask_byte);
+    const bool masked = mask_mode != FX_MASK_NONE && n_mask > 0;
+    if (n_mask < 0 || (masked && (!mask_id || !mask_start || !mask_stop))) return fail(FX_EINVAL, "null mask array");
+    if (hdr && !hdr_off) return fail(FX_EINVAL, "header bytes without their offsets");
+    int rc = fasta_state(h, "formatted records", nullptr, 0);
+    if (rc) return rc;
+    if (!hdr && !h->fa_hdr_cols) return fail(FX_ESTATE, "the table of fx_fasta_set_table holds no header lines: pass the headers");
+    if ((rc = fasta_device(h))) return rc;
+    if (n >= 0x7FFFFFFFll) return fail(FX_ERANGE, "too many queries in one batch");
+    if (hdr) {
+        if (hdr_off[0] != 0) return fail(FX_EINVAL, "header offsets begin at 0");
+        for (int64_t k = 0; k < n; ++k)
+            if (hdr_off[k + 1] < hdr_off[k] || hdr_off[k + 1] - hdr_off[k] > 0x7FFFFFFFll) return fail(FX_EINVAL, "header offsets descend at query %lld", (long long)k);
+    }
+    width = std::min<int64_t>(width, 0x7FFFFFFFll);          // (no query holds more letters: one line either way)
+    PinnedOut<2> out(h);                                   // the records, their offsets
+    if (n == 0) {
+        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
+        out.as<int64_t>(1)[0] = 0;
+        out.release(dst, dst_off);
+        return FX_OK;
+    }
+    Staged st(h);
+    const int64_t hdr_bytes = hdr ? hdr_off[n] : 0;
+    st.reserve_pin((seq_id ? n : 0) * 8 + (start ? 2 * n : 0) * 8 + (flags_per_query ? n : 0) + hdr_bytes + (hdr ? (n + 1) * 8 : 0) +
+                   (masked ? n_mask * 24 : 0) + 8 * 256 + 1024);
+    FaFmtQ Q{};
+    const uint8_t *d_hdr = nullptr;
+    const int64_t *d_ms = nullptr, *d_me = nullptr;
+    if ((rc = st.up(h, seq_id, seq_id ? n : 0, &Q.id)) || (rc = st.up(h, start, start ? n : 0, &Q.start)) || (rc = st.up(h, stop, stop ? n : 0, &Q.stop)) ||
+        (rc = st.up(h, flags_per_query, flags_per_query ? n : 0, &Q.qflags)) || (rc = st.up(h, hdr, hdr_bytes, &d_hdr)) ||
+        (rc = st.up(h, hdr_off, hdr ? n + 1 : 0, &Q.hdr_off)) || (rc = st.up(h, mask_id, masked ? n_mask : 0, &Q.mask_id)) ||
+        (rc = st.up(h, mask_start, masked ? n_mask : 0, &d_ms)) || (rc = st.up(h, mask_stop, masked ? n_mask : 0, &d_me)))
+        return rc;
+    Q.n_mask = masked ? n_mask : 0;
+    const FaFmtTab tab{h->hdr.p, h->fa_boff.p, h->fa_slen.p, h->fa_llen.p, h->fa_elen.p, h->fa_reg.p, h->fa_dlen.p, h->n_hdr};
+    BadFlag bad;
+    if (masked) {                                          // the rows first: a bad one ends the call before anything is sized
+        if ((rc = bad.arm(h, st))) return rc;
+        FX_LAUNCH(h, K_FA_FORMAT_SIZE, k_fa_format_mask, dim3(nblocks(n_mask, BLOCK)), dim3(BLOCK), Q.mask_id, d_ms, d_me, n_mask, tab.slen, tab.n_seq, bad.d);
+        HIPCHK(hipGetLastError());
+        if ((rc = bad.read(h, first_bad))) return rc;
+        if (*first_bad >= 0) return fail(FX_EINVAL, "mask row %lld: outside its record, or not sorted and disjoint", (long long)*first_bad);
+    }
+    ScratchBuf<FaFmtDesc> desc;
+    ScratchBuf<int64_t> cnt, offs, fl;                     // sizes; offsets, records there, letters (n + 1 each); the FLAT list: query, id, start, stop
+    ScratchBuf<uint8_t> force, dev, letters;               // queries an emit pass found white space in; the records; the despaced letters of the FLAT ones
+    int *d_ctl = nullptr;                                  // the FLAT queries, "an emit pass met white space"
+    int64_t *d_tot = nullptr;
+    if ((rc = desc.alloc(h->device, n, h->stream)) || (rc = cnt.alloc(h->device, n, h->stream)) || (rc = offs.alloc(h->device, 3 * (n + 1), h->stream)) ||
+        (rc = fl.alloc(h->device, 4 * n, h->stream)) || (rc = force.alloc(h->device, n, h->stream)) || (rc = st.scratch<int>(2, &d_ctl)) ||
+        (rc = st.scratch<int64_t>(4, &d_tot)) || (rc = bad.arm(h, st)))
+        return rc;
+    HIPCHK(hipMemsetAsync(force.p, 0, (size_t)n, h->stream));
+    Q.force = force.p;
+    uint8_t *d_comp = nullptr;
+    if ((rc = st.scratch<uint8_t>(256, &d_comp))) return rc;
+    hipLaunchKernelGGL(k_fa_format_lut, dim3(1), dim3(BLOCK), 0, h->stream, d_comp);
+    // Two rounds at most: the second only when the first met white space where the line arithmetic expects letters; the queries
+    // it marked are FLAT then, and a FLAT query cannot be marked.
+    for (int round = 0; round < 2; ++round) {
+        HIPCHK(hipMemsetAsync(d_ctl, 0, 2 * sizeof(int), h->stream));
+        int64_t *const f_q = fl.p, *const f_id = fl.p + n, *const f_a = fl.p + 2 * n, *const f_b = fl.p + 3 * n;
+        FX_LAUNCH(h, K_FA_FORMAT_SIZE, k_fa_format_size, dim3(nblocks(n, BLOCK)), dim3(BLOCK), h->d_data, h->n, tab, Q, n, flags, width, min_len, desc.p,
+                  cnt.p, bad.d, f_q, f_id, f_a, f_b, d_ctl);
+        HIPCHK(hipGetLastError());
+        int ctl[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, h->stream));       // (lands before the flag does)
+        if ((rc = bad.read(h, first_bad))) return rc;
+        if (*first_bad >= 0) return fail(FX_ERANGE, "query %lld: record id or interval outside the sequence", (long long)*first_bad);
+        const int64_t n_flat = ctl[0];
+        if (n_flat > 0) {                                  // their forward letters, despaced by the fetch kernels; L = what came
+            int64_t *f_off = nullptr, *f_len = nullptr, f_total = 0;
+            if ((rc = st.scratch<int64_t>(n_flat + 1, &f_off)) || (rc = st.scratch<int64_t>(n_flat, &f_len)) ||
+                (rc = sscan<1>(h, st, K_FA_FORMAT_SCAN, FafLdFlat{f_a, f_b}, n_flat, f_off, d_tot + 3)) || (rc = read_home(h, &f_total, d_tot + 3, 8)) ||
+                (rc = letters.alloc(h->device, std::max<int64_t>(f_total, 1), h->stream)))
+                return rc;
+            FetchQ fq;
+            memset(&fq, 0, sizeof fq);
+            fq.seq_id = f_id; fq.start = f_a; fq.stop = f_b; fq.dst_off = f_off; fq.out_len = f_len;
+            if ((rc = fetch_launch(h, st, fq, true, f_total / n_flat > 512, n_flat, 0, letters.p))) return rc;
+            FX_LAUNCH(h, K_FA_FORMAT_SIZE, k_fa_format_fix, dim3(nblocks(n_flat, BLOCK)), dim3(BLOCK), (const int64_t *)f_q, (const int64_t *)f_off,
+                      (const int64_t *)f_len, n_flat, width, min_len, desc.p, cnt.p);
+        }
+        int64_t tot[3] = {0, 0, 0};
+        if ((rc = sscan<3>(h, st, K_FA_FORMAT_SCAN, FafLdSize{cnt.p, desc.p}, n, offs.p, d_tot)) || (rc = read_home(h, tot, d_tot, 24))) return rc;
+        const int64_t total = tot[0];
+        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 2) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
+        if ((rc = dev.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return rc;
+        if (total > 0)
+            FX_LAUNCH(h, K_FA_FORMAT_EMIT, k_fa_format_emit, dim3((unsigned)nblocks(total, FAF_TILE)), dim3(BLOCK), h->d_data, h->n, (const uint8_t *)letters.p, d_hdr,
+                      (const FaFmtDesc *)desc.p, (const int64_t *)offs.p, n, total, width, d_ms, d_me, masked ? mask_mode : 0, mask_byte, (const uint8_t *)d_comp, dev.p, force.p, d_ctl + 1);
+        if ((rc = home(h, "formatted records", {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}, {ctl, d_ctl, (int64_t)sizeof ctl}}))) return rc;
+        if (!ctl[1]) { *n_kept = tot[1]; *n_bases = tot[2]; break; }
+        if (round == 1) return fail(FX_EDEVICE, "formatted records: white space in despaced letters");
+        fx_pinned_free(out.p[0]); fx_pinned_free(out.p[1]);
+        out.p[0] = out.p[1] = nullptr;
+    }
+    out.release(dst, dst_off);
     return FX_OK;
 }
 
