@@ -500,6 +500,52 @@ int fx_fasta_window_counts(fx_handle *h, const int64_t *ids, int64_t n_ids, int6
 int fx_fasta_class_runs(fx_handle *h, const uint8_t *set32, int64_t min_len, const int64_t *ids, int64_t n_ids, int64_t max_runs,
                         int64_t **rec, int64_t **start, int64_t **stop, int64_t *n, int64_t *n_total);
 
+/* ------------------------------------------------------------------ low-complexity sequence (DUST triplet score; extension)
+ * The mask people run before a search, a k-mer count or a sketch, and the low-complexity read filter
+ * (pyfastx_amd/csrc/fx_dust.hpp).  The reference has no such call.
+ *   Text and letters.  The text of a record and its coordinates are those of fx_fasta_class_runs: the kept bytes (10 / 13 / 32
+ *   dropped), cut at slen, 0-based, half-open.  Letters fold as in the k-mer entries: A a = 0, C c = 1, G g = 2, T t = 3;
+ *   every other kept byte (N, IUPAC codes, U, ...) is INVALID.  Soft-masked sequence therefore scores like upper case.
+ *
+ * fx_fasta_low_complexity: WINDOWED DUST.  window W in 4..64 letters; threshold T in 1..1000, in tenths as sdust and
+ * dustmasker write it (20 means a score of 2.0); min_len >= 1.  Per record of text length L:
+ *   - a triplet at position p is valid when t[p], t[p + 1], t[p + 2] are all valid; its code 16 a + 4 b + c is 0..63;
+ *   - for every e in 2..L - 1 the window that ends at e holds the letters [max(0, e - W + 1), e]: windows at a record's start
+ *     are shorter than W, and a record shorter than W is scored by these alone;
+ *   - c_x = the number of valid triplets of code x that lie wholly inside the window, n = sum c_x,
+ *     S = sum c_x (c_x - 1) / 2;
+ *   - the window QUALIFIES iff n >= 2 and 10 S > T (n - 1) -- all integers, S <= 1891;
+ *   - a triplet that holds an invalid letter is not counted; the window still spans W letters.
+ * The masked set of the record is the union of [max(0, e - W + 1), e + 1) over its qualifying e; the rows are the maximal
+ * intervals of that union (touching intervals are one row); rows shorter than min_len are dropped after the merge.  Rows are
+ * ordered by the position of the record in ids (NULL: all; any order), then by start -- no sort, no atomic.  Nothing joins
+ * across two records, no count or letter of one record reaches the next, a window of only N never qualifies.
+ * This is the windowed form: a whole window is masked, so flanks of up to W minus about 23 letters go with a repeat at W = 64,
+ * T = 20; a smaller window is the finer knob.  sdust's "perfect intervals" are not implemented and parity with sdust /
+ * dustmasker is not claimed.
+ * *n_total = the number of rows; above max_rows: FX_ERANGE, *n = 0 and nothing is allocated; else *n = *n_total rows in
+ * pinned blocks of fx_pinned_alloc that belong to the caller (fx_pinned_free each), never NULL after FX_OK, even for 0 rows.
+ * Builds the rank index when it is not there.  Without a device FX_EDEVICE before any argument is looked at.  FX_EINVAL: a
+ * null handle or output pointer, window outside 4..64, threshold outside 1..1000, min_len < 1, max_rows < 0, a count of ids
+ * without its array, a byte-range shard.  FX_ESTATE: no table built.  An id outside the table: FX_ERANGE.
+ *
+ * fx_fastq_complexity: per query, for s = seq[start:end] of read ids[q] (ids, n_ids, start, end, *first_bad exactly as
+ * fx_fastq_kmers takes them: ids NULL = every read, any order, repeats allowed; start / end both NULL = whole reads):
+ *   length[q]      end - start (int64);
+ *   n_triplets[q]  the number of valid triplets of s (int32);
+ *   dust_sum[q]    sum c_x (c_x - 1) / 2 over the triplet codes of the whole interval (int64; a read of any length, no counter
+ *                  wraps below 2^32 letters);
+ *   n_diff[q]      the number of j with raw byte s[j] != s[j + 1] (int32): fastp's complexity numerator.
+ * The callers derive dust = 10 dust_sum / (n_triplets - 1) (0 when n_triplets < 2; prinseq's scale without its window
+ * averaging) and complexity = n_diff / (length - 1).  One row per query, *n_rows of them, in pinned blocks as above.  Without
+ * a device FX_EDEVICE before any argument is looked at.  FX_EINVAL: a null handle or output pointer, start without end, a
+ * negative id count, a byte-range shard.  FX_ESTATE: before fx_fastq_build.  An id outside the table, or an interval outside
+ * 0 <= start <= end <= rlen: *first_bad = its position among the queries, FX_ERANGE, nothing allocated. */
+int fx_fasta_low_complexity(fx_handle *h, int32_t window, int32_t threshold, int64_t min_len, const int64_t *ids, int64_t n_ids,
+                            int64_t max_rows, int64_t **rec, int64_t **start, int64_t **stop, int64_t *n, int64_t *n_total);
+int fx_fastq_complexity(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end, int64_t **length,
+                        int32_t **n_triplets, int64_t **dust_sum, int32_t **n_diff, int64_t *n_rows, int64_t *first_bad);
+
 /* ------------------------------------------------------------------ tandem repeats
  * fx_fasta_tandem_repeats (extension; the reference has no repeat search): the perfect tandem repeats (microsatellites) of
  * period 1..8 of the selected records (pyfastx_amd/csrc/fx_tandem.hpp).  The text and the coordinates are those of the section

@@ -115,6 +115,8 @@ PROTOTYPES = {
     "fx_fasta_region_counts": (i32, [vp, i32, i64, vp, vp, vp, vp, pi64]),
     "fx_fasta_window_counts": (i32, [vp, vp, i64, i64, i64, i32, i64] + [pvp] * 4 + [pi64]),
     "fx_fasta_class_runs": (i32, [vp, vp, i64, vp, i64, i64] + [pvp] * 3 + [pi64] * 2),
+    "fx_fasta_low_complexity": (i32, [vp, i32, i32, i64, vp, i64, i64] + [pvp] * 3 + [pi64] * 2),
+    "fx_fastq_complexity": (i32, [vp, vp, i64, vp, vp] + [pvp] * 4 + [pi64] * 2),
     "fx_fasta_tandem_repeats": (i32, [vp, vp, i32, i64, vp, i64, i64] + [pvp] * 5 + [pi64] * 2),
     "fx_fasta_orfs": (i32, [vp, u64, u64, i32, i32, i64, vp, i64, i64] + [pvp] * 5 + [pi64] * 2),
     "fx_fasta_translate_alloc": (i32, [vp, i64, vp, vp, vp, vp, vp, u8, pvp, pvp, pi64]),
@@ -1345,6 +1347,19 @@ class Blob:
             raise ValueError("a byte set is 32 bytes")
         return _call(lib().fx_fasta_class_runs, (self._h, bits, int(min_len), *_sel(ids), int(cap)), [np.int64] * 3,
                      counters=(0, 0), err=("n_rows", 1))[0]
+
+    def fasta_low_complexity(self, window=64, threshold=20, min_len=1, ids=None, cap=10**8):
+        """The low-complexity intervals of the windowed DUST score (fx_fasta_low_complexity): window 4..64 letters, threshold
+        in tenths -> (rec, start, stop) pinned arrays; more than `cap` raise FxError(FX_ERANGE) whose .n_rows is the true
+        count."""
+        return _call(lib().fx_fasta_low_complexity, (self._h, int(window), int(threshold), int(min_len), *_sel(ids), int(cap)), [np.int64] * 3,
+                     counters=(0, 0), err=("n_rows", 1))[0]
+
+    def fastq_complexity(self, ids=None, start=None, end=None):
+        """Per query the columns of seq[start:end] (fx_fastq_complexity) -> (length int64, n_triplets int32, dust_sum int64,
+        n_diff int32) in pinned memory.  A bad id or interval raises FxError(FX_ERANGE) with .first_bad."""
+        return _call(lib().fx_fastq_complexity, (self._h, *self._fastq_queries(ids, start, end)), (np.int64, np.int32, np.int64, np.int32),
+                     counters=(0, -1), err=("first_bad", 1))[0]
 
     def fasta_tandem_repeats(self, min_copies, min_len=0, ids=None, cap=10**8):
         """The perfect tandem repeats of period 1..len(min_copies) <= 8 (fx_fasta_tandem_repeats): min_copies[p - 1] copies at

@@ -1058,6 +1058,28 @@ class Fasta(_fxobj.FastaCore):
             return self._db.execute("SELECT chrom FROM seq WHERE ID=?", (int(r) + 1,)).fetchone()[0]
         return annot.runs_blob(blob, kind, min_len, sel, max_runs, letters, name_of)
 
+    def low_complexity(self, window=64, threshold=20, min_len=1, ids=None, max_rows=10**8):
+        """Extension: the low-complexity intervals of the `seq` of the records by the windowed DUST triplet score ->
+        annot.ClassRuns(ids, starts, stops) ordered by (record, start), with .lengths and .write_bed(path);
+        records(mask=...) and write(mask=...) take it as it is.  Letters fold A a C c G g T t, every other letter is invalid.
+        For every letter e >= 2 of a record the window [max(0, e - window + 1), e] is scored: with c_x the valid triplets of
+        code x wholly inside it, n their number and S = sum c_x (c_x - 1) / 2, the window qualifies iff n >= 2 and
+        10 S > threshold (n - 1) -- threshold in tenths as sdust and dustmasker write it, 20 is a score of 2.0.  The rows are
+        the maximal intervals of the union of the qualifying windows (touching ones are one row), those shorter than min_len
+        dropped.  window: 4..64, or a tuple of up to 4 lengths whose rows are joined before min_len.  This is the windowed
+        form: a whole window is masked, so flanks of up to window minus about 23 letters go with a repeat at the defaults; a
+        smaller window is the finer knob.  sdust's perfect intervals are not implemented, parity with sdust / dustmasker is
+        not claimed.  Nothing joins across two records.  ids: restrict to these records.  More than max_rows: ValueError
+        with the count, nothing allocated.  On the GPU from the resident stream (csrc/fx_dust.hpp)."""
+        from . import complexity
+        complexity.check_mask(window, threshold, min_len, max_rows)
+        sel = None if ids is None else np.unique(self._ids_of(ids))
+        blob = self._search_blob()
+
+        def name_of(r):
+            return self._db.execute("SELECT chrom FROM seq WHERE ID=?", (int(r) + 1,)).fetchone()[0]
+        return complexity.mask_blob(blob, window, threshold, min_len, sel, max_rows, name_of)
+
     def tandem_repeats(self, min_copies=(12, 7, 5, 4, 4, 4), min_len=0, ids=None, max_repeats=10**8):
         """Extension: the perfect tandem repeats (microsatellites) of period 1..8 of the `seq` of the records ->
         tandem.TandemRepeats(ids, starts, stops, periods, motif_codes) ordered by record, stop, period, with .lengths, .copies,
@@ -2348,6 +2370,20 @@ class Fastq(_fxobj.FastqCore):
         from . import kmer
         k = kmer.check_k(k)
         return kmer.fastq_counts_blob(self._qc_blob(), self._rlen_host.size, k, canonical, ids, start, end)
+
+    def complexity(self, ids=None, start=None, end=None):
+        """Extension: per-read sequence complexity of s = seq[start:end] of the reads `ids`, counted on the GPU from the
+        resident stream (csrc/fx_dust.hpp) -> dict of numpy columns, one row per query; ids, start and end follow
+        kmer_counts.  length = len(s); n_triplets (int32) = the triplets of s whose three letters are A C G T (either case);
+        dust_sum (int64) = sum c (c - 1) / 2 over the counts c of the 64 triplet codes; n_diff (int32) = the positions j
+        with s[j] != s[j + 1] as bytes.  Derived on the host: dust = 10 * dust_sum / (n_triplets - 1), 0 below two triplets --
+        prinseq's scale over the whole interval, without its averaging over windows of 64: random letters score about 0.08
+        per letter (12 for a read of 150), a homopolymer 5 per letter, so prinseq's cut of 7 fits reads of up to about 64
+        letters and longer reads want a larger one -- and complexity = n_diff / (length - 1), fastp's measure (0 below two
+        letters).  fq.write(path, ids=np.nonzero(c["dust"] <= cut)[0]) is the low-complexity filter.  A bad id or an interval
+        outside its read: IndexError."""
+        from . import complexity
+        return complexity.complexity_blob(self._qc_blob(), self._rlen_host.size, ids, start, end)
 
     def kmer_table(self, k, canonical=False, ids=None, start=None, end=None, min_count=1, max_bytes=None):
         """Extension: the sparse k-mer table of seq[start:end] of the reads `ids`, 1 <= k <= 31 -> kmer.KmerTable; the

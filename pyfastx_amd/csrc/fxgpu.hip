@@ -61,6 +61,7 @@
 #include "fx_kmer_screen.hpp"
 #include "fx_sketch.hpp"
 #include "fx_fastq_dedup.hpp"
+#include "fx_dust.hpp"
 
 using namespace fx;
 
@@ -373,10 +374,10 @@ static void crc_tables(CrcTables *T) {
 }
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_ESEARCH_COUNT, K_ESEARCH_EMIT, K_ESEARCH_BEST, K_ESEARCH_START, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_FA_FORMAT_SIZE, K_FA_FORMAT_SCAN, K_FA_FORMAT_EMIT, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_ESEARCH_COUNT, K_ESEARCH_EMIT, K_ESEARCH_BEST, K_ESEARCH_START, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_FA_FORMAT_SIZE, K_FA_FORMAT_SCAN, K_FA_FORMAT_EMIT, K_DUST_COUNT, K_DUST_SCAN, K_DUST_EMIT, K_FQ_COMPLEXITY, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_esearch_count", "k_esearch_emit", "k_esearch_best", "k_esearch_start", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce", "k_fa_format_size", "k_fa_format_scan", "k_fa_format_emit"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_esearch_count", "k_esearch_emit", "k_esearch_best", "k_esearch_start", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce", "k_fa_format_size", "k_fa_format_scan", "k_fa_format_emit", "k_dust_count", "k_dust_scan", "k_dust_emit", "k_fq_complexity"};
 
 struct Prof {
     bool on = false;
@@ -4725,6 +4726,37 @@ extern "C" int fx_fasta_orfs(fx_handle *h, uint64_t stop_mask, uint64_t start_ma
         rec, start, stop, IvCol{1, (void **)frame}, IvCol{1, (void **)flags}, n, n_total);
 }
 
+// ------------------------------------------------------------------ low-complexity sequence (fx_dust.hpp)
+extern "C" int fx_fasta_low_complexity(fx_handle *h, int32_t window, int32_t threshold, int64_t min_len, const int64_t *ids, int64_t n_ids,
+                                       int64_t max_rows, int64_t **rec, int64_t **start, int64_t **stop, int64_t *n, int64_t *n_total) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !rec || !start || !stop || !n || !n_total) return fail(FX_EINVAL, "null argument");
+    *rec = *start = *stop = nullptr; *n = *n_total = 0;
+    if (window < DUST_MIN_W || window > DUST_MAX_W) return fail(FX_EINVAL, "window %d outside %d..%d", (int)window, DUST_MIN_W, DUST_MAX_W);
+    if (threshold < 1 || threshold > DUST_MAX_T) return fail(FX_EINVAL, "threshold %d outside 1..%d", (int)threshold, DUST_MAX_T);
+    if (min_len < 1) return fail(FX_EINVAL, "min_len %lld must be at least 1", (long long)min_len);
+    if (max_rows < 0) return fail(FX_EINVAL, "max_rows must not be negative");
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(FX_EINVAL, "null id array");
+    const DustArg A{window, threshold, min_len};
+    return run_intervals(
+        h, ids, n_ids, max_rows, K_DUST_SCAN, "intervals", "low-complexity intervals", 2, 1, 1,
+        [&](Staged &st, IvRuns &R) {                       // words: the packed word of the class runs (its low bits the closes), then `since`
+            int rc;
+            FX_LAUNCH(h, K_DUST_COUNT, k_dust_count, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, R.words, R.closes);
+            if ((rc = sscan<1>(h, st, K_DUST_SCAN, AnLdOutside{R.words}, R.P.n_runs, R.NZ, R.d_tot))) return rc;
+            FX_LAUNCH(h, K_DUST_SCAN, k_an_runs_list, dim3(R.grid), dim3(BLOCK), (const uint32_t *)R.words, (const int64_t *)R.NZ, R.P.n_runs, R.list);
+            FX_LAUNCH(h, K_DUST_SCAN, k_dust_close, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (const int64_t *)R.NZ, (const int64_t *)R.list,
+                      (const uint32_t *)R.closes, R.words);
+            return sscan<1>(h, st, K_DUST_SCAN, AnLdCloses{R.words}, R.P.n_runs, R.O, R.d_tot);
+        },
+        [&](IvRuns &R, int64_t *o_rec, int64_t *o_start, int64_t *o_stop, void *, void *) {
+            FX_LAUNCH(h, K_DUST_EMIT, k_dust_emit, dim3(R.grid), dim3(BLOCK), R.P, R.X, A, (const uint32_t *)R.words, (const int64_t *)R.NZ,
+                      (const int64_t *)R.list, (const int64_t *)R.O, o_rec, o_start, o_stop);
+        },
+        rec, start, stop, IvCol{0, nullptr}, IvCol{0, nullptr}, n, n_total);
+}
+
 extern "C" int fx_fasta_translate_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
                                         const uint8_t *strand, const uint8_t *aa64, uint8_t unknown, uint8_t **dst, int64_t **dst_off,
                                         int64_t *first_bad) {
@@ -5911,6 +5943,40 @@ extern "C" int fx_fastq_kmer_screen(fx_handle *h, const fx_kmer_set *set, const 
     } else if (!out.alloc(0, 8)) return fail(FX_ENOMEM, "pinned block");
     out.release(pos);
     *n_pos = total;
+    return FX_OK;
+}
+
+extern "C" int fx_fastq_complexity(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end, int64_t **length,
+                                   int32_t **n_triplets, int64_t **dust_sum, int32_t **n_diff, int64_t *n_rows, int64_t *first_bad) {
+    int rc = an_device();
+    if (rc) return rc;
+    if (!h || !length || !n_triplets || !dust_sum || !n_diff || !n_rows || !first_bad) return fail(FX_EINVAL, "null argument");
+    if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
+    *length = *dust_sum = nullptr; *n_triplets = *n_diff = nullptr; *n_rows = 0; *first_bad = -1;
+    FqBatch b{ids, n_ids, start, end};
+    if ((rc = b.enter(h)) || (rc = b.check(h, first_bad))) return rc;
+    const int64_t n = b.n, m = std::max<int64_t>(n, 1);
+    PinnedOut<4> out(h);
+    auto pinned = [&] { return out.alloc(0, m * 8) && out.alloc(1, m * 4) && out.alloc(2, m * 8) && out.alloc(3, m * 4); };
+    if (n > 0) {
+        Staged st(h);
+        if ((rc = b.up(h, st, first_bad))) return rc;
+        ScratchBuf<int64_t> dev;                           // length, dust_sum, then the two int32 columns
+        if ((rc = dev.alloc(h->device, 3 * n, h->stream))) return rc;
+        const DustCols cols{dev.p, dev.p + n, (int32_t *)(dev.p + 2 * n), (int32_t *)(dev.p + 2 * n) + n};
+        const FqView &v = b.v;
+        const int lpr = std::max(b.q.lpr, 2);              // (at one lane per read the tables of a workgroup would fill 64 KiB)
+        const size_t lds = (size_t)lane_groups(lpr) * 64 * sizeof(uint32_t);
+        FX_LAUNCH_LDS(h, K_FQ_COMPLEXITY, k_fq_complexity, dim3(lane_group_grid<k_fq_complexity>(h, n, lpr)), dim3(BLOCK), lds, v.data, v.base, v.n, v.rlen,
+                      v.soff, b.Q.ids, n, b.Q.start, b.Q.end, lpr, cols);
+        HIPCHK(hipGetLastError());
+        if (!pinned()) return fail(FX_ENOMEM, "pinned blocks for %lld rows", (long long)n);
+        if ((rc = home(h, "complexity", {{out.p[0], cols.length, n * 8}, {out.p[1], cols.n_triplets, n * 4}, {out.p[2], cols.dust_sum, n * 8},
+                                         {out.p[3], cols.n_diff, n * 4}})))
+            return rc;
+    } else if (!pinned()) return fail(FX_ENOMEM, "pinned blocks");
+    out.release(length, n_triplets, dust_sum, n_diff);
+    *n_rows = n;
     return FX_OK;
 }
 
