@@ -1035,6 +1035,43 @@ int fx_fasta_format_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const 
                           uint8_t **dst, int64_t **dst_off, int64_t *n_kept, int64_t *n_bases, int64_t *first_bad);
 int fx_fasta_format_tile(void);
 
+/* ------------------------------------------------------------------ BGZF written on the device (extension)
+ * The reference writes nothing compressed.  A deflate encoder on the device (pyfastx_amd/csrc/fx_deflate.hpp) turns a buffer
+ * into BGZF members, so that the record writers hand the host compressed bytes only.
+ *
+ * Members.  Member m carries the input bytes [m * 65280, min(n, (m + 1) * 65280)) and refers to nothing outside itself; n = 0
+ *   gives no member.  A member is 18 bytes of header (1f 8b 08 04, mtime 0, XFL 0, OS ff, XLEN 6, "BC", SLEN 2, BSIZE - 1), one
+ *   deflate stream of one block, the CRC-32 of the payload and ISIZE.  No EOF member is written: that is the file writer's.
+ * level  0: a stored block per member.  1: a dynamic-Huffman block of literals.  2: matches (lengths 4..258, distances
+ *   1..32768, inside the member) and a dynamic-Huffman block.  At 1 and 2 a member whose coded form would not be smaller is
+ *   stored, so no member exceeds its payload + 31 bytes.  The same input and level give the same bytes on every call.
+ * fx_bgzf_compress: n bytes of a host buffer -> *dst (*dst_bytes bytes) and *member_off (*n_members + 1 offsets of the members
+ *   in *dst; the uncompressed offset of member m is m * 65280), both pinned blocks of fx_pinned_alloc that belong to the caller
+ *   (fx_pinned_free), never NULL after FX_OK.
+ * fx_fastq_format_bgzf_alloc, fx_fasta_format_bgzf_alloc, fx_fastq_pair_merge_bgzf_alloc: the records of their siblings without
+ *   the suffix, compressed before they leave the device.  Arguments, *dst_off (offsets in the UNCOMPRESSED stream), the counts,
+ *   *first_bad and every error are the sibling's; *zdst (*zbytes bytes) and *member_off (*n_members + 1) are as above.
+ * Errors: a level outside 0..2, a null output pointer, n < 0: FX_EINVAL, nothing allocated; no device: FX_EDEVICE (there is no
+ *   CPU path). */
+int fx_bgzf_compress(const uint8_t *src, int64_t n, int level, int device, uint8_t **dst, int64_t *dst_bytes,
+                     int64_t **member_off, int64_t *n_members);
+int fx_fastq_format_bgzf_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                               int64_t min_len, int level, uint8_t **zdst, int64_t **member_off, int64_t **dst_off,
+                               int64_t *n_rows, int64_t *n_kept, int64_t *first_bad, int64_t *zbytes, int64_t *n_members);
+int fx_fasta_format_bgzf_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop,
+                               int flags, const uint8_t *flags_per_query, int64_t width,
+                               const uint8_t *hdr, const int64_t *hdr_off,
+                               int64_t n_mask, const int64_t *mask_id, const int64_t *mask_start, const int64_t *mask_stop,
+                               int mask_mode, int mask_byte, int64_t min_len, int level,
+                               uint8_t **zdst, int64_t **member_off, int64_t **dst_off, int64_t *n_kept, int64_t *n_bases,
+                               int64_t *first_bad, int64_t *zbytes, int64_t *n_members);
+int fx_fastq_pair_merge_bgzf_alloc(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, const int32_t *diag,
+                                   int64_t min_len, int level, uint8_t **zdst, int64_t **member_off, int64_t **dst_off,
+                                   int64_t *n_rows, int64_t *n_merged, int64_t *first_bad, int64_t *zbytes, int64_t *n_members);
+/* The code lengths (at most `limit`, 1..15) and canonical codes, bit-reversed, that the encoder gives nsym (1..288) symbol counts;
+ * host only, for tests: the same routine the kernel runs. */
+int fx_deflate_code_lengths(const uint32_t *freq, int nsym, int limit, uint8_t *lens, uint16_t *codes);
+
 /* ------------------------------------------------------------------ Fastx
  * Replaces kseq_read (kseq.c:138-179) as pyfastx_fastx_next drives it (fastx.c:124-130): index-free iteration over a
  * file with kseq's own record rules -- FASTA and FASTQ records mixed, sequence / quality over any number of lines,

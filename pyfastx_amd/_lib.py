@@ -133,6 +133,12 @@ PROTOTYPES = {
     "fx_fastq_demux": (i32, [vp, vp, i64, i32, vp, vp, vp, vp, vp, i32, i32, i32] + [pvp] * 6 + [pi64, pi64]),
     "fx_fastq_pair_overlap": (i32, [vp, vp, vp, i64, i32, i32, i64, i64, pvp, pvp, pvp, pvp, pvp, pi64, pi64]),
     "fx_fastq_pair_merge_alloc": (i32, [vp, vp, vp, i64, vp, i64, pvp, pvp, pi64, pi64, pi64]),
+    "fx_bgzf_compress": (i32, [vp, i64, i32, i32, pvp, pi64, pvp, pi64]),
+    "fx_fastq_format_bgzf_alloc": (i32, [vp, vp, i64, vp, vp, i64, i32, pvp, pvp, pvp, pi64, pi64, pi64, pi64, pi64]),
+    "fx_fasta_format_bgzf_alloc": (i32, [vp, i64, vp, vp, vp, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, i64, i32, pvp, pvp, pvp, pi64, pi64, pi64,
+                                         pi64, pi64]),
+    "fx_fastq_pair_merge_bgzf_alloc": (i32, [vp, vp, vp, i64, vp, i64, i32, pvp, pvp, pvp, pi64, pi64, pi64, pi64, pi64]),
+    "fx_deflate_code_lengths": (i32, [vp, i32, i32, vp, vp]),
     "fx_fasta_kmers": (i32, [vp, i32, i32, vp, i64, i32, pvp, pi64, pi64]),
     "fx_fastq_kmers": (i32, [vp, i32, i32, vp, i64, vp, vp, pvp, pi64]),
     "fx_fasta_kmer_table": (i32, [vp, i32, i32, vp, i64, i64, i64] + [pvp] * 2 + [pi64] * 4),
@@ -498,6 +504,28 @@ def _ragged(dst, offs, n):
     int64 offsets[n + 1]), pinned."""
     o = pinned_array(offs, n + 2, np.int64)[:n + 1]
     return pinned_array(dst, max(int(o[n]), 1))[:int(o[n])], o
+
+
+def _bgzf_blocks(zdst, moff, zbytes, members):
+    """The block pair of a _bgzf entry (addresses) -> (uint8 stream cut to zbytes, int64 member offsets[members + 1]), pinned."""
+    return pinned_array(zdst, max(zbytes, 1))[:zbytes], pinned_array(moff, members + 1, np.int64)
+
+
+def bgzf_compress(data, level=2, device=0):
+    """The bytes of `data` as BGZF members of 65280 bytes (fx_bgzf_compress; no EOF member) -> (uint8 stream, int64 member
+    offsets[members + 1]), pinned.  A level outside 0..2 raises FxError(FX_EINVAL)."""
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    dst, moff, nb, nm = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int64(0)
+    check(lib().fx_bgzf_compress(a.ctypes.data if a.size else None, a.size, int(level), int(device), C.byref(dst), C.byref(nb), C.byref(moff), C.byref(nm)))
+    return _bgzf_blocks(dst.value, moff.value, int(nb.value), int(nm.value))
+
+
+def deflate_code_lengths(freq, limit=15):
+    """The code lengths and the bit-reversed canonical codes the encoder gives these symbol counts (fx_deflate_code_lengths; host only)."""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    lens, codes = np.zeros(f.size, dtype=np.uint8), np.zeros(f.size, dtype=np.uint16)
+    check(lib().fx_deflate_code_lengths(f.ctypes.data, f.size, int(limit), lens.ctypes.data, codes.ctypes.data))
+    return lens, codes
 
 
 def too_many(e, noun, arg, limit):
@@ -1209,8 +1237,8 @@ class Blob:
         return pinned_array(dst.value, max(int(o[n]), 1))[:int(o[n])], o
 
     def fasta_format_alloc(self, n, seq_id=None, start=None, stop=None, flags=0, flags_per_query=None, width=60, hdr=None,
-                           hdr_off=None, mask=None, mask_mode=0, mask_byte=78, min_len=0):
-        """FASTA records of n queries (fx_fasta_format_alloc): seq_id None: the records 0..n-1; start = stop = None: whole
+                           hdr_off=None, mask=None, mask_mode=0, mask_byte=78, min_len=0, level=None):
+        """FASTA records of n queries (fx_fasta_format_alloc; level 0..2: fx_fasta_format_bgzf_alloc, see below): seq_id None: the records 0..n-1; start = stop = None: whole
         records; hdr / hdr_off: the headers' bytes and their n + 1 offsets, or None for the records' own; mask: None or
         (ids, starts, stops) sorted and disjoint -> (uint8 buffer, int64 offsets[n + 1], records kept, their letters), pinned.
         A bad query raises FxError(FX_ERANGE), a bad mask row FxError(FX_EINVAL), each with .first_bad."""
@@ -1230,6 +1258,10 @@ class Blob:
             raise ValueError("hdr_off must hold n + 1 offsets")
         head = (self._h, int(n), _ptr(seq_id), _ptr(start), _ptr(stop), int(flags), _ptr(fpq), int(width), _ptr(hdr), _ptr(hdr_off),
                 n_mask, _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), int(mask_mode), int(mask_byte), int(min_len))
+        if level is not None:                                  # -> (stream, member offsets, record offsets in the uncompressed stream, kept, letters)
+            (zdst, moff, offs), (kept, bases, _, zb, nm) = _call(lib().fx_fasta_format_bgzf_alloc, head + (int(level),), (RAW, RAW, RAW),
+                                                                 counters=(0, 0, -1, 0, 0), err=("first_bad", 2))
+            return _bgzf_blocks(zdst, moff, zb, nm) + (pinned_array(offs, int(n) + 1, np.int64), kept, bases)
         (dst, offs), (kept, bases, _) = _call(lib().fx_fasta_format_alloc, head, (RAW, RAW), counters=(0, 0, -1), err=("first_bad", 2))
         return _ragged(dst, offs, int(n)) + (kept, bases)
 
@@ -1443,10 +1475,15 @@ class Blob:
                 -1 if tail_qual is None else int(tail_qual))
         return _call(lib().fx_fastq_trim, head, [np.int64] * 2, counters=(0, -1), err=("first_bad", 1))[0]
 
-    def fastq_format_alloc(self, ids=None, start=None, end=None, min_len=0):
-        """Four-line records of the queries cut to [start, end) (fx_fastq_format_alloc; start = end = None: whole reads) ->
+    def fastq_format_alloc(self, ids=None, start=None, end=None, min_len=0, level=None):
+        """Four-line records of the queries cut to [start, end) (fx_fastq_format_alloc; level 0..2: fx_fastq_format_bgzf_alloc,
+        see below; start = end = None: whole reads) ->
         (uint8 buffer, int64 offsets[n + 1], records kept), pinned.  A bad id or interval raises FxError(FX_ERANGE) with
         .first_bad."""
+        if level is not None:                                  # -> (stream, member offsets, record offsets in the uncompressed stream, kept)
+            (zdst, moff, offs), (n, kept, _, zb, nm) = _call(lib().fx_fastq_format_bgzf_alloc, (self._h, *self._fastq_queries(ids, start, end), int(min_len), int(level)),
+                                                             (RAW, RAW, RAW), counters=(0, 0, -1, 0, 0), err=("first_bad", 2))
+            return _bgzf_blocks(zdst, moff, zb, nm) + (pinned_array(offs, n + 1, np.int64), kept)
         (dst, offs), (n, kept, _) = _call(lib().fx_fastq_format_alloc, (self._h, *self._fastq_queries(ids, start, end), int(min_len)),
                                           (RAW, RAW), counters=(0, 0, -1), err=("first_bad", 2))
         return _ragged(dst, offs, n) + (kept,)
@@ -1479,11 +1516,16 @@ class Blob:
                         [np.int32] * 3 + [np.int64] * 2, counters=(0, -1), err=("first_bad", 1))
         return dict(zip(("diag", "overlap", "mismatches", "end1", "end2"), cols))
 
-    def fastq_pair_merge_alloc(self, mate, diag, ids=None, min_len=0):
-        """The merged records of the pairs (fx_fastq_pair_merge_alloc; diag: what fastq_pair_overlap returned for the same
+    def fastq_pair_merge_alloc(self, mate, diag, ids=None, min_len=0, level=None):
+        """The merged records of the pairs (fx_fastq_pair_merge_alloc; level 0..2: fx_fastq_pair_merge_bgzf_alloc, see below; diag: what fastq_pair_overlap returned for the same
         ids) -> (uint8 buffer, int64 offsets[n + 1], records merged), pinned.  A bad id or diagonal raises
         FxError(FX_ERANGE) with .first_bad."""
         diag = np.ascontiguousarray(diag, dtype=np.int32)
+        if level is not None:                                  # -> (stream, member offsets, record offsets in the uncompressed stream, merged)
+            (zdst, moff, offs), (n, merged, _, zb, nm) = _call(lib().fx_fastq_pair_merge_bgzf_alloc,
+                                                               (self._h, mate._h, *_sel(ids), diag if diag.size else None, int(min_len), int(level)),
+                                                               (RAW, RAW, RAW), counters=(0, 0, -1, 0, 0), err=("first_bad", 2))
+            return _bgzf_blocks(zdst, moff, zb, nm) + (pinned_array(offs, n + 1, np.int64), merged)
         (dst, offs), (n, merged, _) = _call(lib().fx_fastq_pair_merge_alloc, (self._h, mate._h, *_sel(ids), diag if diag.size else None, int(min_len)),
                                             (RAW, RAW), counters=(0, 0, -1), err=("first_bad", 2))
         return _ragged(dst, offs, n) + (merged,)

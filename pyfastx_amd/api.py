@@ -1273,8 +1273,9 @@ class Fasta(_fxobj.FastaCore):
         buf, offs, _ = self._st.blob.fetch_ranges(off, ln, ln, flags=_F_RAW)
         return (buf if buf.size else np.zeros(1, dtype=np.uint8)), np.ascontiguousarray(offs, dtype=np.int64)
 
-    def _records_call(self, q, lo, hi):
-        """Queries [lo, hi) of a plan through fx_fasta_format_alloc -> (buffer, offsets, records kept, their letters)."""
+    def _records_call(self, q, lo, hi, level=None):
+        """Queries [lo, hi) of a plan through fx_fasta_format_alloc -> (buffer, offsets, records kept, their letters); with a
+        BGZF level (bgzf.level_of): (stream, member offsets, offsets, records kept, their letters)."""
         from . import fasta_out as fo
         whole = lo == 0 and hi == q["n"]
         cut = (lambda a: a if a is None or whole else a[lo:hi])
@@ -1295,7 +1296,7 @@ class Fasta(_fxobj.FastaCore):
         try:
             return q["blob"].fasta_format_alloc(hi - lo, ids, cut(q["starts"]), cut(q["stops"]), flags=q["flags"], flags_per_query=cut(q["fpq"]),
                                                 width=q["width"], hdr=hdr, hdr_off=hdr_off, mask=mask, mask_mode=q["mode"], mask_byte=q["byte"],
-                                                min_len=q["min_len"])
+                                                min_len=q["min_len"], **({} if level is None else {"level": level}))
         except _lib.FxError as e:
             err = fo.bad_query(e, ids, self._seq_counts, lo)
             raise (_fx_to_py(e) if err is e else err)
@@ -1318,11 +1319,15 @@ class Fasta(_fxobj.FastaCore):
         return buf, offs
 
     def write(self, path, names_or_ids=None, starts=None, stops=None, strand=None, width=60, mask=None, mask_mode="soft", mask_char="N",
-              uppercase=False, headers="auto", min_len=0, batch_bytes=1 << 30):
+              uppercase=False, headers="auto", min_len=0, batch_bytes=1 << 30, compress=None):
         """Extension: the records of `records` written to the plain file `path`, in batches of consecutive queries whose
         size bound fits batch_bytes of pinned memory (a single larger query goes alone) -> {"records": records written,
-        "bases": their letters, "dropped": queries that fell below min_len}."""
-        from . import fasta_out as fo
+        "bases": their letters, "dropped": queries that fell below min_len}.  compress: None or False: plain text; True (level
+        2) or a level 0, 1, 2: a BGZF file, compressed on the GPU (csrc/fx_deflate.hpp) so that only compressed bytes come
+        to the host -- every batch its own members (its last may be short), the EOF member once at the end; the result
+        gains "compressed_bytes" (the file's size) and "members" (the EOF member included).  Anything else: ValueError."""
+        from . import bgzf, fasta_out as fo
+        level = bgzf.level_of(compress)
         q = self._records_plan(names_or_ids, starts, stops, strand, width, mask, mask_mode, mask_char, uppercase, headers, min_len)
         n, ids = q["n"], q["ids"]
         slen = np.asarray(self._table()["slen"], dtype=np.int64)
@@ -1347,12 +1352,18 @@ class Fasta(_fxobj.FastaCore):
         fo._int(batch_bytes, "batch_bytes", 1)
         kept = bases = 0
         with open(path, "wb") as f:
+            z = None if level is None else bgzf.Tally(f)
             for lo, hi in fo.batches(bound, batch_bytes):
-                buf, _, k, b = self._records_call(q, lo, hi)
-                f.write(memoryview(buf))
+                if z is None:
+                    buf, _, k, b = self._records_call(q, lo, hi)
+                    f.write(memoryview(buf))
+                else:
+                    stream, moff, _, k, b = self._records_call(q, lo, hi, level)
+                    z.add(stream, moff)
                 kept += k
                 bases += b
-        return {"records": int(kept), "bases": int(bases), "dropped": int(n - kept)}
+            tail = {} if z is None else z.finish()
+        return {"records": int(kept), "bases": int(bases), "dropped": int(n - kept), **tail}
 
 
 class FastaKeys:
@@ -2457,11 +2468,15 @@ class Fastq(_fxobj.FastqCore):
         buf, offs, _ = _trim.records_blob(self._qc_blob(), self._rlen_host.size, ids, start, end, min_len)
         return buf, offs
 
-    def write(self, path, ids=None, start=None, end=None, min_len=0, batch_bytes=1 << 30):
+    def write(self, path, ids=None, start=None, end=None, min_len=0, batch_bytes=1 << 30, compress=None):
         """Extension: the records of `records` written to the plain file `path`, in batches of consecutive queries whose
         upper bound fits batch_bytes of pinned memory -> {"reads": records written, "bases": their bases, "dropped": queries
-        that fell below min_len}."""
-        from . import trim as _trim
+        that fell below min_len}.  compress: None or False: plain text; True (level 2) or a level 0, 1, 2: a BGZF file,
+        compressed on the GPU (csrc/fx_deflate.hpp) so that only compressed bytes come to the host -- every batch its own
+        members (its last may be short), the EOF member once at the end; the result gains "compressed_bytes" (the file's
+        size) and "members" (the EOF member included).  Anything else: ValueError."""
+        from . import bgzf, trim as _trim
+        level = bgzf.level_of(compress)
         blob = self._qc_blob()
         n_reads = self._rlen_host.size
         ids = _trim.check_ids(ids, n_reads)
@@ -2469,16 +2484,22 @@ class Fastq(_fxobj.FastqCore):
         start, end = _trim.check_intervals(start, end, n)
         kept = bases = 0
         with open(path, "wb") as f:
+            z = None if level is None else bgzf.Tally(f)
             for lo, hi in _trim.batches(self._tab_host, ids, n_reads, batch_bytes):
                 q = np.arange(lo, hi, dtype=np.int64) if ids is None else ids[lo:hi]
                 a, b = (None, None) if start is None else (start[lo:hi], end[lo:hi])
-                buf, offs, k = _trim.records_blob(blob, n_reads, q, a, b, min_len)
-                f.write(memoryview(buf))
+                if z is None:
+                    buf, offs, k = _trim.records_blob(blob, n_reads, q, a, b, min_len)
+                    f.write(memoryview(buf))
+                else:
+                    stream, moff, offs, k = _trim.records_blob(blob, n_reads, q, a, b, min_len, level)
+                    z.add(stream, moff)
                 kept += k
                 there = np.diff(offs) > 0
                 ln = self._rlen_host[q].astype(np.int64) if a is None else b - a
                 bases += int(ln[there].sum())
-        return {"reads": int(kept), "bases": int(bases), "dropped": int(n - kept)}
+            tail = {} if z is None else z.finish()
+        return {"reads": int(kept), "bases": int(bases), "dropped": int(n - kept), **tail}
 
     def demux(self, samples, where="header", offset=0, mismatches=1, margin=1, revcomp=False, ids=None):
         """Extension: barcode demultiplexing on the GPU from the resident stream (csrc/fx_fastq_demux.hpp) -> demux.Demux, one
@@ -2496,12 +2517,13 @@ class Fastq(_fxobj.FastqCore):
         args = _demux.demux_args(samples, where, offset, mismatches, margin, revcomp)
         return _demux.demux_blob(self._qc_blob(), self._rlen_host, ids, args)
 
-    def demux_write(self, dm, pattern, unassigned=None, ambiguous=None, cut=False, min_len=0, batch_bytes=1 << 30):
+    def demux_write(self, dm, pattern, unassigned=None, ambiguous=None, cut=False, min_len=0, batch_bytes=1 << 30, compress=None):
         """Extension: one file per sample of `dm` (what demux returned for this file) through write: `pattern` holds
         "{sample}"; unassigned / ambiguous: a path for those reads, or None to drop them; cut=True writes the reads without
-        their inline barcodes (dm.intervals()).  A bin without reads gets no file -> {name: (path, records written)}, the
-        two extra bins under "unassigned" and "ambiguous"."""
-        from . import demux as _demux
+        their inline barcodes (dm.intervals()); compress: as write takes it.  A bin without reads gets no file -> {name:
+        (path, records written)}, the two extra bins under "unassigned" and "ambiguous"."""
+        from . import bgzf, demux as _demux
+        level = bgzf.level_of(compress)
         if not isinstance(dm, _demux.Demux) or (dm._ids is None and len(dm) != self._rlen_host.size):
             raise ValueError("dm must be what demux returned for this file")
         start, end = dm.intervals() if cut else (None, None)
@@ -2512,7 +2534,7 @@ class Fastq(_fxobj.FastqCore):
                 continue
             ids = pos if dm._ids is None else dm._ids[pos]
             r = self.write(path, ids=ids, start=None if start is None else start[pos], end=None if end is None else end[pos],
-                           min_len=min_len, batch_bytes=batch_bytes)
+                           min_len=min_len, batch_bytes=batch_bytes, **({} if level is None else {"compress": level}))
             out[key] = (path, r["reads"])
         return out
 

@@ -662,19 +662,9 @@ struct CrcTables {
 __device__ __forceinline__ uint32_t crc_shift(const uint32_t (*t)[256], uint32_t v) {
     return t[0][v & 0xFFu] ^ t[1][(v >> 8) & 0xFFu] ^ t[2][(v >> 16) & 0xFFu] ^ t[3][v >> 24];
 }
-__global__ __launch_bounds__(256) void k_bgzf_crc(const uint8_t *__restrict__ data, const int64_t *__restrict__ uoff,
-                                                 const int32_t *__restrict__ isize, const uint8_t *__restrict__ cbuf,
-                                                 const int64_t *__restrict__ cdata_off, const int32_t *__restrict__ cdata_len,
-                                                 int64_t nmem, const CrcTables *__restrict__ T, int32_t *__restrict__ status) {
-    __shared__ uint32_t tab[4][256], sh[CRC_NSH][4][256];
-    for (int i = threadIdx.x; i < 4 * 256; i += 256) (&tab[0][0])[i] = (&T->crc[0][0])[i];
-    for (int i = threadIdx.x; i < CRC_NSH * 4 * 256; i += 256) (&sh[0][0][0])[i] = (&T->sh[0][0][0])[i];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int64_t m = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-    if (m >= nmem) return;
-    const int64_t n = isize[m];
-    const uint8_t *p = data + uoff[m];
+// The CRC-32 of the n bytes at p, by one wave (every lane returns it); tab, sh: T's byte and shift tables in LDS.
+__device__ __forceinline__ uint32_t crc_member(const uint8_t *__restrict__ p, int64_t n, const uint32_t (*tab)[256], const uint32_t (*sh)[4][256],
+                                               const CrcTables *__restrict__ T, int lane) {
     const int64_t nrows = (n + CRC_ROW - 1) / CRC_ROW;
     uint32_t acc = 0;                                        // crc_0 of the rows so far (wave-uniform)
     for (int64_t r = 0; r < nrows; ++r) {
@@ -704,11 +694,25 @@ __global__ __launch_bounds__(256) void k_bgzf_crc(const uint8_t *__restrict__ da
         }
         acc = crc_shift(sh[6], acc) ^ c;
     }
-    if (lane == 0 && status[m] == INFL_OK) {
-        uint32_t init = 0xFFFFFFFFu;                         // shift_n(~0): n in binary, one stored matrix per set bit
-        for (int j = 0; j < 17; ++j)
-            if ((n >> j) & 1) { uint32_t v = 0; for (int b = 0; b < 32; ++b) v ^= ((init >> b) & 1u) ? T->pow2[j][b] : 0u; init = v; }
-        const uint32_t got = n ? ~(acc ^ init) : 0u;
+    uint32_t init = 0xFFFFFFFFu;                             // shift_n(~0): n in binary, one stored matrix per set bit
+    for (int j = 0; j < 17; ++j)
+        if ((n >> j) & 1) { uint32_t v = 0; for (int b = 0; b < 32; ++b) v ^= ((init >> b) & 1u) ? T->pow2[j][b] : 0u; init = v; }
+    return n ? ~(acc ^ init) : 0u;
+}
+__global__ __launch_bounds__(256) void k_bgzf_crc(const uint8_t *__restrict__ data, const int64_t *__restrict__ uoff,
+                                                 const int32_t *__restrict__ isize, const uint8_t *__restrict__ cbuf,
+                                                 const int64_t *__restrict__ cdata_off, const int32_t *__restrict__ cdata_len,
+                                                 int64_t nmem, const CrcTables *__restrict__ T, int32_t *__restrict__ status) {
+    __shared__ uint32_t tab[4][256], sh[CRC_NSH][4][256];
+    for (int i = threadIdx.x; i < 4 * 256; i += 256) (&tab[0][0])[i] = (&T->crc[0][0])[i];
+    for (int i = threadIdx.x; i < CRC_NSH * 4 * 256; i += 256) (&sh[0][0][0])[i] = (&T->sh[0][0][0])[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t m = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    if (m >= nmem) return;
+    if (status[m] != INFL_OK) return;                        // (wave-uniform)
+    const uint32_t got = crc_member(data + uoff[m], isize[m], tab, sh, T, lane);
+    if (lane == 0) {
         const uint8_t *t = cbuf + cdata_off[m] + cdata_len[m];
         const uint32_t want = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
         if (want != got) status[m] = INFL_ECRC;

@@ -62,6 +62,7 @@
 #include "fx_sketch.hpp"
 #include "fx_fastq_dedup.hpp"
 #include "fx_dust.hpp"
+#include "fx_deflate.hpp"
 
 using namespace fx;
 
@@ -372,12 +373,16 @@ static void crc_tables(CrcTables *T) {
         for (int byte = 0; byte < 4; ++byte)
             for (uint32_t v = 0; v < 256; ++v) T->sh[k][byte][v] = times(T->pow2[CRC_SH0 + k], v << (8 * byte));
 }
+static const CrcTables *crc_tables_host() {                  // made once (k_bgzf_crc, k_bgzf_crc_put)
+    static const CrcTables *tabs = [] { CrcTables *t = new CrcTables; crc_tables(t); return t; }();
+    return tabs;
+}
 
 enum KernelId { K_SPAN_SCAN = 0, K_GRAN_REDUCE, K_GRAN_PREFIX, K_HDR_REC, K_GRAN_LINES, K_GRAN_EXACT, K_FASTA_FINALIZE, K_FETCH,
-                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_ESEARCH_COUNT, K_ESEARCH_EMIT, K_ESEARCH_BEST, K_ESEARCH_START, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_FA_FORMAT_SIZE, K_FA_FORMAT_SCAN, K_FA_FORMAT_EMIT, K_DUST_COUNT, K_DUST_SCAN, K_DUST_EMIT, K_FQ_COMPLEXITY, K_NKERN };
+                K_FASTA_COMP, K_FASTA_COMP_EDGE, K_FASTA_COMP_SMALL, K_FASTQ_LINES, K_FASTQ_ROWS, K_FASTQ_EMIT, K_FASTQ_STATS, K_FASTQ_COMP, K_FASTQ_FETCH, K_BGZF_INFLATE, K_BGZF_COPY, K_BGZF_CRC, K_SCAN_COMP, K_COMP_ATTRIBUTE, K_BGZF_SERIAL, K_FETCH_REST, K_KQ_LINES, K_KQ_PREFIX, K_KQ_WALK, K_KQ_GATHER, K_SEARCH_COUNT, K_SEARCH_SCAN, K_SEARCH_EMIT, K_FQ_READ_STATS, K_FQ_SELECT, K_FQ_SELECT_SCAN, K_FQ_SELECT_EMIT, K_FQ_CYCLE_HIST, K_FQ_TRIM, K_FQ_FORMAT_COUNT, K_FQ_FORMAT_SCAN, K_FQ_FORMAT_EMIT, K_KMER_FASTA, K_KMER_SCAN, K_KMER_FIX, K_KMER_FASTQ, K_KT_KEPT, K_KT_HIST, K_KT_EMIT, K_KT_SORT, K_KT_REDUCE, K_KT_FOLD, K_KS_INSERT, K_KS_CONTAINS, K_KS_FASTQ, K_KS_FASTA, K_KS_SCREEN, K_DD_HASH, K_DD_SORT, K_DD_VERIFY, K_DD_SELECT, K_ASEARCH_COUNT, K_ASEARCH_EMIT, K_ESEARCH_COUNT, K_ESEARCH_EMIT, K_ESEARCH_BEST, K_ESEARCH_START, K_FP_OVERLAP, K_FP_MERGE_COUNT, K_FP_MERGE_SCAN, K_FP_MERGE_EMIT, K_AN_RANK, K_AN_SCAN, K_AN_REGION, K_AN_RUNS_COUNT, K_AN_RUNS_SCAN, K_AN_RUNS_EMIT, K_TD_COUNT, K_TD_SCAN, K_TD_CLOSE, K_TD_EMIT, K_ORF_COUNT, K_ORF_SCAN, K_ORF_CLOSE, K_ORF_EMIT, K_TR_TRANSLATE, K_FQ_DEMUX, K_FQ_DEMUX_GROUP, K_PWM_COUNT, K_PWM_EMIT, K_PWM_BEST, K_MZ_COUNT, K_MZ_EMIT, K_SK_COUNT, K_SK_SCAN, K_SK_EMIT, K_SK_SORT, K_SK_REDUCE, K_FA_FORMAT_SIZE, K_FA_FORMAT_SCAN, K_FA_FORMAT_EMIT, K_DUST_COUNT, K_DUST_SCAN, K_DUST_EMIT, K_FQ_COMPLEXITY, K_BGZF_STORE, K_BGZF_DEFLATE, K_BGZF_CRC_PUT, K_BGZF_SCAN, K_BGZF_PACK, K_NKERN };
 static const char *const kKernelNames[K_NKERN] = {
     "k_span_scan", "k_gran_reduce", "k_gran_prefix", "k_hdr_rec", "k_gran_lines", "k_gran_exact", "k_fasta_finalize", "k_fetch",
-    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_esearch_count", "k_esearch_emit", "k_esearch_best", "k_esearch_start", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce", "k_fa_format_size", "k_fa_format_scan", "k_fa_format_emit", "k_dust_count", "k_dust_scan", "k_dust_emit", "k_fq_complexity"};
+    "k_fasta_comp", "k_fasta_comp_edge", "k_fasta_comp_small", "k_fastq_lines", "k_fastq_rows", "k_fastq_emit", "k_fastq_stats", "k_fastq_comp", "k_fastq_fetch", "k_bgzf_decode", "k_bgzf_copy", "k_bgzf_crc", "k_scan_comp", "k_comp_attribute", "k_bgzf_decode_serial", "k_fetch_rest", "k_kq_lines", "k_kq_prefix", "k_kq_walk", "k_kq_gather", "k_search_count", "k_search_scan", "k_search_emit", "k_fq_read_stats", "k_fq_select", "k_fq_select_scan", "k_fq_select_emit", "k_fq_cycle_hist", "k_fq_trim", "k_fq_format_count", "k_fq_format_scan", "k_fq_format_emit", "k_kmer_fasta", "k_kmer_scan", "k_kmer_fix", "k_kmer_fastq", "k_kt_kept", "k_kt_hist", "k_kt_emit", "k_kt_sort", "k_kt_reduce", "k_kt_fold", "k_ks_insert", "k_ks_contains", "k_ks_fastq", "k_ks_fasta", "k_ks_screen", "k_dd_hash", "k_dd_sort", "k_dd_verify", "k_dd_select", "k_asearch_count", "k_asearch_emit", "k_esearch_count", "k_esearch_emit", "k_esearch_best", "k_esearch_start", "k_fp_overlap", "k_fp_merge_count", "k_fp_merge_scan", "k_fp_merge_emit", "k_an_rank", "k_an_scan", "k_an_region", "k_an_runs_count", "k_an_runs_scan", "k_an_runs_emit", "k_td_count", "k_td_scan", "k_td_close", "k_td_emit", "k_orf_count", "k_orf_scan", "k_orf_close", "k_orf_emit", "k_tr_translate", "k_fq_demux", "k_fq_demux_group", "k_pwm_count", "k_pwm_emit", "k_pwm_best", "k_mz_count", "k_mz_emit", "k_sk_count", "k_sk_scan", "k_sk_emit", "k_sk_sort", "k_sk_reduce", "k_fa_format_size", "k_fa_format_scan", "k_fa_format_emit", "k_dust_count", "k_dust_scan", "k_dust_emit", "k_fq_complexity", "k_bgzf_store", "k_bgzf_deflate", "k_bgzf_crc_put", "k_bgzf_scan", "k_bgzf_pack"};
 
 struct Prof {
     bool on = false;
@@ -1134,9 +1139,8 @@ static int bgzf_inflate_staged(fx_handle *h, const uint8_t *d_cp, const int64_t 
     static const bool no_crc = [] { const char *e = getenv("FX_BGZF_NO_CRC"); return e && atoi(e) != 0; }();
     ScratchBuf<CrcTables> d_crc;
     if (!no_crc) {                                           // every member against the CRC-32 of its trailer, as zlib does in gzread
-        static const CrcTables *tabs = [] { CrcTables *t = new CrcTables; crc_tables(t); return t; }();
         if ((rc = d_crc.alloc(h->device, 1, h->stream))) return rc;
-        HIPCHK(hipMemcpyAsync(d_crc.p, tabs, sizeof(CrcTables), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_crc.p, crc_tables_host(), sizeof(CrcTables), hipMemcpyHostToDevice, h->stream));
         FX_LAUNCH(h, K_BGZF_CRC, k_bgzf_crc, dim3(nblocks(nmem, 4)), dim3(256), h->d_data, d_uoff, d_isize, d_cp, d_coff, d_clen,
                   nmem, d_crc.p, d_status.p);
     }
@@ -3572,18 +3576,84 @@ static int emit_passing(fx_handle *h, Staged &st, int id_scan, int id_emit, cons
     return home(h, what, col, N);
 }
 
+// ------------------------------------------------------------------ BGZF out of a device buffer (fx_deflate.hpp)
+// Extension: the reference writes nothing compressed.
+// The n bytes at d_src as BGZF members of DFL_MEMBER bytes each, on the device: the packed stream, the members + 1 offsets of
+// the members in it, *bytes (waited for at levels 1 and 2, where only the scan of the sizes knows it).  n > 0.
+struct BgzfDev { ScratchBuf<uint8_t> stream; ScratchBuf<int64_t> moff; int64_t bytes = 0, members = 0; };
+static int bgzf_encode(fx_handle *h, Staged &st, const uint8_t *d_src, int64_t n, int level, BgzfDev *o) {
+    int rc;
+    const int64_t nm = o->members = (n + DFL_MEMBER - 1) / DFL_MEMBER;
+    ScratchBuf<CrcTables> d_crc;
+    if ((rc = o->moff.alloc(h->device, nm + 1, h->stream)) || (rc = d_crc.alloc(h->device, 1, h->stream))) return rc;
+    HIPCHK(hipMemcpyAsync(d_crc.p, crc_tables_host(), sizeof(CrcTables), hipMemcpyHostToDevice, h->stream));
+    int n_cu = 256;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
+    if (level == 0) {
+        o->bytes = n + 31 * nm;
+        if ((rc = o->stream.alloc(h->device, o->bytes, h->stream))) return rc;
+        FX_LAUNCH(h, K_BGZF_STORE, k_bgzf_store, dim3((unsigned)std::min<int64_t>(nm, 8 * (int64_t)std::max(n_cu, 1))), dim3(BLOCK), d_src, n, nm, o->stream.p, o->moff.p);
+        FX_LAUNCH(h, K_BGZF_CRC_PUT, k_bgzf_crc_put, dim3(nblocks(nm, 4)), dim3(256), d_src, n, nm, (const CrcTables *)d_crc.p, o->stream.p, (int64_t)DFL_STORED,
+                  (const int64_t *)nullptr);
+        HIPCHK(hipGetLastError());
+        return FX_OK;
+    }
+    // one workgroup per CU (its LDS holds one member's payload and tables); each has a word of scratch per position for its tokens
+    const int64_t grid = std::min<int64_t>(nm, std::max(n_cu, 1));
+    ScratchBuf<uint8_t> stage;
+    ScratchBuf<int64_t> sizes;
+    ScratchBuf<uint32_t> tok;
+    int64_t *d_tot = nullptr;
+    if ((rc = stage.alloc(h->device, nm * DFL_SLOT, h->stream)) || (rc = sizes.alloc(h->device, nm, h->stream)) ||
+        (rc = tok.alloc(h->device, grid * DFL_SLOT, h->stream)) || (rc = st.scratch<int64_t>(1, &d_tot)))
+        return rc;
+    FX_LAUNCH(h, K_BGZF_DEFLATE, k_bgzf_deflate, dim3((unsigned)grid), dim3(DFL_THREADS), d_src, n, nm, level, tok.p, stage.p, sizes.p);
+    FX_LAUNCH(h, K_BGZF_CRC_PUT, k_bgzf_crc_put, dim3(nblocks(nm, 4)), dim3(256), d_src, n, nm, (const CrcTables *)d_crc.p, stage.p, (int64_t)DFL_SLOT,
+              (const int64_t *)sizes.p);
+    if ((rc = sscan<1>(h, st, K_BGZF_SCAN, DflLdSize{sizes.p}, nm, o->moff.p, d_tot)) || (rc = read_home(h, &o->bytes, d_tot, 8)) ||
+        (rc = o->stream.alloc(h->device, o->bytes, h->stream)))
+        return rc;
+    FX_LAUNCH(h, K_BGZF_PACK, k_bgzf_pack, dim3((unsigned)std::min<int64_t>(nm, 8 * (int64_t)std::max(n_cu, 1))), dim3(BLOCK), (const uint8_t *)stage.p,
+              (const int64_t *)o->moff.p, nm, o->stream.p);
+    HIPCHK(hipGetLastError());
+    return FX_OK;
+}
+// What a _bgzf entry hands back beside its sibling's columns: the stream, its bytes, the member offsets (members + 1), their number.
+struct BgzfReq { int level; uint8_t **zdst; int64_t **member_off; int64_t *zbytes, *n_members; };
+static bool bgzf_req_ok(const BgzfReq &z) { return z.zdst && z.member_off && z.zbytes && z.n_members; }
+static void bgzf_req_clear(const BgzfReq &z) { *z.zdst = nullptr; *z.member_off = nullptr; *z.zbytes = 0; *z.n_members = 0; }
+// The compress step between a writer's emit and its copies home: `total` bytes of records at d_rec -> the stream and the member
+// table in pinned blocks of the caller's, with `extra` (the writer's own column) on the same wait.  Only compressed bytes and
+// tables cross the link.  total == 0: no member, one offset of 0.
+static int bgzf_home(fx_handle *h, Staged &st, const char *what, const uint8_t *d_rec, int64_t total, const BgzfReq &z, D2H extra) {
+    int rc;
+    BgzfDev o;
+    PinnedOut<2> out(h);                                   // the stream, the member offsets
+    if (total > 0 && (rc = bgzf_encode(h, st, d_rec, total, z.level, &o))) return rc;
+    if (!out.alloc(0, std::max<int64_t>(o.bytes, 1)) || !out.alloc(1, (o.members + 1) * 8))
+        return fail(FX_ENOMEM, "pinned blocks for %lld bytes of BGZF", (long long)o.bytes);
+    if (total == 0) out.as<int64_t>(1)[0] = 0;
+    if ((rc = home(h, what, {{out.p[0], o.stream.p, o.bytes}, {out.p[1], o.moff.p, total > 0 ? (o.members + 1) * 8 : 0}, extra}))) return rc;
+    out.release(z.zdst, z.member_off);
+    *z.zbytes = o.bytes;
+    *z.n_members = o.members;
+    return FX_OK;
+}
+
 // Variable-length records of n queries into pinned memory (*dst, their n + 1 offsets in *dst_off): count(sizes, bad flag) sizes
 // every record (0: dropped) and flags a query it rejects (-> *first_bad, bad_fmt); the scan under id_scan gives the offsets, the
 // bytes and the records there (-> *n_there), both enqueued home before the flag is waited for; emit(offsets, bytes) writes them.
 // The pinned blocks are taken only once the flag is clean.  n == 0: one offset of 0.
+// z (the _bgzf entries): the records stay on the device and go through bgzf_home instead; dst is not asked for then.
 template <class Count, class Emit>
 static int run_records(fx_handle *h, Staged &st, int64_t n, int id_scan, const char *what, const char *bad_fmt, Count count, Emit emit,
-                       uint8_t **dst, int64_t **dst_off, int64_t *n_there, int64_t *first_bad) {
+                       uint8_t **dst, int64_t **dst_off, int64_t *n_there, int64_t *first_bad, const BgzfReq *z = nullptr) {
     int rc;
     PinnedOut<2> out(h);                                   // the records, their offsets
     if (n == 0) {
-        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
+        if ((!z && !out.alloc(0, 1)) || !out.alloc(1, 16)) return FX_ENOMEM;
         out.as<int64_t>(1)[0] = 0;
+        if (z && (rc = bgzf_home(h, st, what, nullptr, 0, *z, D2H{nullptr, nullptr, 0}))) return rc;
     } else {
         ScratchBuf<int64_t> cnt, offs;                     // record sizes; exclusive offsets (n + 1), then the records there (n + 1)
         int64_t *d_tot = nullptr, tot[2] = {0, 0};
@@ -3597,11 +3667,13 @@ static int run_records(fx_handle *h, Staged &st, int64_t n, int id_scan, const c
         if ((rc = bad.read(h, first_bad))) return rc;
         if (*first_bad >= 0) return fail(FX_ERANGE, bad_fmt, (long long)*first_bad);
         const int64_t total = tot[0];
-        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
+        if ((!z && !out.alloc(0, std::max<int64_t>(total, 1))) || !out.alloc(1, (n + 1) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
         ScratchBuf<uint8_t> dev;
         if ((rc = dev.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return rc;
         if (total > 0) emit((const int64_t *)offs.p, dev.p);
-        if ((rc = home(h, what, {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}}))) return rc;
+        if (z) rc = bgzf_home(h, st, what, dev.p, total, *z, D2H{out.p[1], offs.p, (n + 1) * 8});
+        else rc = home(h, what, {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}});
+        if (rc) return rc;
         *n_there = tot[1];
     }
     out.release(dst, dst_off);
@@ -5031,10 +5103,14 @@ extern "C" int fx_fastq_trim(fx_handle *h, const int64_t *ids, int64_t n_ids, in
     return FX_OK;
 }
 
-extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
-                                     int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept, int64_t *first_bad) {
-    if (!h || !dst || !dst_off || !n_rows || !n_kept || !first_bad) return fail(FX_EINVAL, "null argument");
-    *dst = nullptr; *dst_off = nullptr; *n_rows = 0; *n_kept = 0; *first_bad = -1;
+// z: the _bgzf entry (dst is null then)
+static int fastq_format(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end, int64_t min_len, uint8_t **dst,
+                        int64_t **dst_off, int64_t *n_rows, int64_t *n_kept, int64_t *first_bad, const BgzfReq *z) {
+    if (!h || (!dst && !z) || !dst_off || !n_rows || !n_kept || !first_bad || (z && !bgzf_req_ok(*z))) return fail(FX_EINVAL, "null argument");
+    if (dst) *dst = nullptr;
+    *dst_off = nullptr; *n_rows = 0; *n_kept = 0; *first_bad = -1;
+    if (z) bgzf_req_clear(*z);
+    if (z && (z->level < 0 || z->level > 2)) return fail(FX_EINVAL, "level %d outside 0..2", z->level);
     if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
     if ((start == nullptr) != (end == nullptr)) return fail(FX_EINVAL, "start and end come together");
     if (min_len < 0) return fail(FX_EINVAL, "negative min_len");
@@ -5055,21 +5131,36 @@ extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n
         FX_LAUNCH(h, K_FQ_FORMAT_EMIT, k_fq_format_emit, dim3(nblocks(n, lane_groups(q.lpr))), dim3(BLOCK), v.data, v.base, v.n, v.soff, v.qoff, v.dlen,
                   Q.ids, n, Q.start, offs, q.lpr, dev);
     };
-    if ((rc = run_records(h, st, n, K_FQ_FORMAT_SCAN, "format", kBadInterval, count, emit, dst, dst_off, n_kept, first_bad))) return rc;
+    if ((rc = run_records(h, st, n, K_FQ_FORMAT_SCAN, "format", kBadInterval, count, emit, dst, dst_off, n_kept, first_bad, z))) return rc;
     *n_rows = n;
     return FX_OK;
+}
+extern "C" int fx_fastq_format_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end,
+                                     int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept, int64_t *first_bad) {
+    if (!dst) return fail(FX_EINVAL, "null argument");
+    return fastq_format(h, ids, n_ids, start, end, min_len, dst, dst_off, n_rows, n_kept, first_bad, nullptr);
+}
+extern "C" int fx_fastq_format_bgzf_alloc(fx_handle *h, const int64_t *ids, int64_t n_ids, const int64_t *start, const int64_t *end, int64_t min_len,
+                                          int level, uint8_t **zdst, int64_t **member_off, int64_t **dst_off, int64_t *n_rows, int64_t *n_kept,
+                                          int64_t *first_bad, int64_t *zbytes, int64_t *n_members) {
+    const BgzfReq z{level, zdst, member_off, zbytes, n_members};
+    return fastq_format(h, ids, n_ids, start, end, min_len, nullptr, dst_off, n_rows, n_kept, first_bad, &z);
 }
 
 // ------------------------------------------------------------------ FASTA records written back out (fx_fasta_format.hpp)
 // Extension: the reference has no counterpart (verbatim copies only, sequence.c:314-335).
 extern "C" int fx_fasta_format_tile(void) { return FAF_TILE; }
 
-extern "C" int fx_fasta_format_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop, int flags,
-                                     const uint8_t *flags_per_query, int64_t width, const uint8_t *hdr, const int64_t *hdr_off, int64_t n_mask,
-                                     const int64_t *mask_id, const int64_t *mask_start, const int64_t *mask_stop, int mask_mode, int mask_byte,
-                                     int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_kept, int64_t *n_bases, int64_t *first_bad) {
-    if (!h || !dst || !dst_off || !n_kept || !n_bases || !first_bad) return fail(FX_EINVAL, "null argument");
-    *dst = nullptr; *dst_off = nullptr; *n_kept = 0; *n_bases = 0; *first_bad = -1;
+// z: the _bgzf entry (dst is null then)
+static int fasta_format(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop, int flags,
+                        const uint8_t *flags_per_query, int64_t width, const uint8_t *hdr, const int64_t *hdr_off, int64_t n_mask,
+                        const int64_t *mask_id, const int64_t *mask_start, const int64_t *mask_stop, int mask_mode, int mask_byte,
+                        int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_kept, int64_t *n_bases, int64_t *first_bad, const BgzfReq *z) {
+    if (!h || (!dst && !z) || !dst_off || !n_kept || !n_bases || !first_bad || (z && !bgzf_req_ok(*z))) return fail(FX_EINVAL, "null argument");
+    if (dst) *dst = nullptr;
+    *dst_off = nullptr; *n_kept = 0; *n_bases = 0; *first_bad = -1;
+    if (z) bgzf_req_clear(*z);
+    if (z && (z->level < 0 || z->level > 2)) return fail(FX_EINVAL, "level %d outside 0..2", z->level);
     if (n < 0) return fail(FX_EINVAL, "negative query count");
     if ((start == nullptr) != (stop == nullptr)) return fail(FX_EINVAL, "start and stop come together");
     if (!seq_id && start) return fail(FX_EINVAL, "intervals need record ids");
@@ -5093,13 +5184,14 @@ extern "C" int fx_fasta_format_alloc(fx_handle *h, int64_t n, const int64_t *seq
     }
     width = std::min<int64_t>(width, 0x7FFFFFFFll);          // (no query holds more letters: one line either way)
     PinnedOut<2> out(h);                                   // the records, their offsets
+    Staged st(h);
     if (n == 0) {
-        if (!out.alloc(0, 1) || !out.alloc(1, 16)) return FX_ENOMEM;
+        if ((!z && !out.alloc(0, 1)) || !out.alloc(1, 16)) return FX_ENOMEM;
         out.as<int64_t>(1)[0] = 0;
+        if (z && (rc = bgzf_home(h, st, "formatted records", nullptr, 0, *z, D2H{nullptr, nullptr, 0}))) return rc;
         out.release(dst, dst_off);
         return FX_OK;
     }
-    Staged st(h);
     const int64_t hdr_bytes = hdr ? hdr_off[n] : 0;
     st.reserve_pin((seq_id ? n : 0) * 8 + (start ? 2 * n : 0) * 8 + (flags_per_query ? n : 0) + hdr_bytes + (hdr ? (n + 1) * 8 : 0) +
                    (masked ? n_mask * 24 : 0) + 8 * 256 + 1024);
@@ -5164,18 +5256,74 @@ extern "C" int fx_fasta_format_alloc(fx_handle *h, int64_t n, const int64_t *seq
         int64_t tot[3] = {0, 0, 0};
         if ((rc = sscan<3>(h, st, K_FA_FORMAT_SCAN, FafLdSize{cnt.p, desc.p}, n, offs.p, d_tot)) || (rc = read_home(h, tot, d_tot, 24))) return rc;
         const int64_t total = tot[0];
-        if (!out.alloc(0, std::max<int64_t>(total, 1)) || !out.alloc(1, (n + 2) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
+        if ((!z && !out.alloc(0, std::max<int64_t>(total, 1))) || !out.alloc(1, (n + 2) * 8)) return fail(FX_ENOMEM, "pinned blocks for %lld bytes of records", (long long)total);
         if ((rc = dev.alloc(h->device, std::max<int64_t>(total, 1), h->stream))) return rc;
         if (total > 0)
             FX_LAUNCH(h, K_FA_FORMAT_EMIT, k_fa_format_emit, dim3((unsigned)nblocks(total, FAF_TILE)), dim3(BLOCK), h->d_data, h->n, (const uint8_t *)letters.p, d_hdr,
                       (const FaFmtDesc *)desc.p, (const int64_t *)offs.p, n, total, width, d_ms, d_me, masked ? mask_mode : 0, mask_byte, (const uint8_t *)d_comp, dev.p, force.p, d_ctl + 1);
-        if ((rc = home(h, "formatted records", {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}, {ctl, d_ctl, (int64_t)sizeof ctl}}))) return rc;
+        if (z) {                                           // the records stay where they are: the flag first, then the compress step
+            if ((rc = read_home(h, ctl, d_ctl, (int64_t)sizeof ctl))) return rc;
+            if (!ctl[1] && (rc = bgzf_home(h, st, "formatted records", dev.p, total, *z, D2H{out.p[1], offs.p, (n + 1) * 8}))) return rc;
+        } else if ((rc = home(h, "formatted records", {{out.p[0], dev.p, total}, {out.p[1], offs.p, (n + 1) * 8}, {ctl, d_ctl, (int64_t)sizeof ctl}}))) return rc;
         if (!ctl[1]) { *n_kept = tot[1]; *n_bases = tot[2]; break; }
         if (round == 1) return fail(FX_EDEVICE, "formatted records: white space in despaced letters");
         fx_pinned_free(out.p[0]); fx_pinned_free(out.p[1]);
         out.p[0] = out.p[1] = nullptr;
     }
     out.release(dst, dst_off);
+    return FX_OK;
+}
+extern "C" int fx_fasta_format_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop, int flags,
+                                     const uint8_t *flags_per_query, int64_t width, const uint8_t *hdr, const int64_t *hdr_off, int64_t n_mask,
+                                     const int64_t *mask_id, const int64_t *mask_start, const int64_t *mask_stop, int mask_mode, int mask_byte,
+                                     int64_t min_len, uint8_t **dst, int64_t **dst_off, int64_t *n_kept, int64_t *n_bases, int64_t *first_bad) {
+    if (!dst) return fail(FX_EINVAL, "null argument");
+    return fasta_format(h, n, seq_id, start, stop, flags, flags_per_query, width, hdr, hdr_off, n_mask, mask_id, mask_start, mask_stop, mask_mode, mask_byte,
+                        min_len, dst, dst_off, n_kept, n_bases, first_bad, nullptr);
+}
+extern "C" int fx_fasta_format_bgzf_alloc(fx_handle *h, int64_t n, const int64_t *seq_id, const int64_t *start, const int64_t *stop, int flags,
+                                          const uint8_t *flags_per_query, int64_t width, const uint8_t *hdr, const int64_t *hdr_off, int64_t n_mask,
+                                          const int64_t *mask_id, const int64_t *mask_start, const int64_t *mask_stop, int mask_mode, int mask_byte,
+                                          int64_t min_len, int level, uint8_t **zdst, int64_t **member_off, int64_t **dst_off, int64_t *n_kept,
+                                          int64_t *n_bases, int64_t *first_bad, int64_t *zbytes, int64_t *n_members) {
+    const BgzfReq z{level, zdst, member_off, zbytes, n_members};
+    return fasta_format(h, n, seq_id, start, stop, flags, flags_per_query, width, hdr, hdr_off, n_mask, mask_id, mask_start, mask_stop, mask_mode, mask_byte,
+                        min_len, nullptr, dst_off, n_kept, n_bases, first_bad, &z);
+}
+
+// The bytes of a host buffer as BGZF (fx_deflate.hpp): staged, compressed, the stream and the members + 1 offsets of its members
+// home in pinned blocks (fx_pinned_free).  No EOF member: that is the file writer's.  A handle of its own for the call.
+extern "C" int fx_bgzf_compress(const uint8_t *src, int64_t n, int level, int device, uint8_t **dst, int64_t *dst_bytes, int64_t **member_off,
+                                int64_t *n_members) {
+    if (!dst || !dst_bytes || !member_off || !n_members) return fail(FX_EINVAL, "null argument");
+    *dst = nullptr; *dst_bytes = 0; *member_off = nullptr; *n_members = 0;
+    if (level < 0 || level > 2) return fail(FX_EINVAL, "level %d outside 0..2", level);
+    if (n < 0 || (n > 0 && !src)) return fail(FX_EINVAL, "bad buffer");
+    fx_handle *h = nullptr;
+    int rc = new_handle(device, &h);
+    if (rc) return rc;
+    {
+        Staged st(h);
+        ScratchBuf<uint8_t> d_in;
+        const BgzfReq z{level, dst, member_off, dst_bytes, n_members};
+        if (n > 0 && !(rc = d_in.alloc(h->device, n, h->stream))) {
+            const hipError_t e = hipMemcpyAsync(d_in.p, src, (size_t)n, hipMemcpyHostToDevice, h->stream);
+            if (e != hipSuccess) rc = fail(FX_EDEVICE, "H2D: %s", hipGetErrorString(e));
+        }
+        if (!rc) rc = bgzf_home(h, st, "bgzf compress", d_in.p, n, z, D2H{nullptr, nullptr, 0});
+    }
+    (void)fx_close(h);
+    return rc;
+}
+// dfl_huff on the host (pure: tests pin the length limit and Kraft's equality without a device); the ranking is dfl_rank's order
+extern "C" int fx_deflate_code_lengths(const uint32_t *freq, int nsym, int limit, uint8_t *lens, uint16_t *codes) {
+    if (!freq || !lens || !codes || nsym < 1 || nsym > 288 || limit < 1 || limit > 15) return fail(FX_EINVAL, "bad argument");
+    std::vector<uint16_t> srt;
+    for (int s = 0; s < nsym; ++s) if (freq[s]) srt.push_back((uint16_t)s);
+    if (((size_t)1 << limit) < srt.size()) return fail(FX_EINVAL, "%d symbols do not fit codes of %d bits", (int)srt.size(), limit);
+    std::sort(srt.begin(), srt.end(), [&](uint16_t a, uint16_t b) { return freq[a] != freq[b] ? freq[a] < freq[b] : a < b; });
+    DflHuffWork W;
+    dfl_huff(freq, nsym, srt.data(), (int)srt.size(), limit, lens, codes, &W);
     return FX_OK;
 }
 
@@ -5353,10 +5501,14 @@ extern "C" int fx_fastq_pair_overlap(fx_handle *h1, fx_handle *h2, const int64_t
     return FX_OK;
 }
 
-extern "C" int fx_fastq_pair_merge_alloc(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, const int32_t *diag, int64_t min_len,
-                                         uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_merged, int64_t *first_bad) {
-    if (!h1 || !h2 || !dst || !dst_off || !n_rows || !n_merged || !first_bad) return fail(FX_EINVAL, "null argument");
-    *dst = nullptr; *dst_off = nullptr; *n_rows = 0; *n_merged = 0; *first_bad = -1;
+// z: the _bgzf entry (dst is null then)
+static int pair_merge(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, const int32_t *diag, int64_t min_len, uint8_t **dst,
+                      int64_t **dst_off, int64_t *n_rows, int64_t *n_merged, int64_t *first_bad, const BgzfReq *z) {
+    if (!h1 || !h2 || (!dst && !z) || !dst_off || !n_rows || !n_merged || !first_bad || (z && !bgzf_req_ok(*z))) return fail(FX_EINVAL, "null argument");
+    if (dst) *dst = nullptr;
+    *dst_off = nullptr; *n_rows = 0; *n_merged = 0; *first_bad = -1;
+    if (z) bgzf_req_clear(*z);
+    if (z && (z->level < 0 || z->level > 2)) return fail(FX_EINVAL, "level %d outside 0..2", z->level);
     if (ids && n_ids < 0) return fail(FX_EINVAL, "negative id count");
     if (min_len < 0) return fail(FX_EINVAL, "negative min_len");
     FqLaunch q1, q2;
@@ -5378,10 +5530,21 @@ extern "C" int fx_fastq_pair_merge_alloc(fx_handle *h1, fx_handle *h2, const int
         FX_LAUNCH(h1, K_FP_MERGE_EMIT, k_fp_merge_emit, dim3(nblocks(n, lane_groups(lpr))), dim3(BLOCK), A, B, d_ids, n, d_diag, offs, lpr, dev);
     };
     if ((rc = run_records(h1, st, n, K_FP_MERGE_SCAN, "pair merge", "the diagonal of query %lld lies outside its pair", count, emit, dst, dst_off, n_merged,
-                          first_bad)))
+                          first_bad, z)))
         return rc;
     *n_rows = n;
     return FX_OK;
+}
+extern "C" int fx_fastq_pair_merge_alloc(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, const int32_t *diag, int64_t min_len,
+                                         uint8_t **dst, int64_t **dst_off, int64_t *n_rows, int64_t *n_merged, int64_t *first_bad) {
+    if (!dst) return fail(FX_EINVAL, "null argument");
+    return pair_merge(h1, h2, ids, n_ids, diag, min_len, dst, dst_off, n_rows, n_merged, first_bad, nullptr);
+}
+extern "C" int fx_fastq_pair_merge_bgzf_alloc(fx_handle *h1, fx_handle *h2, const int64_t *ids, int64_t n_ids, const int32_t *diag, int64_t min_len,
+                                              int level, uint8_t **zdst, int64_t **member_off, int64_t **dst_off, int64_t *n_rows,
+                                              int64_t *n_merged, int64_t *first_bad, int64_t *zbytes, int64_t *n_members) {
+    const BgzfReq z{level, zdst, member_off, zbytes, n_members};
+    return pair_merge(h1, h2, ids, n_ids, diag, min_len, nullptr, dst_off, n_rows, n_merged, first_bad, &z);
 }
 
 // ------------------------------------------------------------------ k-mer spectra (fx_kmer.hpp)

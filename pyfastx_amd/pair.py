@@ -47,12 +47,14 @@ def overlap_blob(blob1, blob2, n_reads, ids, args):
     return blob1.fastq_pair_overlap(blob2, ids, **args)
 
 
-def merge_blob(blob1, blob2, n_reads, ids, diag, min_len):
-    """-> (buffer, offsets, merged)"""
+def merge_blob(blob1, blob2, n_reads, ids, diag, min_len, level=None):
+    """-> (buffer, offsets, merged); with a BGZF level (bgzf.level_of): (stream, member offsets, offsets, merged)"""
     ids = _trim.check_ids(ids, n_reads)
     diag = check_diag(diag, n_reads if ids is None else ids.size)
     min_len = _trim._int(min_len, "min_len", 0)
     try:
+        if level is not None:
+            return blob1.fastq_pair_merge_alloc(blob2, diag, ids, min_len, level=level)
         return blob1.fastq_pair_merge_alloc(blob2, diag, ids, min_len)
     except _lib.FxError as e:
         raise _lib.outside(e, "diagonal", "pair")
@@ -163,10 +165,13 @@ class FastqPair:
         buf, offs, _ = merge_blob(b1, b2, n, ids, diag, min_len)
         return buf, offs
 
-    def write(self, path1, path2, ids=None, start1=None, end1=None, start2=None, end2=None, min_len=0, batch_bytes=1 << 30):
+    def write(self, path1, path2, ids=None, start1=None, end1=None, start2=None, end2=None, min_len=0, batch_bytes=1 << 30, compress=None):
         """Both mates through Fastq.write, in step: a pair is kept only when BOTH mates keep min_len bases of their interval
         (start / end of a mate both None: whole reads), and the two files get the same pairs in the same order ->
-        {"pairs": written, "bases1", "bases2", "dropped"}."""
+        {"pairs": written, "bases1", "bases2", "dropped"}.  compress: as Fastq.write takes it, for both files (their
+        "compressed_bytes" and "members" come back as pairs)."""
+        from . import bgzf
+        level = bgzf.level_of(compress)
         n_reads = self._blobs()[2]
         ids = _trim.check_ids(ids, n_reads)
         n = n_reads if ids is None else ids.size
@@ -177,11 +182,15 @@ class FastqPair:
         keep = kept_pairs(L1 if start1 is None else end1 - start1, L2 if start2 is None else end2 - start2, min_len)
         q = (np.arange(n, dtype=np.int64) if ids is None else ids)[keep]
         cut = lambda a: None if a is None else a[keep]
-        r1 = self.fq1.write(path1, ids=q, start=cut(start1), end=cut(end1), min_len=min_len, batch_bytes=batch_bytes)
-        r2 = self.fq2.write(path2, ids=q, start=cut(start2), end=cut(end2), min_len=min_len, batch_bytes=batch_bytes)
+        zk = {} if level is None else {"compress": level}       # (plain: the call as it always was)
+        r1 = self.fq1.write(path1, ids=q, start=cut(start1), end=cut(end1), min_len=min_len, batch_bytes=batch_bytes, **zk)
+        r2 = self.fq2.write(path2, ids=q, start=cut(start2), end=cut(end2), min_len=min_len, batch_bytes=batch_bytes, **zk)
         if r1["reads"] != r2["reads"] or r1["reads"] != q.size:
             raise RuntimeError("the two files fell out of step (%d, %d records for %d pairs)" % (r1["reads"], r2["reads"], q.size))
-        return {"pairs": int(q.size), "bases1": r1["bases"], "bases2": r2["bases"], "dropped": int(n - q.size)}
+        out = {"pairs": int(q.size), "bases1": r1["bases"], "bases2": r2["bases"], "dropped": int(n - q.size)}
+        if level is not None:
+            out.update({k: (r1[k], r2[k]) for k in ("compressed_bytes", "members")})
+        return out
 
     def demux(self, samples, mate=1, **demux_kwargs):
         """Fastq.demux on one mate (1 or 2) with its arguments -> demux.Demux; it remembers the mate for demux_write."""
@@ -191,11 +200,12 @@ class FastqPair:
         dm.mate = mate
         return dm
 
-    def demux_write(self, dm, pattern1, pattern2, unassigned=None, ambiguous=None, cut=False, min_len=0, batch_bytes=1 << 30):
+    def demux_write(self, dm, pattern1, pattern2, unassigned=None, ambiguous=None, cut=False, min_len=0, batch_bytes=1 << 30, compress=None):
         """Both mates of every bin of `dm` through write, in step: pattern1 / pattern2 hold "{sample}"; unassigned / ambiguous:
-        a pair of paths, or None to drop those pairs; cut=True takes the inline barcodes off the mate that was looked at ->
-        {name: (path1, path2, pairs written)}."""
-        from . import demux as _demux
+        a pair of paths, or None to drop those pairs; cut=True takes the inline barcodes off the mate that was looked at;
+        compress: as write takes it -> {name: (path1, path2, pairs written)}."""
+        from . import bgzf, demux as _demux
+        level = bgzf.level_of(compress)
         if not isinstance(dm, _demux.Demux) or (dm._ids is None and len(dm) != len(self)):
             raise ValueError("dm must be what demux returned for this pair")
         for extra in (unassigned, ambiguous):
@@ -211,14 +221,17 @@ class FastqPair:
             if pos.size == 0:
                 continue
             cutk = {} if start is None else {"start%d" % dm.mate: start[pos], "end%d" % dm.mate: end[pos]}
-            r = self.write(path1, path2, ids=pos if dm._ids is None else dm._ids[pos], min_len=min_len, batch_bytes=batch_bytes, **cutk)
+            r = self.write(path1, path2, ids=pos if dm._ids is None else dm._ids[pos], min_len=min_len, batch_bytes=batch_bytes, **cutk,
+                           **({} if level is None else {"compress": level}))
             out[key] = (path1, path2, r["pairs"])
         return out
 
-    def write_merged(self, path, ids=None, diag=None, min_len=0, batch_bytes=1 << 30):
+    def write_merged(self, path, ids=None, diag=None, min_len=0, batch_bytes=1 << 30, compress=None):
         """The records of merge written to the plain file `path`, in batches of consecutive queries whose upper bound fits
         batch_bytes of pinned memory -> {"merged": records written, "bases": their bases, "unmerged": the ids (int64) of the
-        queries that produced no record -- what write takes to keep them as pairs}."""
+        queries that produced no record -- what write takes to keep them as pairs}.  compress: as Fastq.write takes it."""
+        from . import bgzf
+        level = bgzf.level_of(compress)
         b1, b2, n_reads = self._blobs()
         ids = _trim.check_ids(ids, n_reads)
         n = n_reads if ids is None else ids.size
@@ -230,15 +243,21 @@ class FastqPair:
         merged = bases = 0
         rest = []
         with open(path, "wb") as f:
+            z = None if level is None else bgzf.Tally(f)
             for lo, hi in _trim.batches(bound, ids, n_reads, batch_bytes):
                 q = np.arange(lo, hi, dtype=np.int64) if ids is None else ids[lo:hi]
-                buf, offs, k = merge_blob(b1, b2, n_reads, q, diag[lo:hi], min_len)
-                f.write(memoryview(buf))
+                if z is None:
+                    buf, offs, k = merge_blob(b1, b2, n_reads, q, diag[lo:hi], min_len)
+                    f.write(memoryview(buf))
+                else:
+                    stream, moff, offs, k = merge_blob(b1, b2, n_reads, q, diag[lo:hi], min_len, level)
+                    z.add(stream, moff)
                 merged += k
                 there = np.diff(offs) > 0
                 L1, L2 = self._lengths(q)
                 bases += int(insert_of(diag[lo:hi], L1, L2)[there].sum())
                 rest.append(q[~there])
-        return {"merged": int(merged), "bases": int(bases), "unmerged": np.concatenate(rest) if rest else np.zeros(0, dtype=np.int64)}
+            tail = {} if z is None else z.finish()
+        return {"merged": int(merged), "bases": int(bases), "unmerged": np.concatenate(rest) if rest else np.zeros(0, dtype=np.int64), **tail}
 
     insert_histogram = staticmethod(insert_histogram)

@@ -92,12 +92,14 @@ def trim_blob(blob, n_reads, ids, phred, args):
     return {"start": start, "end": end}
 
 
-def records_blob(blob, n_reads, ids, start, end, min_len):
-    """-> (buffer, offsets, kept)"""
+def records_blob(blob, n_reads, ids, start, end, min_len, level=None):
+    """-> (buffer, offsets, kept); with a BGZF level (bgzf.level_of): (stream, member offsets, offsets, kept)"""
     ids = check_ids(ids, n_reads)
     start, end = check_intervals(start, end, n_reads if ids is None else ids.size)
     min_len = _int(min_len, "min_len", 0)
     try:
+        if level is not None:
+            return blob.fastq_format_alloc(ids, start, end, min_len, level=level)
         return blob.fastq_format_alloc(ids, start, end, min_len)
     except _lib.FxError as e:
         raise _lib.outside(e)
